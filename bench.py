@@ -96,7 +96,64 @@ def parse():
                          "other lane's kernels sharing the chip -- what roofline.achieved is measured on)")
     ap.add_argument("--breakdown", default=None, help="write a per-kernel-class time/FLOP/byte table (one extra, "
                                                        "untimed, fully instrumented step) to this file")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32; a fixed, seeded sample where an output is larger than the budget; rank 0 only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22  # elements sampled from the parameters and from the gradients (16 MB each in float32)
+DUMP_SEED = 3407
+
+
+def dump_outputs(dirname, arrays):
+    """Writes {name: tensor} as DIR/<name>.npy in float32 (float64 stays float64), at most DUMP_BUDGET_BYTES in all."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"[bench] dumped {len(host)} arrays ({total / 2**20:.1f} MB) to {dirname}", file=sys.stderr, flush=True)
+
+
+def seeded_sample(tensors, k=DUMP_SAMPLE, seed=DUMP_SEED):
+    """A fixed sample of the concatenation of `tensors` (each flattened in its logical, row-major element order, so the
+    sample does not depend on how a build lays its buffers out): the sorted distinct positions of k seeded draws, or every
+    element when there are no more than k."""
+    numels = [t.numel() for t in tensors]
+    total = sum(numels)
+    if total <= k:
+        return torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    pos = torch.randint(0, total, (k,), generator=torch.Generator().manual_seed(seed)).unique()
+    out, start = [], 0
+    for t, n in zip(tensors, numels):
+        lo, hi = torch.searchsorted(pos, torch.tensor([start, start + n]))
+        if hi > lo:
+            out.append(t.detach().reshape(-1)[(pos[lo:hi] - start).to(t.device)].float())
+        start += n
+    return torch.cat(out)
+
+
+def pretrain_outputs(trainer, model, loss):
+    """What one pre-training step hands its caller: the loss, the parameters it updated and the BatchNorm buffers it moved
+    (the model's own tensors, in named order), plus the gradients it computed (as the optimizer consumed them: in f16 mode
+    still multiplied by the loss scale).  Parameters and gradients share one seeded sample; the buffers go in whole."""
+    grads = trainer._engine().store.grad_views()
+    return {"loss": loss.reshape(-1),
+            "params": seeded_sample([p for _, p in model.named_parameters()]),
+            "grads": seeded_sample(grads),
+            "bn_buffers": torch.cat([b.detach().reshape(-1).float() for _, b in model.named_buffers()
+                                     if b.is_floating_point()])}
 
 
 def usable_cores():
@@ -172,7 +229,7 @@ def linear_probe_bench(args):
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
-        return loss
+        return loss, outs
 
     for _ in range(args.warmup):
         step()
@@ -181,10 +238,13 @@ def linear_probe_bench(args):
     ops.set_profiler(prof)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, outs = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     ops.set_profiler(None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(-1), **{f"logits_{i}": o for i, o in enumerate(outs)},
+                                         "params": seeded_sample([p for p in m.parameters() if p.requires_grad])})
     dom = prof.summary().get("conv_gemm_128x128", {"flops": 0.0, "ms": 0.0, "launches": 0})
     achieved = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
     peak = MFMA_PEAK_TFLOPS[args.dtype]
@@ -227,6 +287,8 @@ def inference_bench(args):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         ops.set_profiler(None)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {f"pred_{i}": p for i, p in enumerate(preds)})
     dom = prof.summary().get("conv_gemm_128x128", {"flops": 0.0, "ms": 0.0, "launches": 0})
     achieved = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
     peak = MFMA_PEAK_TFLOPS[args.dtype]
@@ -280,7 +342,7 @@ def mlc_train_bench(args):
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
-        return loss
+        return loss, preds
 
     for _ in range(args.warmup):
         step()
@@ -289,10 +351,13 @@ def mlc_train_bench(args):
     ops.set_profiler(prof)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, preds = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     ops.set_profiler(None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(-1), **{f"prototype_logits_{i}": p for i, p in enumerate(preds)},
+                                         "params": seeded_sample([p for p in m.parameters() if p.requires_grad])})
     # the per-epoch clustering: 8 spherical k-means (10 iterations each) over a 2048 x 512 memory bank
     nmem = 2048
     idx = torch.arange(nmem, device=dev)
@@ -435,10 +500,12 @@ def dry_run_rank(args):
         x = [torch.randn(2, 3, 32, 32, generator=g) for _ in range(4)]
         t0 = time.perf_counter()
         for _ in range(max(1, args.steps)):
-            trainer.step(x[:2], x[2:])
+            loss = trainer.step(x[:2], x[2:])
         if world > 1:
-            dist.barrier()
+            dist.all_reduce(torch.zeros(1))  # not barrier(): it probes the accelerator, i.e. opens the GPU
         mine = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, pretrain_outputs(trainer, model, loss))
         el = torch.tensor([mine], dtype=torch.float64)
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -570,6 +637,8 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     ops.set_profiler(None)
+    if args.dump_outputs and rank == 0:  # before the untimed steps below move the weights on
+        dump_outputs(args.dump_outputs, pretrain_outputs(trainer, model, loss))
     loss_val = float(loss)
     witness = dp_witness(world, backend if (world > 1 or force_dp) else "none", dev, elapsed, args.steps, trainer)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)

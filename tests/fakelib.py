@@ -34,6 +34,17 @@ class _FakeFn:
         return 0
 
 
+class _NoStreamScope:
+    """Stands in for ops.stream_scope, which asks torch for the current HIP stream: that initialises the HIP runtime and,
+    on a machine with a GPU, opens the device in every one of these CPU-only processes."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
 class FakeLib:
     def __init__(self):
         self.calls = []
@@ -48,7 +59,7 @@ class FakeLib:
 def installed():
     from sm3hip import _lib, ops
     fake = FakeLib()
-    saved = (_lib._lib, ops._chk, ops._stream)
+    saved = (_lib._lib, ops._chk, ops._stream, ops.stream_scope)
 
     def chk(t, dtype=None, name="tensor"):
         if t is None:
@@ -58,8 +69,8 @@ def installed():
         if dtype is not None and t.dtype != dtype:
             raise ValueError(f"{name}: expected {dtype}, got {t.dtype}")
 
-    _lib._lib, ops._chk, ops._stream = fake, chk, (lambda: None)
+    _lib._lib, ops._chk, ops._stream, ops.stream_scope = fake, chk, (lambda: None), _NoStreamScope
     try:
         yield fake
     finally:
-        _lib._lib, ops._chk, ops._stream = saved
+        _lib._lib, ops._chk, ops._stream, ops.stream_scope = saved

@@ -55,7 +55,9 @@ def _entry(fn, rank, world, port, q):
         torch.set_num_threads(4 if world <= 2 else 1)
         dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
         out = fn(rank, world)
-        dist.barrier()
+        # a collective on a CPU tensor instead of dist.barrier(): barrier() probes the accelerator, which initialises HIP and
+        # so opens the GPU in every rank of this CPU-only group on a machine that has one
+        dist.all_reduce(torch.zeros(1))
         dist.destroy_process_group()
         q.put((rank, True, out))
     except Exception:
