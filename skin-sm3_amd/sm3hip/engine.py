@@ -333,6 +333,7 @@ class SM3Engine:
         # (GPU test suite passes with it on) but measured slower -- 2 700 vs 2 780 pairs/s -- so off: two lanes
         # already keep HBM and MFMA busy, four only add contention
         self.view_lanes = _os.environ.get("SM3_VIEW_LANES", "0") == "1"
+        self._lane_g = {}  # view lane -> (its own gradient buffer, first slot): see _lane_grad_begin
         self._bn_ev = {}
         self._ordered_bn = False  # set while the two views of a branch run on two lanes
         self.side_wgrad = _os.environ.get("SM3_SIDE_WGRAD", "0") == "1"  # round 1: slower (2600 vs 2790 pairs/s); round 6, fixed-order sums on the side stream too: 4 631-4 651 vs 4 601-4 632 (+0.5 %, noise) on the default 4 hardware queues, 4 465 vs 4 590 with GPU_MAX_HW_QUEUES=8 -- stays opt-in
@@ -534,7 +535,35 @@ class SM3Engine:
         return self.store.flat2d(self.store.flat_p, name)
 
     def _g(self, name):
-        return self.store.flat2d(self.store.flat_g, name)
+        lg = self._lane_g.get(self._lane)
+        if lg is None:
+            return self.store.flat2d(self.store.flat_g, name)
+        buf, lo = lg  # a view lane's own gradient buffer over the slots [lo, lo + buf.numel()) of the flat one
+        shape, off = self.store.shapes[name], self.store.offsets[name] - lo
+        n = math.prod(shape)
+        if off < 0 or off + n > buf.numel():
+            raise RuntimeError(f"{name} is outside the gradient range of lane {self._lane}")
+        v = buf[off: off + n]
+        return v.view(shape[0], -1) if len(shape) >= 2 else v
+
+    # With SM3_VIEW_LANES=1 the two views of a branch run encoder_backward on two streams at once, and every gradient
+    # kernel adds into its target by read-modify-write (fixed-order slab sums, BatchNorm parameter sums): on one buffer the
+    # two lanes would lose each other's addends.  View lane #1 therefore accumulates into a buffer of its own, which is
+    # added into the flat gradient after the join, behind view 0's addends: a fixed order, so the step stays
+    # bit-reproducible.
+    def _lane_grad_begin(self, plan):
+        """On the current (view-1) lane: a zeroed private gradient buffer over the slots of `plan`'s parameters."""
+        names = [n for n in self.store.names if n.startswith(plan.prefix)]
+        lo = min(self.store.offsets[n] for n in names)
+        hi = max(self.store.offsets[n] + math.prod(self.store.shapes[n]) for n in names)
+        buf = self._work("lane_grad", hi - lo)[: hi - lo]
+        buf.zero_()
+        self._lane_g[self._lane] = (buf, lo)
+
+    def _lane_grad_end(self, lane):
+        """On the branch's lane, after it waited for `lane`: flat gradient += that lane's buffer."""
+        buf, lo = self._lane_g.pop(lane)
+        self.store.flat_g[lo: lo + buf.numel()].add_(buf)
 
     # ---- conv + BN (+residual) (+ReLU) ---------------------------------------------------
     def conv_bn(self, cu, bu, x, N, H, W, relu, residual=None, train=True, save=None, out_f32=False, y_out=None,
@@ -1150,10 +1179,12 @@ class SM3Engine:
                 return False
         return True
 
-    def encoder_forward(self, plan, x, train, feat_f32, feat_t, save=None, views=1):
+    def encoder_forward(self, plan, x, train, feat_f32, feat_t, save=None, views=1, taps=None):
         """x: NCHW fp32 [N,3,H,W] (as the loader delivers it, tools/backbone_train.py:89-92).
         Writes the pooled features into feat_f32 [N,2048] (fp32) and feat_t (dtype copy, optional).
-        views=2: x holds two views back to back (N = 2B), BatchNorm statistics per view."""
+        views=2: x holds two views back to back (N = 2B), BatchNorm statistics per view.
+        taps (tests): a dict that receives taps["x"] = [max-pool output, output of block 0, block 1, ...], clones of the
+        [N*H*W, C] `dtype` maps at every block boundary (views back to back).  None: nothing is recorded."""
         xs = list(x) if isinstance(x, (list, tuple)) else [x]  # the views of the batch, back to back
         if any(t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3 or t.shape != xs[0].shape for t in xs):
             raise ValueError("encoder input must be NCHW float32 with 3 channels")
@@ -1163,11 +1194,11 @@ class SM3Engine:
             x = xs[0]
         self._V = views if train else 1
         try:
-            self._encoder_forward(plan, x, train, feat_f32, feat_t, save)
+            self._encoder_forward(plan, x, train, feat_f32, feat_t, save, taps)
         finally:
             self._V = 1
 
-    def _encoder_forward(self, plan, x, train, feat_f32, feat_t, save):
+    def _encoder_forward(self, plan, x, train, feat_f32, feat_t, save, taps=None):
         if self.stem16:
             # 16-bit modes: the images are rounded ONCE (the rounding the stem kernels used to apply per staged tile, forward
             # and again in the weight gradient) into a row-padded 16-bit copy that both kernels stage by LDS-DMA; the views
@@ -1209,6 +1240,8 @@ class SM3Engine:
             ops.maxpool_fwd(self.dtype, y, p, N, Ho, Wo, 64, amax)
         del stem_in
         cur, h, w = p, Hp, Wp
+        if taps is not None:
+            taps["x"] = [p.clone()]
         block_recs = []
         # BatchNorm by linearity for conv3 -> bn3 (csrc/linbn.hip) needs two moments of conv3's input y2 per view: sum(y2),
         # which bn2's apply pass adds up on the side (per-block partial rows), and the Gram matrix y2^T y2, one launch of the
@@ -1262,6 +1295,8 @@ class SM3Engine:
                 y3, h3, w3 = self.join_fused(blk, br[1], y2, cur, N, h, w, h2, w2, br)
                 block_recs.append(br)
                 cur, h, w = y3, h3, w3
+                if taps is not None:
+                    taps["x"].append(cur.clone())
                 continue
             if "cd" in blk and lazy:
                 # downsample branch: convolution + statistics only; its BatchNorm is applied inside the join below
@@ -1284,22 +1319,36 @@ class SM3Engine:
                     br[-1].linbn = True  # backward of conv3 -> bn3 by linearity; needs br[1].colsum / .gram (moments of y2)
             block_recs.append(br)
             cur, h, w = y3, h3, w3
+            if taps is not None:
+                taps["x"].append(cur.clone())
         ops.avgpool_fwd(self.dtype, cur, feat_f32, feat_t, N, h * w, plan.out_dim)
         if save is not None:
             save.append({"plan": plan, "stem": recs[0], "stem_hw": (Ho, Wo), "pool_hw": (Hp, Wp), "argmax": amax,
                          "blocks": block_recs, "N": N, "last_hw": (h, w), "V": self._V})
 
-    def encoder_backward(self, ctx, dfeat, last_view=True):
+    def encoder_backward(self, ctx, dfeat, last_view=True, taps=None):
         """dfeat: [N,2048] `dtype` gradient of the pooled features.  On the last view of a step each stage's
         parameter gradients are final once its blocks are done: grad_ready fires per stage so the caller can
-        start that bucket's all-reduce while earlier stages are still computing."""
+        start that bucket's all-reduce while earlier stages are still computing.
+        taps (tests): a dict that receives taps["g"][i], a clone of the gradient arriving at the boundary of
+        encoder_forward's taps["x"][i] (complete: every addend is in), and taps["g_pre_relu"][i]: whether that
+        gradient is already masked by the ReLU of the block that produced taps["x"][i], i.e. taken with respect to
+        its pre-ReLU sum (out + identity) rather than its output.  The last block receives the un-masked pooled
+        gradient (False); an inner boundary whose gradient came out of a data-gradient launch with the previous
+        block's BatchNorm-backward phase 1 in its epilogue is masked (True), one that was summed without it is not;
+        the max-pool output has no ReLU after it (False).  None: nothing is recorded."""
         plan, N = ctx["plan"], ctx["N"]
         h, w = ctx["last_hw"]
         dcur = torch.empty(N * h * w, plan.out_dim, dtype=self.tdt, device=dfeat.device)
         ops.avgpool_bwd(self.dtype, dfeat, dcur, N, h * w, plan.out_dim)
         fr = None  # rows of fused BN-backward partials that came with dcur
+        if taps is not None:
+            taps["g"] = [None] * (len(plan.blocks) + 1)
+            taps["g_pre_relu"] = [False] * (len(plan.blocks) + 1)
         for bi in range(len(plan.blocks) - 1, -1, -1):
             blk, br = plan.blocks[bi], ctx["blocks"][bi]
+            if taps is not None:  # before this block's first kernel, which masks dcur in place when fr is None
+                taps["g"][bi + 1], taps["g_pre_relu"][bi + 1] = dcur.clone(), fr is not None
             if "cd" in blk:
                 r1, r2, rd, r3 = br
             else:
@@ -1381,6 +1430,8 @@ class SM3Engine:
             if last_view and "cd" in blk and bi > 0:  # first block of a stage: the stage is complete
                 stage = blk["c1"].name.rsplit(".", 2)[0]  # e.g. derm_backbone.encoder.layer4
                 self._notify(stage + ".", stage + ".")
+        if taps is not None:
+            taps["g"][0] = dcur.clone()  # the gradient of the max-pool output (not masked: maxpool_bn_bwd applies the mask)
         # maxpool -> stem BN/ReLU -> stem weight gradient (no data gradient: the image needs none)
         Ho, Wo = ctx["stem_hw"]
         rs = ctx["stem"]
@@ -1609,6 +1660,8 @@ class SM3Engine:
                 continue
             for v in (1, 0):
                 with self.lane(key + "#1" if (split and v == 1) else key, streams):
+                    if split and v == 1:
+                        self._lane_grad_begin(plan)
                     # with the views on two lanes a stage's gradients are final only when BOTH are done: the
                     # per-stage notifications of the last view are replaced by one round after the join below
                     self.encoder_backward(saved[key]["enc"][v], dfe[key][v * B:(v + 1) * B],
@@ -1618,6 +1671,7 @@ class SM3Engine:
             if split:
                 with self.lane(key, streams):
                     torch.cuda.current_stream().wait_stream(streams[key + "#1"])
+                    self._lane_grad_end(key + "#1")
                     for li in (4, 3, 2):
                         self._notify(f"{plan.prefix}layer{li}.", f"{plan.prefix}layer{li}.")
                     self._notify(plan.prefix + "conv1", plan.prefix + "layer1.")
