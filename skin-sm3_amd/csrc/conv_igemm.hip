@@ -579,7 +579,9 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
                 }
                 eoff[k] = (uint32_t)((opix * p.Co + ncol) * 2);  // tensors stay below 3 GB (host check)
                 if (p.addend) {
-                    if (p.add_sp_h) {  // compact stride-2 addend: present at even (y, x) only
+                    if (p.add_sp_h && !dense_out) {  // compact addend on the (0, 0) parity class: row m of the GEMM (host check)
+                        pre_add[k] = ldg16<true>(p.addend + ((long)m * p.Co + ncol) * 2);
+                    } else if (p.add_sp_h) {  // compact stride-2 addend: present at even (y, x) only
                         if (((oy | ox) & 1) == 0)
                             pre_add[k] = ldg16<true>(p.addend + ((((long)nn * p.add_sp_h + (oy >> 1)) * p.add_sp_w + (ox >> 1)) * p.Co + ncol) * 2);
                     } else {
@@ -919,7 +921,9 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
                 }
                 e_off[k] = opix * p.Co + ncol;
                 if (p.addend) {
-                    if (p.add_sp_h) {  // compact stride-2 addend: present at even (y, x) only (dense output)
+                    if (p.add_sp_h && !dense) {  // compact addend on the (0, 0) parity class: row m of the GEMM (host check)
+                        pre_add[k] = ldg16<true>(p.addend + ((long)m * p.Co + ncol) * SZ);
+                    } else if (p.add_sp_h) {  // compact stride-2 addend: present at even (y, x) only (dense output)
                         const int nn = fdiv(m, p.div_HoWo);
                         const int rem = m - nn * p.HoWo;
                         const int oy = fdiv(rem, p.div_Wo);
@@ -1322,8 +1326,16 @@ static int conv_gather_gemm_impl(const sm3_conv_desc* d, const void* x, const vo
     p.fz_row_off1 = 0;
     p.add_sp_h = p.add_sp_w = 0;
     if (fuse && fuse->addend_sp_h > 0) {
+        // Two layouts of a compact stride-2 addend [N][Hs][Ws][Co], told apart by the descriptor:
+        //  - dense output (a 1x1 / stride-1 data gradient): present at the even (y, x) of the output grid, Hs = ceil(Ho / 2);
+        //  - the (0, 0) parity class of a stride-2 data gradient (osy = osx = 2, ooy = oox = 0): the class's own Ho x Wo grid
+        //    is the even pixels, so the addend is row-aligned with the GEMM (Hs = Ho) and read at row m.
+        // The other three classes touch no even pixel and take no compact addend.
         const bool dense = d->osy == 1 && d->osx == 1 && d->ooy == 0 && d->oox == 0 && d->Hout == d->Ho && d->Wout == d->Wo;
-        if (!addend || !dense || fuse->addend_sp_h != (d->Ho + 1) / 2 || fuse->addend_sp_w != (d->Wo + 1) / 2) return SM3_EINVAL;
+        const bool even_class = d->osy == 2 && d->osx == 2 && d->ooy == 0 && d->oox == 0;
+        if (!addend || !(dense || even_class)) return SM3_EINVAL;
+        if (dense && (fuse->addend_sp_h != (d->Ho + 1) / 2 || fuse->addend_sp_w != (d->Wo + 1) / 2)) return SM3_EINVAL;
+        if (even_class && (fuse->addend_sp_h != d->Ho || fuse->addend_sp_w != d->Wo)) return SM3_EINVAL;
         p.add_sp_h = fuse->addend_sp_h;
         p.add_sp_w = fuse->addend_sp_w;
     }

@@ -82,7 +82,7 @@ class _EncoderFn(torch.autograd.Function):
 
 
 def encoder_features(resnet, x):
-    """conv1 ... avgpool + flatten of a bare ResNet on the HIP engine: [N,2048] fp32."""
+    """conv1 ... avgpool + flatten of a bare ResNet on the HIP engine: [N, 512 * expansion] fp32 (512 or 2048)."""
     eng = encoder_engine_for(resnet)
     if _needs_grad(resnet):
         return _EncoderFn.apply(eng, "main", resnet.training, x, *_params(resnet))

@@ -219,25 +219,40 @@ class Rec:
 
 
 class EncoderPlan:
-    def __init__(self, prefix, block_counts=(3, 4, 6, 3)):
+    """Units of a torchvision ResNet encoder.  block="bottleneck": c1 (1x1) / b1, c2 (3x3, stride s) / b2, c3 (1x1, x4) /
+    b3 per block; block="basic" (resnet18/34): c1 (3x3, stride s) / b1, c2 (3x3) / b2.  cd / bd (1x1 downsample, stride
+    s) where the block changes the stride or the width (reference resnet.py:251-262) -- every stage entry of a Bottleneck
+    network, layer2..4 of a BasicBlock one.  The last unit of a block is always its join (bn + identity + ReLU)."""
+
+    def __init__(self, prefix, block_counts=(3, 4, 6, 3), block="bottleneck"):
+        if block not in ("bottleneck", "basic"):
+            raise ValueError(block)
         self.prefix = prefix
+        self.basic = block == "basic"
         self.stem = ConvUnit(prefix + "conv1", 3, 64, 7, 2, 3, stem=True)
         self.stem_bn = BNUnit(prefix + "bn1", 64)
         self.blocks = []
+        exp = 1 if self.basic else 4
         inpl = 64
         for li, ((planes, _, stride), nblocks) in enumerate(zip(RESNET50_LAYERS, block_counts), start=1):
             for b in range(nblocks):
                 p = f"{prefix}layer{li}.{b}."
                 s = stride if b == 0 else 1
-                blk = {
-                    "c1": ConvUnit(p + "conv1", inpl, planes, 1, 1, 0), "b1": BNUnit(p + "bn1", planes),
-                    "c2": ConvUnit(p + "conv2", planes, planes, 3, s, 1), "b2": BNUnit(p + "bn2", planes),
-                    "c3": ConvUnit(p + "conv3", planes, planes * 4, 1, 1, 0), "b3": BNUnit(p + "bn3", planes * 4),
-                }
-                if b == 0:
-                    blk["cd"] = ConvUnit(p + "downsample.0", inpl, planes * 4, 1, s, 0)
-                    blk["bd"] = BNUnit(p + "downsample.1", planes * 4)
-                    inpl = planes * 4
+                if self.basic:
+                    blk = {
+                        "c1": ConvUnit(p + "conv1", inpl, planes, 3, s, 1), "b1": BNUnit(p + "bn1", planes),
+                        "c2": ConvUnit(p + "conv2", planes, planes, 3, 1, 1), "b2": BNUnit(p + "bn2", planes),
+                    }
+                else:
+                    blk = {
+                        "c1": ConvUnit(p + "conv1", inpl, planes, 1, 1, 0), "b1": BNUnit(p + "bn1", planes),
+                        "c2": ConvUnit(p + "conv2", planes, planes, 3, s, 1), "b2": BNUnit(p + "bn2", planes),
+                        "c3": ConvUnit(p + "conv3", planes, planes * 4, 1, 1, 0), "b3": BNUnit(p + "bn3", planes * 4),
+                    }
+                if s != 1 or inpl != planes * exp:
+                    blk["cd"] = ConvUnit(p + "downsample.0", inpl, planes * exp, 1, s, 0)
+                    blk["bd"] = BNUnit(p + "downsample.1", planes * exp)
+                    inpl = planes * exp
                 self.blocks.append(blk)
         self.out_dim = inpl
 
@@ -267,7 +282,12 @@ class ProjectorPlan:
 # the engine
 # ------------------------------------------------------------------------------------------
 def enc_mod_out_dim(enc_mod):
-    return 512 * 4
+    """Width of the pooled features of a src.models.resnet.ResNet: 512 (BasicBlock) or 2048 (Bottleneck)."""
+    return 512 if enc_block(enc_mod) == "basic" else 512 * 4
+
+
+def enc_block(enc_mod):
+    return getattr(enc_mod, "block_type", "bottleneck")
 
 
 class SM3Engine:
@@ -302,21 +322,22 @@ class SM3Engine:
             proj_dim = module.proj_dim
             for key in ("derm", "clinic"):
                 enc_mod = getattr(module, key + "_backbone").encoder
-                self.branches[key] = (EncoderPlan(f"{key}_backbone.encoder.", enc_mod.block_counts),
+                self.branches[key] = (EncoderPlan(f"{key}_backbone.encoder.", enc_mod.block_counts, enc_block(enc_mod)),
                                       ProjectorPlan(f"{key}_backbone.projector.", enc_mod_out_dim(enc_mod), proj_dim))
+            dims = [self.branches[k][0].out_dim for k in ("derm", "clinic")]
             if kind == "v3":
-                cp = ProjectorPlan("cross_proj.", 2048, proj_dim)
+                cp = ProjectorPlan("cross_proj.", dims[0], proj_dim)
                 self.cross = (cp, cp)
             else:
-                self.cross = (ProjectorPlan("cross_proj.0.", 2048, proj_dim),
-                              ProjectorPlan("cross_proj.1.", 2048, proj_dim))
+                self.cross = (ProjectorPlan("cross_proj.0.", dims[0], proj_dim),
+                              ProjectorPlan("cross_proj.1.", dims[1], proj_dim))
             if getattr(module, "meta_proj", None) is not None:  # metadata-MLP extension (src/models/simclr.py)
                 self.meta = ProjectorPlan("meta_proj.", module.meta_proj[0].in_features, proj_dim)
         elif kind == "simclr":
-            self.branches["main"] = (EncoderPlan("encoder.", module.encoder.block_counts),
+            self.branches["main"] = (EncoderPlan("encoder.", module.encoder.block_counts, enc_block(module.encoder)),
                                      ProjectorPlan("projector.", module.encoder_out_dim, module.proj_dim))
         elif kind == "encoder":
-            self.branches["main"] = (EncoderPlan("", module.block_counts), None)
+            self.branches["main"] = (EncoderPlan("", module.block_counts, enc_block(module)), None)
         else:
             raise ValueError(kind)
         self._ws = {}
@@ -1148,11 +1169,15 @@ class SM3Engine:
                 per_view = total // V
                 off = 0
                 for dd in descs:
+                    add, sp = addend, addend_sparse
+                    if sp is not None and len(descs) > 1 and (dd.ooy, dd.oox) != (0, 0):
+                        # parity classes of a stride-2 data gradient: a compact (even-pixel) addend belongs to class (0, 0)
+                        add = sp = None
                     # a unit whose backward goes by linearity (Rec.linbn) needs no sum(dz * xhat) from here: its
                     # pre-BatchNorm tensor is not read
-                    n = ops.conv_dgrad_bnfuse(dd, dxo, cu.w_dgrad, dx, addend, fuse.mask if fuse.relu else None,
+                    n = ops.conv_dgrad_bnfuse(dd, dxo, cu.w_dgrad, dx, add, fuse.mask if fuse.relu else None,
                                               None if fuse.linbn else fuse.xo, fuse.mean, fuse.invstd, part, off, views=V,
-                                              row_offset_view1=per_view + off, addend_sparse=addend_sparse)
+                                              row_offset_view1=per_view + off, addend_sparse=sp)
                     off += n // V
                 return dx, off
             if addend_sparse is not None:
@@ -1248,10 +1273,34 @@ class SM3Engine:
         # weight-gradient kernel on y2 alone (plain-store split-K slabs); sm3_linbn_moments adds both up in a fixed order,
         # so the forward pass stays bit-reproducible.
         Vt = self._V if train else 1
-        lin_ok = [self.linbn and train and save is not None and b["c3"].Co % 128 == 0 and b["c3"].Ci % 64 == 0
+        lin_ok = [self.linbn and train and save is not None and "c3" in b and b["c3"].Co % 128 == 0 and b["c3"].Ci % 64 == 0
                   for b in plan.blocks]
         for bi, (blk, lin) in enumerate(zip(plan.blocks, lin_ok)):
             br = [] if save is not None else None
+            if plan.basic:
+                # BasicBlock (reference resnet.py:91-106): conv1 -> bn1 -> relu -> conv2 -> bn2 (+identity) -> relu.  Both
+                # convolutions are 3x3, so none of the by-linearity forms (1x1 only) applies; a downsample branch stops after
+                # its statistics and is normalised inside the join, as in the two-pass Bottleneck join.  Saved units:
+                # [conv1, (downsample,) conv2] -- the join is last, as in a Bottleneck.
+                y1, h1, w1 = self.conv_bn(blk["c1"], blk["b1"], cur, N, h, w, True, None, train, br)
+                ra = pend = None
+                if "cd" in blk and lazy:
+                    ra = (self._work("scale_d", 2 * 2048), self._work("shift_d", 2 * 2048))
+                    pend = [] if (train and self.stat_sync is not None) else None
+                    idn, _, _ = self.conv_bn(blk["cd"], blk["bd"], cur, N, h, w, False, None, train, br, apply=False,
+                                             scale_shift=ra, pending=pend)
+                elif "cd" in blk:
+                    idn, _, _ = self.conv_bn(blk["cd"], blk["bd"], cur, N, h, w, False, None, train, br)
+                else:
+                    idn = cur  # layer1: the max-pool output, or the previous block's output
+                y2, h2, w2 = self.conv_bn(blk["c2"], blk["b2"], y1, N, h1, w1, True, idn, train, br, res_affine=ra,
+                                          pending=pend)
+                del y1, idn
+                block_recs.append(br)
+                cur, h, w = y2, h2, w2
+                if taps is not None:
+                    taps["x"].append(cur.clone())
+                continue
             # conv1 -> bn1 -> relu -> conv2 (resnet.py:144-150).  Where conv2 runs on the halo-resident kernel, bn1's apply +
             # ReLU happens on conv2's staged input image: conv1 stops after its statistics, conv2 reads conv1's RAW output
             # and writes the activation + ReLU bits that its weight gradient and bn1's backward need on the side
@@ -1349,39 +1398,52 @@ class SM3Engine:
             blk, br = plan.blocks[bi], ctx["blocks"][bi]
             if taps is not None:  # before this block's first kernel, which masks dcur in place when fr is None
                 taps["g"][bi + 1], taps["g_pre_relu"][bi + 1] = dcur.clone(), fr is not None
-            if "cd" in blk:
-                r1, r2, rd, r3 = br
-            else:
-                (r1, r2, r3), rd = br, None
-            if r3.linbn:
-                # conv3 -> bn3 by linearity: dz (dcur, masked) feeds the weight- and data-gradient GEMMs as it is
-                if fr is None:  # last block: dcur is the un-masked gradient from the pooling layer
-                    C3, V3 = r3.cu.Co, r3.V
-                    rows3 = r3.N * r3.Ho * r3.Wo // V3
-                    prow = ops.bn_bwd_partial_rows(rows3, C3)
-                    bpart = self._work("partials", V3 * prow * 2 * C3)
-                    ops.bn_bwd_reduce(self.dtype, dcur, None, r3.xo, r3.mean, r3.invstd, dcur, rows3, C3, bpart,
-                                      mask=r3.mask, views=V3)
-                else:
-                    prow, bpart = fr, self._ws[(self._lane, "fz_partials")]
-                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 else None
-                lin_d = rd is not None and (rd.linbn or (
-                    self.linbn_ds and rd.cu.Ci % 64 == 0 and not rd.frozen_stats and
-                    (rd.cu.stride == 1 or (prev_r3 is not None and self.fuse_bn_bwd and rd.cu.stride == 2 and
-                                           (prev_r3.V == 1 or (r1.N * r1.H * r1.W) % 256 == 0)))))
-                dy2, fr2, dxd = self.conv3_backward_linbn(r3, r2, dcur, bpart, prow, rd=rd, lin_d=lin_d)
-                dz = None if rd is not None else dcur
-            else:
-                if rd is not None:
-                    dx3, dxd = self.bn_backward_join(r3, rd, dcur, fused_rows=fr)
+            if plan.basic:
+                # BasicBlock: the join's BatchNorm(s), conv2 with bn1's phase 1 in its epilogue, bn1; conv1's data gradient
+                # below takes the identity gradient (or the downsample's compact one) as its addend
+                if "cd" in blk:
+                    r1, rd, r2 = br
+                    dx2, dxd = self.bn_backward_join(r2, rd, dcur, fused_rows=fr)
                     dz = None
                 else:
-                    dx3, dz = self.bn_backward(r3, dcur, keep_dz=True, fused_rows=fr)
-                dy2, fr2 = self.conv_backward(r3, dx3, fuse=r2)
-                del dx3
-            dx2, _ = self.bn_backward(r2, dy2, keep_dz=False, fused_rows=fr2)
-            dy1, fr1 = self.conv_backward(r2, dx2, fuse=r1)
-            del dx2, dy2
+                    (r1, r2), rd = br, None
+                    dx2, dz = self.bn_backward(r2, dcur, keep_dz=True, fused_rows=fr)
+                dy1, fr1 = self.conv_backward(r2, dx2, fuse=r1)
+                del dx2
+            else:
+                if "cd" in blk:
+                    r1, r2, rd, r3 = br
+                else:
+                    (r1, r2, r3), rd = br, None
+                if r3.linbn:
+                    # conv3 -> bn3 by linearity: dz (dcur, masked) feeds the weight- and data-gradient GEMMs as it is
+                    if fr is None:  # last block: dcur is the un-masked gradient from the pooling layer
+                        C3, V3 = r3.cu.Co, r3.V
+                        rows3 = r3.N * r3.Ho * r3.Wo // V3
+                        prow = ops.bn_bwd_partial_rows(rows3, C3)
+                        bpart = self._work("partials", V3 * prow * 2 * C3)
+                        ops.bn_bwd_reduce(self.dtype, dcur, None, r3.xo, r3.mean, r3.invstd, dcur, rows3, C3, bpart,
+                                          mask=r3.mask, views=V3)
+                    else:
+                        prow, bpart = fr, self._ws[(self._lane, "fz_partials")]
+                    prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 else None
+                    lin_d = rd is not None and (rd.linbn or (
+                        self.linbn_ds and rd.cu.Ci % 64 == 0 and not rd.frozen_stats and
+                        (rd.cu.stride == 1 or (prev_r3 is not None and self.fuse_bn_bwd and rd.cu.stride == 2 and
+                                               (prev_r3.V == 1 or (r1.N * r1.H * r1.W) % 256 == 0)))))
+                    dy2, fr2, dxd = self.conv3_backward_linbn(r3, r2, dcur, bpart, prow, rd=rd, lin_d=lin_d)
+                    dz = None if rd is not None else dcur
+                else:
+                    if rd is not None:
+                        dx3, dxd = self.bn_backward_join(r3, rd, dcur, fused_rows=fr)
+                        dz = None
+                    else:
+                        dx3, dz = self.bn_backward(r3, dcur, keep_dz=True, fused_rows=fr)
+                    dy2, fr2 = self.conv_backward(r3, dx3, fuse=r2)
+                    del dx3
+                dx2, _ = self.bn_backward(r2, dy2, keep_dz=False, fused_rows=fr2)
+                dy1, fr1 = self.conv_backward(r2, dx2, fuse=r1)
+                del dx2, dy2
             dx1, _ = self.bn_backward(r1, dy1, keep_dz=False, fused_rows=fr1)
             if rd is not None and isinstance(dxd, dict):
                 # the downsample unit went by linearity: its data gradient is the two-segment product of dz (= dcur) and the
@@ -1406,12 +1468,15 @@ class SM3Engine:
                 cd = rd.cu
                 V = prev_r3.V if prev_r3 is not None else 1
                 if (prev_r3 is not None and self.fuse_bn_bwd and cd.stride == 2
-                        and (V == 1 or (r1.N * r1.H * r1.W) % 256 == 0)):
+                        and (V == 1 or all((dd.N * dd.Ho * dd.Wo) % 256 == 0
+                                           for dd in r1.cu.dgrad_descs(self.dtype, r1.N, r1.H, r1.W)[0]))):
                     # Join of the two data gradients of a stride-2 downsample block WITHOUT a second pass over the
                     # block-input gradient: the downsample convolution's data gradient is computed first, compact (it
                     # only exists at the even pixels), and conv1's data gradient takes it as a sparse addend -- so that
                     # launch sees the complete gradient of the previous block's output and runs that block's
-                    # BatchNorm-backward phase 1 in its epilogue, like every other block boundary.
+                    # BatchNorm-backward phase 1 in its epilogue, like every other block boundary.  A BasicBlock's conv1
+                    # is the 3x3 / stride-2 one: its data gradient is four parity-class launches, and the compact addend
+                    # goes to the (0, 0) class, whose rows are exactly the downsample's pixels.
                     self._wgrad(cd, rd, dxd)
                     hs, ws = rd.Ho, rd.Wo
                     dd = cd.compact_dgrad_desc(self.dtype, rd.N, hs, ws)

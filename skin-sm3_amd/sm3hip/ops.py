@@ -217,7 +217,12 @@ def conv_dgrad_bnfuse(desc, dy_in, w_dgrad, dz_out, addend, mask, bn_x, mean, in
         raise ValueError("dz_out / bn_x size does not match descriptor")
     if addend_sparse is not None:  # compact [N, Hs, Ws, Co] addend for the even output positions
         hs, ws = addend_sparse
-        if addend is None or (hs, ws) != ((desc.Ho + 1) // 2, (desc.Wo + 1) // 2) or \
+        dense = (desc.osy, desc.osx, desc.ooy, desc.oox) == (1, 1, 0, 0) and (desc.Hout, desc.Wout) == (desc.Ho, desc.Wo)
+        # dense output: the addend covers the even pixels of the launch's grid; the (0, 0) parity class of a stride-2 data
+        # gradient: the launch's own grid IS the even pixels, so the addend has its shape
+        want = ((desc.Ho + 1) // 2, (desc.Wo + 1) // 2) if dense else (desc.Ho, desc.Wo)
+        even_class = (desc.osy, desc.osx, desc.ooy, desc.oox) == (2, 2, 0, 0)
+        if addend is None or (not dense and not even_class) or (hs, ws) != want or \
                 addend.numel() != desc.N * hs * ws * desc.Co:
             raise ValueError("sparse addend size does not match descriptor")
     elif addend is not None and addend.numel() != n_out:

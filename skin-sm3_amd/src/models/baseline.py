@@ -10,20 +10,32 @@ are not on the SM3 path.
 import torch
 import torch.nn as nn
 
-from .resnet import resnet50, resnet101, resnet152
+from .resnet import resnet18, resnet34, resnet50, resnet101, resnet152
 
 NUM_CLASSES = [5, 3, 2, 3, 3, 3, 3, 2]  # DIAG, PN, BWV, VS, PIG, STR, DaG, RS (backbone_eval.py:60-62)
 
 
+_REFERENCE_DEFAULT = object()
+
+
 class Baseline(nn.Module):
-    def __init__(self, arch="resnet50", weights=None):
+    def __init__(self, arch="resnet50", weights=_REFERENCE_DEFAULT):
+        """weights: None (random initialisation), a state_dict path, or a torchvision enum name served from the local
+        torch-hub cache (src/models/resnet.py).  Left out, it is None for the Bottleneck archs -- this mirror's default
+        since it was built -- and, for the BasicBlock archs, the reference's own default (baseline.py:61,
+        weights="IMAGENET1K_V1"): Baseline("resnet18") means ImageNet-pretrained encoders there, and without the cached
+        file that raises NotImplementedError here instead of silently training from random weights.
+        tools/backbone_eval.py always passes weights explicitly (--arch-weights, default None)."""
         super().__init__()
-        ctor = {"resnet50": resnet50, "resnet101": resnet101, "resnet152": resnet152}.get(arch)
+        ctor = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "resnet101": resnet101,
+                "resnet152": resnet152}.get(arch)
         if ctor is None:
-            raise NotImplementedError(f"arch {arch!r}: the SM3 HIP engine implements Bottleneck ResNets")
+            raise NotImplementedError(f"arch {arch!r}: the SM3 HIP engine implements the torchvision ResNets")
+        if weights is _REFERENCE_DEFAULT:
+            weights = "IMAGENET1K_V1" if arch in ("resnet18", "resnet34") else None
         self.derm_backbone = ctor(weights=weights)
         self.clinic_backbone = ctor(weights=weights)
-        feat_dim = 2048 * 2
+        feat_dim = self.derm_backbone.fc.in_features * 2  # 512 * 2 (resnet18/34) or 2048 * 2
         self.derm_backbone.fc = nn.Identity()
         self.clinic_backbone.fc = nn.Identity()
         self.classifier = nn.ModuleList([nn.Linear(feat_dim, n) for n in NUM_CLASSES])

@@ -1,13 +1,13 @@
 """ResNet encoders on the SM3 HIP engine -- drop-in for the reference's src/models/resnet.py.
 
-Same public surface as the reference file (resnet.py:177-329, 724-751): `ResNet`, `Bottleneck`,
-`resnet50/101/152(weights=None, progress=True, **kwargs)`, attribute names (`conv1, bn1, relu, maxpool,
+Same public surface as the reference file (resnet.py:177-329, 680-751): `ResNet`, `BasicBlock`, `Bottleneck`,
+`resnet18/34/50/101/152(weights=None, progress=True, **kwargs)`, attribute names (`conv1, bn1, relu, maxpool,
 layer1..4, avgpool, fc`) and therefore the same state_dict keys, Kaiming fan_out initialisation
 (resnet.py:227-232) and `zero_init_residual`.  The nn.Conv2d / nn.BatchNorm2d children are parameter
 containers only: `forward` runs the hand-written gfx950 kernels through sm3hip.engine (stem im2col +
 MFMA GEMM, gather-GEMM convolutions with BN-statistics epilogues, fused BN/residual/ReLU, pooling).
-No torchvision dependency.  BasicBlock architectures (resnet18/34) are not on the SM3 path
-(run.sh uses resnet50 only) and are rejected.
+No torchvision dependency.  Both block families run on the engine: BasicBlock (resnet18/34, the reference's
+default architecture) and Bottleneck (resnet50/101/152).
 """
 import os
 from typing import Any, List, Optional
@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-__all__ = ["ResNet", "Bottleneck", "resnet50", "resnet101", "resnet152"]
+__all__ = ["ResNet", "BasicBlock", "Bottleneck", "resnet18", "resnet34", "resnet50", "resnet101", "resnet152"]
 
 
 def conv3x3(in_planes: int, out_planes: int, stride: int = 1) -> nn.Conv2d:
@@ -25,6 +25,27 @@ def conv3x3(in_planes: int, out_planes: int, stride: int = 1) -> nn.Conv2d:
 
 def conv1x1(in_planes: int, out_planes: int, stride: int = 1) -> nn.Conv2d:
     return nn.Conv2d(in_planes, out_planes, kernel_size=1, stride=stride, bias=False)
+
+
+class BasicBlock(nn.Module):
+    """Parameter container for one ResNet basic block (two 3x3 convolutions, stride on the first; reference
+    resnet.py:59-106)."""
+    expansion: int = 1
+
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: Optional[nn.Module] = None,
+                 norm_layer=None) -> None:
+        super().__init__()
+        norm_layer = norm_layer or nn.BatchNorm2d
+        self.conv1 = conv3x3(inplanes, planes, stride)
+        self.bn1 = norm_layer(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = conv3x3(planes, planes)
+        self.bn2 = norm_layer(planes)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x: Tensor) -> Tensor:  # pragma: no cover - blocks are sequenced by the engine
+        raise RuntimeError("BasicBlock blocks are executed by sm3hip.engine, not called individually")
 
 
 class Bottleneck(nn.Module):
@@ -53,8 +74,9 @@ class ResNet(nn.Module):
     def __init__(self, block, layers: List[int], num_classes: int = 1000, zero_init_residual: bool = False,
                  norm_layer=None) -> None:
         super().__init__()
-        if block is not Bottleneck:
-            raise NotImplementedError("the SM3 HIP engine implements Bottleneck ResNets (resnet50/101/152)")
+        if block not in (BasicBlock, Bottleneck):
+            raise NotImplementedError("the SM3 HIP engine implements BasicBlock and Bottleneck ResNets")
+        self.block_type = "basic" if block is BasicBlock else "bottleneck"
         norm_layer = norm_layer or nn.BatchNorm2d
         self._norm_layer = norm_layer
         self.block_counts = list(layers)
@@ -80,6 +102,8 @@ class ResNet(nn.Module):
             for m in self.modules():
                 if isinstance(m, Bottleneck) and m.bn3.weight is not None:
                     nn.init.constant_(m.bn3.weight, 0)
+                elif isinstance(m, BasicBlock) and m.bn2.weight is not None:
+                    nn.init.constant_(m.bn2.weight, 0)
 
     def _make_layer(self, block, planes: int, blocks: int, stride: int = 1) -> nn.Sequential:
         downsample = None
@@ -99,7 +123,7 @@ class ResNet(nn.Module):
 
     def _forward_impl(self, x: Tensor) -> Tensor:
         from sm3hip.bridge import encoder_features
-        feat = encoder_features(self, x)  # [N, 2048] fp32: conv1 ... avgpool + flatten
+        feat = encoder_features(self, x)  # [N, 512 * expansion] fp32: conv1 ... avgpool + flatten
         return self.fc(feat)
 
     def forward(self, x: Tensor) -> Tensor:
@@ -109,25 +133,34 @@ class ResNet(nn.Module):
 def _load_weights(model: ResNet, weights: Any, hub_file: str) -> None:
     """`weights` may be None, a path to a state_dict file, or a torchvision enum name such as
     "IMAGENET1K_V1" (tools/backbone_train.py passes args.arch_weights); the latter is served from the
-    local torch-hub cache only -- this build never downloads."""
+    local torch-hub cache only -- this build never downloads.  Weights that are neither a file nor cached raise
+    NotImplementedError (a RuntimeError): fetching them is the part of torchvision's loader this build does not have."""
     if weights is None:
         return
     path = str(weights)
     if not os.path.isfile(path):
         cache = os.path.join(torch.hub.get_dir(), "checkpoints", hub_file)
         if not os.path.isfile(cache):
-            raise RuntimeError(f"weights={weights!r}: no local file and no cached {cache}; "
-                               "pass weights=None or a state_dict path (no network access)")
+            raise NotImplementedError(f"weights={weights!r}: no local file and no cached {cache}; "
+                                      "pass weights=None or a state_dict path (no network access)")
         path = cache
     state = torch.load(path, map_location="cpu")
     model.load_state_dict(state.get("state_dict", state))
 
 
-def _resnet(layers: List[int], weights: Any, hub_file: str, **kwargs: Any) -> ResNet:
+def _resnet(layers: List[int], weights: Any, hub_file: str, block=Bottleneck, **kwargs: Any) -> ResNet:
     kwargs.pop("progress", None)
-    model = ResNet(Bottleneck, layers, **kwargs)
+    model = ResNet(block, layers, **kwargs)
     _load_weights(model, weights, hub_file)
     return model
+
+
+def resnet18(*, weights: Any = None, progress: bool = True, **kwargs: Any) -> ResNet:
+    return _resnet([2, 2, 2, 2], weights, "resnet18-f37072fd.pth", block=BasicBlock, **kwargs)
+
+
+def resnet34(*, weights: Any = None, progress: bool = True, **kwargs: Any) -> ResNet:
+    return _resnet([3, 4, 6, 3], weights, "resnet34-b627a593.pth", block=BasicBlock, **kwargs)
 
 
 def resnet50(*, weights: Any = None, progress: bool = True, **kwargs: Any) -> ResNet:

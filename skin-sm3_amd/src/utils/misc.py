@@ -92,6 +92,17 @@ def amp_dtype(args):
     return torch.float16 if args.amp_dtype == "fp16" else torch.bfloat16
 
 
+MLC_ARCHS = ("resnet50", "resnet101", "resnet152")
+
+
+def require_mlc_arch(arch, tool):
+    """The multi-label tools (mlc_train / mlc_eval / inference) build their heads on 2 x 2048 pooled features, i.e. on
+    Bottleneck encoders; the BasicBlock ones (resnet18/34, 512-wide) are rejected here, before any kernel runs."""
+    if arch not in MLC_ARCHS:
+        raise SystemExit(f"{tool}: -a {arch} is not supported: the multi-label heads are built on 2048-wide Bottleneck "
+                         f"features (one of {', '.join(MLC_ARCHS)}); resnet18/34 run in backbone_train / backbone_eval")
+
+
 def describe_ignored(args, parser):
     """Names of the compatibility-only flags the caller set to something other than their default."""
     out = []

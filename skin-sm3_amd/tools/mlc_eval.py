@@ -135,6 +135,8 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    from src.utils.misc import require_mlc_arch
+    require_mlc_arch(args.arch, "mlc_eval")
     if args.data_name != "synthetic":
         raise SystemExit("only --data-name synthetic is available in this build (dataset pipeline is out of scope)")
     if args.mlc_proj != "v4" or args.num_labels != 8:

@@ -135,6 +135,8 @@ def cluster_memory(args, prototype, K, local_index, local_emb, nmb_kmeans_iters=
 
 
 def main(local_rank, args):
+    from src.utils.misc import require_mlc_arch
+    require_mlc_arch(args.arch, "mlc_train")
     world = args.world_size
     args.rank = local_rank
     # test knobs, as in bench.py (a 2-rank rehearsal on a one-GPU box: both ranks on device 0 over gloo)
