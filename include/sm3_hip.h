@@ -564,7 +564,8 @@ int sm3_mlc_attention_fwd(const float* qkv, float* out, int B, int S, int D, int
 int sm3_mlc_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int S, int D, int nhead, float p,
                           uint32_t seed, int label_major, void* stream);
 /* out = LayerNorm(a + dropout_p(b)) * gamma + beta; stats[rows][2] = (mean, rstd).  Backward: da = d(sum), db = mask/(1-p) *
- * d(sum), dgamma / dbeta accumulated (atomics). */
+ * d(sum), dgamma / dbeta accumulated (atomics).  D <= 4096 (--mlc-proj v0 runs the layer at d_model = in_dim); the row sums
+ * have a fixed order. */
 int sm3_mlc_add_ln_fwd(const float* a, const float* b, const float* gamma, const float* beta, float eps, float p,
                        uint32_t seed, float* out, float* stats, int64_t rows, int D, void* stream);
 int sm3_mlc_add_ln_bwd(const float* dout, const float* a, const float* b, const float* stats, const float* gamma, float p,
@@ -594,6 +595,23 @@ int sm3_mlc_heads_bwd(const float* dlogits, const float* x, const float* W, cons
 int sm3_mlc_kmeans_assign(const float* emb, const float* centroids, int64_t* assign, float* sums, int* counts, int N, int D,
                           int K, void* stream);
 int sm3_mlc_kmeans_update(float* centroids, const float* sums, const int* counts, int K, int D, void* stream);
+
+/* ---- grouped 1x1 GEMM: the per-label layers of the BN-MLP label projectors (reference src/models/projector.py:5-62, built by
+ * tools/mlc_train.py:352-361 and tools/mlc_eval.py:344-353 for --mlc-proj v1 / v2 / v3), exact f32 (SM3_F32 only) ------------
+ * G groups over one batch of `rows`: group g reads columns [g*K, (g+1)*K) of x [rows][G*K] and writes columns [g*N, (g+1)*N)
+ * of y [rows][G*N] -- the label-major layout in which the BatchNorm1d of one layer for all labels is ONE BatchNorm over G*N
+ * channels.  Within a group every sum has the order of a single-group sm3_conv_gather_gemm / sm3_conv_wgrad_det on compact
+ * operands, so a grouped launch equals G per-group launches bit for bit.
+ * Forward: y = per-group x_g w[g]^T, w: [G][N][K]; stat_partials (nullable): [ceil(rows / 128)][2][G*N] per-row-block sums and
+ * sums of squares of y for train-mode BatchNorm (sm3_bn_stats_reduce / sm3_bn_finalize over G*N channels).
+ * Data gradient: the same entry with the transposed banks w_t [G][K][N] (dx_g = dy_g w[g]; K and N swap roles). */
+int sm3_grouped_gemm(int dtype, const void* x, const void* w, void* y, float* stat_partials, int rows, int groups, int K, int N,
+                     void* stream);
+/* Weight gradient, a function of its inputs (no float atomics): dw[g] += dy_g^T x_g, dw: [G][N][K] fp32; x: [rows][G*K], dy:
+ * [rows][G*N].  slabs: room for slab_capacity banks of G*N*K floats; the pixel slices of each group are those of
+ * sm3_conv_wgrad_det on one group with the same capacity, and one sm3_slab_reduce adds them up. */
+int sm3_grouped_wgrad_det(int dtype, const void* x, const void* dy, float* dw, float* slabs, int slab_capacity, int rows,
+                          int groups, int K, int N, void* stream);
 
 /* ---- peer-to-peer SyncBatchNorm statistics exchange on one node (csrc/p2p.hip; opt-in, RCCL is the default) ----------------
  * Replaces the all-reduce torch.nn.SyncBatchNorm performs per BatchNorm and direction (tools/backbone_train.py:510) for the

@@ -69,6 +69,10 @@ struct ConvParams {
     // such a launch can reach (general gather, 4-stage deep, 8-wave; every epilogue), so that the bits of a layer's output do
     // not depend on which of them the grid size selects (B vs 2B, both views in one batch vs per-view passes); 0 = tap outer
     int kord;
+    // grouped launches (kVarGrp, sm3_grouped_gemm): gridDim.y = groups; group g reads x + g * g_x_bytes, w + g * g_w_bytes and
+    // writes y + g * g_y_bytes, its BatchNorm partial sums at column g * Co of rows part_ld floats wide
+    long g_x_bytes, g_w_bytes, g_y_bytes;
+    int groups, part_ld;
     int dbg;  // SM3_CONV_DBG: experiment switches of the split K loop (bit 0: consumer waves at s_setprio 1)
 };
 

@@ -91,7 +91,10 @@ struct StampRec {
 //              (one read of that tensor and one launch per Bottleneck) disappears (forward half).
 // (bits 1 and 8 were the loader / consumer split and the 16 x 16 x 32 MFMA shape of round 4: measured slower two rounds
 // running and removed in round 6 -- profiles/r04a_split_ab_*.txt, r04a_mfma_16x16x32_ab_single_lane.txt, scratch/r6_pruned_variants.patch)
-constexpr int kVarPw = 2, kVarNoX = 4, kVarHalo = 16, kVarHaloBn = 32;
+//   kVarGrp    grouped 1x1 launches (sm3_grouped_gemm, exact-f32 general epilogue): workgroup row blockIdx.y is group g, whose
+//              operands and outputs sit at the byte offsets g * g_{x,w,y}_bytes; everything inside a group -- tiles, K order,
+//              epilogue -- is the single-group launch's, so a grouped launch equals G separate launches bit for bit.
+constexpr int kVarPw = 2, kVarNoX = 4, kVarHalo = 16, kVarHaloBn = 32, kVarGrp = 64;
 template <typename T, int BM, int BN, int WM, int WN, int STAGES, int EPI, bool SEG = false, int VAR = 0>
 // registers: the 1-stage kernels (34 KB of LDS) run 4 workgroups per CU = 4 waves per SIMD, so their epilogues must fit 128
 // registers; the 2- and 4-stage kernels are limited to 2 / 1 workgroups per CU by their LDS and may use 256
@@ -99,6 +102,8 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
     static_assert(STAGES == 1 || STAGES == 4, "one-stage loop, or the 4-stage ring of the small-grid launches");
     constexpr bool PW = (VAR & kVarPw) != 0, NOX = (VAR & kVarNoX) != 0;
     constexpr bool HALO = (VAR & kVarHalo) != 0, HALOBN = (VAR & kVarHaloBn) != 0;
+    constexpr bool GRP = (VAR & kVarGrp) != 0;
+    static_assert(!GRP || (EPI == 0 && !SEG && VAR == kVarGrp), "kVarGrp: the general epilogue, one K segment");
     static_assert(!HALOBN || (HALO && EPI == 1), "kVarHaloBn: the plain forward epilogue of the halo kernel");
     static_assert(!HALO || (EPI >= 1 && STAGES == 1 && !SEG && !(VAR & kVarPw) && sizeof(T) == 2 && WM * WN == 4),
                   "kVarHalo: 16-bit lean one-stage kernels, 4 waves");
@@ -138,8 +143,15 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
     const int bn = bid % p.tilesN, bm = bid / p.tilesN;
     const int m0 = bm * BM, n0 = bn * BN;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    // group of a grouped launch (kVarGrp); otherwise these are p.x / p.w / p.y / p.partials themselves
+    const long grp = GRP ? (long)blockIdx.y : 0;
+    const char* const gx = GRP ? p.x + grp * p.g_x_bytes : p.x;
+    const char* const gw = GRP ? p.w + grp * p.g_w_bytes : p.w;
+    char* const gy = GRP ? p.y + grp * p.g_y_bytes : p.y;
+    float* const gpart = (GRP && p.partials) ? p.partials + grp * p.Co : p.partials;
+    const long part_ld = GRP ? (long)p.part_ld : (long)p.Co;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)gx, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)gw, 0, p.w_bytes, 0x00020000);
     // second segment's operands (SEG only; otherwise aliases that the optimiser drops)
     const __amdgpu_buffer_rsrc_t rx1 =
         SEG ? __builtin_amdgcn_make_buffer_rsrc((void*)p.x1, 0, p.x1_bytes, 0x00020000) : rx;
@@ -961,8 +973,8 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
                 s1 += sStat[(w * BN + tid) * 2 + 0];
                 s2 += sStat[(w * BN + tid) * 2 + 1];
             }
-            p.partials[((long)bm * 2 + 0) * p.Co + n0 + tid] = s1;
-            p.partials[((long)bm * 2 + 1) * p.Co + n0 + tid] = s2;
+            gpart[((long)bm * 2 + 0) * part_ld + n0 + tid] = s1;
+            gpart[((long)bm * 2 + 1) * part_ld + n0 + tid] = s2;
         }
 #pragma unroll
         for (int k = 0; k < NROW; ++k) {
@@ -1022,9 +1034,9 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
                     f_s1[e] += dzr[e];
                     f_s2[e] += dzr[e] * (xv[e] - f_mu[e]) * f_is[e];  // f_mu = f_is = 0 without x: the slot stays 0
                 }
-                stg16<true>(p.y + boff, packed);
+                stg16<true>(gy + boff, packed);
             } else {
-                stg16<true>(p.y + boff, pack16<T>(v));
+                stg16<true>(gy + boff, pack16<T>(v));
             }
         }
     }
@@ -1127,7 +1139,7 @@ int launch_conv_st(const ConvParams& p0, hipStream_t st) {
     }
     const long nblocks = (long)p.tilesM * p.tilesN;
     if (nblocks <= 0 || nblocks > 0x7fffffffL) return SM3_EINVAL;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(WM * WN * 64), LDS, st, p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks, (VAR & kVarGrp) ? (unsigned)p.groups : 1u), dim3(WM * WN * 64), LDS, st, p);
     SM3_CHECK_LAUNCH();
     return 0;
 }
@@ -1464,6 +1476,61 @@ extern "C" int sm3_conv3x3_bnin(const sm3_conv_desc* d, const void* x_raw, const
     if (!in_scale || !in_shift || !act_out || !mask_out || views < 1) return SM3_EINVAL;
     const BnIn b{in_scale, in_shift, views, act_out, mask_out, false};
     return conv_gather_gemm_impl(d, x_raw, w, y, nullptr, stat_partials, nullptr, stream, nullptr, nullptr, &b);
+}
+
+// Grouped 1x1 GEMM (exact f32): y[:, g*N:(g+1)*N] = x[:, g*K:(g+1)*K] @ w[g]^T for g < groups, one launch.  Each group is the
+// single-group gather-GEMM over a strided view: x as an image [rows][1][groups][K] read at column 0 with a column stride of
+// `groups` (base shifted to group g's K block), y as [rows][1][groups][N] written at column 0 (base shifted likewise) -- the same
+// tiles, K order and epilogue as sm3_conv_gather_gemm on the compact per-group operands.  Tile shape and K-loop depth are
+// picked from the whole grid (they change speed, never bits).
+extern "C" int sm3_grouped_gemm(int dtype, const void* x, const void* w, void* y, float* stat_partials, int rows, int groups,
+                                int K, int N, void* stream) {
+    if (dtype != SM3_F32) return SM3_EDTYPE;
+    if (!x || !w || !y || rows <= 0 || groups <= 0 || groups > 65535 || K <= 0 || N <= 0) return SM3_EINVAL;
+    if ((long)groups * K > 0x7fffffffL || (long)groups * N > 0x7fffffffL) return SM3_EINVAL;
+    sm3_conv_desc d{};
+    d.dtype = SM3_F32;
+    d.N = rows; d.Hi = 1; d.Wi = groups; d.Ci = K;
+    d.Ho = 1; d.Wo = 1; d.Co = N;
+    d.sy = 1; d.sx = groups;
+    d.ntaps = 1;
+    d.w_row_stride = K;
+    d.Hout = 1; d.Wout = groups;
+    d.osy = 1; d.osx = 1; d.ooy = 0; d.oox = 0;
+    ConvParams p;
+    const int rc = fill_params(&d, p, 4);
+    if (rc) return rc;
+    if ((long)rows * groups * N * 4 >= 0xC0000000L) return SM3_EINVAL;
+    p.x = (const char*)x; p.w = (const char*)w; p.y = (char*)y; p.addend = nullptr;
+    p.partials = stat_partials;
+    p.fz_mask = nullptr; p.fz_x = nullptr; p.fz_mean = nullptr; p.fz_invstd = nullptr; p.fz_partials = nullptr;
+    p.fz_row_off = 0; p.fz_view_tiles = 0; p.fz_row_off1 = 0;
+    p.add_sp_h = p.add_sp_w = 0;
+    p.ep_scale = p.ep_shift = p.ep_gamma = p.ep_beta = p.ep_rm = p.ep_rv = nullptr;
+    p.ep_eps = 0.f; p.ep_relu = 0; p.ep_mask = nullptr;
+    p.x1 = p.w1 = nullptr; p.col_bias = nullptr;
+    p.x1_bytes = p.w1_bytes = p.w_view_bytes = p.w1_view_bytes = 0;
+    p.Ci1 = p.kchunks1 = p.w1_row_stride = p.nsteps_seg = 0;
+    for (int t = 0; t < SM3_MAX_TAPS; ++t) p.tap_src[t] = 0;
+    p.in_scale = p.in_shift = nullptr; p.in_act = nullptr; p.in_mask = nullptr;
+    p.kord = 0;
+    p.groups = groups;
+    p.g_x_bytes = (long)K * 4;
+    p.g_w_bytes = (long)N * K * 4;
+    p.g_y_bytes = (long)N * 4;
+    p.part_ld = groups * N;
+    hipStream_t st = (hipStream_t)stream;
+    const long tm = (rows + kBM - 1) / kBM;
+    const long tiles128 = tm * ((N + 127) / 128) * groups;
+    const bool narrow = N <= 64 || (tiles128 <= 96 && p.kchunks >= 6);
+    const long nblocks = tm * ((N + (narrow ? 63 : 127)) / (narrow ? 64 : 128)) * groups;
+    const char* dv = getenv("SM3_CONV_DEEP");
+    const bool deep = !(dv && atoi(dv) == 0) && nblocks <= 256 && p.kchunks >= 6;
+    if (narrow)
+        return deep ? launch_conv_st<float, kBM, 64, 2, 2, 4, 0, false, kVarGrp>(p, st)
+                    : launch_conv_st<float, kBM, 64, 2, 2, 1, 0, false, kVarGrp>(p, st);
+    return deep ? launch_conv_st<float, kBM, 128, 2, 2, 4, 0, false, kVarGrp>(p, st)
+                : launch_conv_st<float, kBM, 128, 2, 2, 1, 0, false, kVarGrp>(p, st);
 }
 
 #ifdef SM3_STAMP

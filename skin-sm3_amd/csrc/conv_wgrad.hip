@@ -52,6 +52,10 @@ struct WgradParams {
     // slice adds its tiles to dw_direct itself (rmw: plain read-modify-write, one writer per element) -- no slab, no reduce
     float* dw_direct;
     int pair_rule, rmw;
+    // grouped launches (GRP, sm3_grouped_wgrad_det): gridDim.y = groups; group g reads x + g * g_x_bytes (rows x_ld elements
+    // apart) and dy + g * g_dy_bytes (rows dy_ld apart) and writes its [Co][Ci] block at dw + g * g_dw (slab or direct)
+    long g_x_bytes, g_dy_bytes, g_dw;
+    int groups, x_ld, dy_ld;
 };
 
 #ifdef SM3_STAMP
@@ -84,8 +88,9 @@ __device__ __forceinline__ uint32_t swz_bytes(int row) {
 // KG = 2: two groups of 4 waves share a workgroup, each walks half of the workgroup's pixel slice with its own LDS ring
 // and accumulators; group 1 hands its tile to group 0 through LDS and ONE set of f32 atomics leaves the workgroup --
 // the same waves per CU as two 4-wave workgroups at half the atomic traffic (the 1x1 layers paid 20 % for atomics).
-template <typename T, int BMW, int BNW, int KP, bool DENSE, int NST, int KG = 1>  // KP = pixels per K-step, NST = LDS stages
+template <typename T, int BMW, int BNW, int KP, bool DENSE, int NST, int KG = 1, bool GRP = false>  // KP = pixels per K-step, NST = LDS stages
 __global__ __launch_bounds__(256 * KG, NST == 1 ? 4 : 1) void conv_wgrad_kernel(const WgradParams p) {
+    static_assert(!GRP || DENSE, "grouped launches: the dense (1x1) loader");
     constexpr int SZ = sizeof(T);
     constexpr bool kBf16 = (SZ == 2);
     constexpr int RA = BMW * SZ, RB = BNW * SZ;                 // bytes per tile row (one pixel)
@@ -129,7 +134,11 @@ __global__ __launch_bounds__(256 * KG, NST == 1 ? 4 : 1) void conv_wgrad_kernel(
     const bool second = tco * BMW >= p.Co;
     const int co0 = second ? tco * BMW - p.Co : tco * BMW;
     const int dyC = second ? p.Co1 : p.Co;  // channels (row pitch) of the tensor this tile reads
-    const char* const dy_base = second ? p.dy1 : p.dy;
+    const long gid = GRP ? (long)blockIdx.y : 0;  // group of a grouped launch
+    const char* const dy_base = (second ? p.dy1 : p.dy) + (GRP ? gid * p.g_dy_bytes : 0);
+    const char* const x_base = GRP ? p.x + gid * p.g_x_bytes : p.x;
+    const int dyP = GRP ? p.dy_ld : dyC;   // row pitch (elements) of dY ...
+    const int xP = GRP ? p.x_ld : p.Ci;    // ... and of X
     const int view = slice / p.splits_view;
     const int kbeg0 = view * p.Mv + (slice - view * p.splits_view) * p.k_per_split;
     const int kend = min((view + 1) * p.Mv, kbeg0 + p.k_per_split);
@@ -141,9 +150,9 @@ __global__ __launch_bounds__(256 * KG, NST == 1 ? 4 : 1) void conv_wgrad_kernel(
 
     // descriptors: dY rows end at kend (rows of the next slice must read as zero); X is the whole tensor
     const __amdgpu_buffer_rsrc_t rdy =
-        __builtin_amdgcn_make_buffer_rsrc((void*)dy_base, 0, (uint32_t)kend * (uint32_t)(dyC * SZ), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)dy_base, 0, (uint32_t)kend * (uint32_t)(dyP * SZ), 0x00020000);
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.x, 0, DENSE ? (uint32_t)kend * (uint32_t)(p.Ci * SZ) : p.x_bytes, 0x00020000);
+        (void*)x_base, 0, DENSE ? (uint32_t)kend * (uint32_t)(xP * SZ) : p.x_bytes, 0x00020000);
 
     // lane -> (row inside the DMA instruction, 16-byte chunk inside the row)
     const int a_rin = (lane * 16) / RA, a_pos = ((lane * 16) % RA) / 16;
@@ -156,7 +165,7 @@ __global__ __launch_bounds__(256 * KG, NST == 1 ? 4 : 1) void conv_wgrad_kernel(
         const int r = (wave + 4 * i) * RPI_A + a_rin;  // pixel row inside the K-step
         const uint32_t lchunk = ((uint32_t)a_pos * 16u) ^ swz_bytes<RA, kBf16>(r);
         const bool col_ok = co0 + (int)(lchunk / SZ) < dyC;
-        a_off[i] = col_ok ? (uint32_t)(kbeg + r) * (uint32_t)(dyC * SZ) + (uint32_t)(co0 * SZ) + lchunk : kOOB;
+        a_off[i] = col_ok ? (uint32_t)(kbeg + r) * (uint32_t)(dyP * SZ) + (uint32_t)(co0 * SZ) + lchunk : kOOB;
     }
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
@@ -165,7 +174,7 @@ __global__ __launch_bounds__(256 * KG, NST == 1 ? 4 : 1) void conv_wgrad_kernel(
         const bool col_ok = ci0 + (int)(lchunk / SZ) < p.Ci;
         b_row[i] = col_ok ? r : -(1 << 28);
         b_cho[i] = (uint32_t)(ci0 * SZ) + lchunk;
-        b_off[i] = col_ok ? (uint32_t)(kbeg + r) * (uint32_t)(p.Ci * SZ) + b_cho[i] : kOOB;  // DENSE form
+        b_off[i] = col_ok ? (uint32_t)(kbeg + r) * (uint32_t)(xP * SZ) + b_cho[i] : kOOB;  // DENSE form
     }
     const uint32_t smem_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
     int g_m[BI], g_n[BI], g_oy[BI], g_ox[BI];  // non-DENSE: output pixel of this lane's X rows in the next step to stage
@@ -182,11 +191,11 @@ __global__ __launch_bounds__(256 * KG, NST == 1 ? 4 : 1) void conv_wgrad_kernel(
     auto dma_stage = [&](int stage, int step) {
         const uint32_t sA = smem_lds + (uint32_t)((grp * NST + stage) * STAGE) + (uint32_t)wave * 1024u;
         const uint32_t sB = sA + A_BYTES;
-        const uint32_t soff_a = (uint32_t)(step * KP) * (uint32_t)(dyC * SZ);
+        const uint32_t soff_a = (uint32_t)(step * KP) * (uint32_t)(dyP * SZ);
 #pragma unroll
         for (int i = 0; i < AI; ++i) dma16(rdy, sA + i * 4096, a_off[i], soff_a);
         if constexpr (DENSE) {
-            const uint32_t soff_b = (uint32_t)(step * KP) * (uint32_t)(p.Ci * SZ);
+            const uint32_t soff_b = (uint32_t)(step * KP) * (uint32_t)(xP * SZ);
 #pragma unroll
             for (int i = 0; i < BI; ++i) dma16(rx, sB + i * 4096, b_off[i], soff_b);
         } else {
@@ -377,9 +386,9 @@ __global__ __launch_bounds__(256 * KG, NST == 1 ? 4 : 1) void conv_wgrad_kernel(
                 for (int r = 0; r < 16; ++r) acc[i][j][r] += xch[((wave * TM * TN + i * TN + j) * 16 + r) * 64 + lane];
     }
     const int frow = lane & 31, fh = lane >> 5;
-    float* const dw_out = p.slab_stride ? p.dw + (long)slice * p.slab_stride
-                          : second    ? p.dw1 + (long)view * p.dw1_view_stride
-                                      : p.dw + (long)view * p.dw_view_stride;
+    float* const dw_out = (p.slab_stride ? p.dw + (long)slice * p.slab_stride
+                           : second    ? p.dw1 + (long)view * p.dw1_view_stride
+                                       : p.dw + (long)view * p.dw_view_stride) + (GRP ? gid * p.g_dw : 0);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -603,7 +612,7 @@ static int cus_per_xcd() {
     return r;
 }
 
-template <typename T, int BMW, int BNW, int KP, bool DENSE, int NST, int KG = 1>
+template <typename T, int BMW, int BNW, int KP, bool DENSE, int NST, int KG = 1, bool GRP = false>
 int launch_wgrad_kp(WgradParams p, hipStream_t st) {
     constexpr int SZ = sizeof(T);
     constexpr int LDS = KG * NST * KP * (BMW * SZ + BNW * SZ);
@@ -614,7 +623,7 @@ int launch_wgrad_kp(WgradParams p, hipStream_t st) {
     p.adv_oy = (KP % p.HoWo) / p.Wo;
     p.adv_ox = (KP % p.HoWo) % p.Wo;
     const long gx = (long)p.tilesCo * p.ntaps * p.tilesCi;
-    auto kern = conv_wgrad_kernel<T, BMW, BNW, KP, DENSE, NST, KG>;
+    auto kern = conv_wgrad_kernel<T, BMW, BNW, KP, DENSE, NST, KG, GRP>;
     // resident workgroups per CU, and the dynamic-LDS limit of the function: per (instantiation, device), set once each
     static std::atomic<int> per_cu_dev[32];
     const int dev = current_device();
@@ -666,7 +675,7 @@ int launch_wgrad_kp(WgradParams p, hipStream_t st) {
     }
     const long nblocks = gx * (splits >= 8 ? (splits + 7) / 8 * 8 : splits);
     if (gx > 0x7fffffffL || nblocks > 0x7fffffffL) return SM3_EINVAL;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256 * KG), LDS, st, p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks, GRP ? (unsigned)p.groups : 1u), dim3(256 * KG), LDS, st, p);
     SM3_CHECK_LAUNCH();
     return 0;
 }
@@ -943,4 +952,53 @@ extern "C" int sm3_conv_wgrad_cat(const sm3_conv_desc* d, const void* x, const v
                                   void* stream) {
     if (Co1 > 0 && d && d->Co % 128) return SM3_EALIGN;  // tiles of 64 or 128 channels never straddle the two tensors
     return wgrad_impl(d, x, dy, dw, dy1, Co1, dw1, views, (long)dw_view_stride, (long)dw1_view_stride, stream);
+}
+
+// Grouped weight gradient of sm3_grouped_gemm, fixed order: dw[g] += dy[:, g*N:(g+1)*N]^T x[:, g*K:(g+1)*K] for g < groups in
+// ONE launch.  Every group is cut into the pixel slices a single-group sm3_conv_wgrad_det of [rows, K] x [rows, N] takes (the
+// partition depends on the per-group geometry and the device only, slab_capacity being the same), slab j holding all groups'
+// blocks ([groups][N][K]); one sm3_slab_reduce over the whole bank then sums every element in the order of the single-group
+// reduce.  So a grouped launch equals G single-group launches bit for bit.
+extern "C" int sm3_grouped_wgrad_det(int dtype, const void* x, const void* dy, float* dw, float* slabs, int slab_capacity,
+                                     int rows, int groups, int K, int N, void* stream) {
+    if (dtype != SM3_F32) return SM3_EDTYPE;
+    if (!x || !dy || !dw || !slabs || slab_capacity < 1 || rows <= 0 || groups <= 0 || groups > 65535 || K <= 0 || N <= 0)
+        return SM3_EINVAL;
+    if ((K * 4) % 16 != 0 || (N * 4) % 16 != 0) return SM3_EALIGN;
+    if (((uintptr_t)slabs | (uintptr_t)dw) & 15) return SM3_EALIGN;
+    if ((long)rows * groups * K * 4 >= 0xC0000000L || (long)rows * groups * N * 4 >= 0xC0000000L) return SM3_EINVAL;
+    WgradParams p;
+    p.x = (const char*)x; p.dy = (const char*)dy; p.dw = slabs;
+    p.dy1 = nullptr; p.dw1 = nullptr; p.Co1 = 0;
+    p.views = 1; p.Mv = rows;
+    p.dw_view_stride = 0; p.dw1_view_stride = 0;
+    p.slab_cap = slab_capacity;
+    p.slab_stride = (long)groups * N * K;
+    p.dw_direct = dw;
+    p.pair_rule = 0;
+    p.rmw = 0;
+    p.M = rows; p.Hi = 1; p.Wi = 1; p.Ci = K; p.Co = N;
+    p.sy = 1; p.sx = 1; p.ntaps = 1;
+    for (int t = 0; t < SM3_MAX_TAPS; ++t) { p.dyt[t] = 0; p.dxt[t] = 0; p.wtap[t] = 0; }
+    p.w_row_stride = K;
+    p.HoWo = 1; p.Wo = 1; p.Ho = 1;
+    p.div_HoWo = make_fastdiv(1u);
+    p.div_Wo = make_fastdiv(1u);
+    p.x_bytes = (uint32_t)((long)rows * groups * K * 4);
+    p.groups = groups;
+    p.g_x_bytes = (long)K * 4;
+    p.g_dy_bytes = (long)N * 4;
+    p.g_dw = (long)N * K;
+    p.x_ld = groups * K;
+    p.dy_ld = groups * N;
+    hipStream_t st = (hipStream_t)stream;
+    // the tile and K-loop choice of wgrad_impl -> launch_wgrad for a dense f32 product of these per-group sizes
+    const bool nco = N <= 64, nci = K <= 64;
+    int rc;
+    if (nco && nci) rc = launch_wgrad_kp<float, 64, 64, 16, true, 4, 2, true>(p, st);
+    else if (nco) rc = launch_wgrad_kp<float, 64, 128, 16, true, 4, 2, true>(p, st);
+    else if (nci) rc = launch_wgrad_kp<float, 128, 64, 16, true, 4, 2, true>(p, st);
+    else rc = launch_wgrad_kp<float, 128, 128, 16, true, 4, 2, true>(p, st);
+    if (rc != 0 || g_last_slabs == 0) return rc;  // 0 slabs: one slice per group added its tiles to dw itself
+    return sm3_slab_reduce(slabs, g_last_slabs, (int64_t)groups * N * K, dw, 1, stream);
 }

@@ -141,6 +141,10 @@ __global__ __launch_bounds__(256) void mlc_attention_bwd_kernel(const float* __r
 }
 
 // ---- out = LayerNorm(a + dropout(b)) ; stats[row] = (mean, rstd) -------------------------------------------------
+// One wave per row, NV values per lane in registers: NV = 16 for D <= 1024, NV = 64 for the 4096-wide rows of --mlc-proj v0
+// (d_model = in_dim, mlc_train.py:352-353).  The row sums are wave_sum over the lanes' sums in d order: the same fixed order
+// for every D, and for D <= 1024 the same instructions as before the wide form existed.
+template <int NV>
 __global__ __launch_bounds__(256) void mlc_add_ln_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                                              float eps, float p, uint32_t seed, float* __restrict__ out,
@@ -149,7 +153,7 @@ __global__ __launch_bounds__(256) void mlc_add_ln_fwd_kernel(const float* __rest
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
-    float v[16], s = 0.f;
+    float v[NV], s = 0.f;
     int n = 0;
     for (int d = lane; d < D; d += 64, ++n) {
         const int64_t o = row * D + d;
@@ -170,6 +174,7 @@ __global__ __launch_bounds__(256) void mlc_add_ln_fwd_kernel(const float* __rest
 }
 
 // ds = gradient w.r.t. (a + dropout(b)); da = ds; db = mask/(1-p) * ds; dgamma/dbeta += (atomics)
+template <int NV>
 __global__ __launch_bounds__(256) void mlc_add_ln_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ a,
                                                              const float* __restrict__ b, const float* __restrict__ stats,
                                                              const float* __restrict__ gamma, float p, uint32_t seed,
@@ -181,7 +186,7 @@ __global__ __launch_bounds__(256) void mlc_add_ln_bwd_kernel(const float* __rest
     if (row >= rows) return;
     const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
     const float mean = stats[2 * row], rstd = stats[2 * row + 1];
-    float xh[16], g[16], s1 = 0.f, s2 = 0.f;
+    float xh[NV], g[NV], s1 = 0.f, s2 = 0.f;
     int n = 0;
     for (int d = lane; d < D; d += 64, ++n) {
         const int64_t o = row * D + d;
@@ -440,8 +445,8 @@ extern "C" int sm3_mlc_attention_bwd(const float* qkv, const float* dout, float*
 }
 extern "C" int sm3_mlc_add_ln_fwd(const float* a, const float* b, const float* gamma, const float* beta, float eps, float p,
                                   uint32_t seed, float* out, float* stats, int64_t rows, int D, void* stream) {
-    if (!a || !b || !gamma || !beta || !out || !stats || rows <= 0 || D <= 0 || D > 1024 || p < 0.f || p >= 1.f) return SM3_EINVAL;
-    hipLaunchKernelGGL(mlc_add_ln_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, b, gamma,
+    if (!a || !b || !gamma || !beta || !out || !stats || rows <= 0 || D <= 0 || D > 4096 || p < 0.f || p >= 1.f) return SM3_EINVAL;
+    hipLaunchKernelGGL(D <= 1024 ? mlc_add_ln_fwd_kernel<16> : mlc_add_ln_fwd_kernel<64>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, b, gamma,
                        beta, eps, p, seed, out, stats, rows, D);
     SM3_CHECK_LAUNCH();
     return 0;
@@ -449,10 +454,10 @@ extern "C" int sm3_mlc_add_ln_fwd(const float* a, const float* b, const float* g
 extern "C" int sm3_mlc_add_ln_bwd(const float* dout, const float* a, const float* b, const float* stats, const float* gamma,
                                   float p, uint32_t seed, float* da, float* db, float* dgamma, float* dbeta, int64_t rows,
                                   int D, void* stream) {
-    if (!dout || !a || !b || !stats || !gamma || !da || !db || !dgamma || !dbeta || rows <= 0 || D <= 0 || D > 1024 || p < 0.f ||
+    if (!dout || !a || !b || !stats || !gamma || !da || !db || !dgamma || !dbeta || rows <= 0 || D <= 0 || D > 4096 || p < 0.f ||
         p >= 1.f)
         return SM3_EINVAL;
-    hipLaunchKernelGGL(mlc_add_ln_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dout, a, b,
+    hipLaunchKernelGGL(D <= 1024 ? mlc_add_ln_bwd_kernel<16> : mlc_add_ln_bwd_kernel<64>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dout, a, b,
                        stats, gamma, p, seed, da, db, dgamma, dbeta, rows, D);
     SM3_CHECK_LAUNCH();
     return 0;

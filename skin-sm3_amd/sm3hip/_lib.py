@@ -159,6 +159,8 @@ SIGNATURES = {
     "sm3_mlc_heads_bwd": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "sm3_mlc_kmeans_assign": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "sm3_mlc_kmeans_update": [_P, _P, _P, _I, _I, _P],
+    "sm3_grouped_gemm": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "sm3_grouped_wgrad_det": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
 _lib = None

@@ -1,9 +1,23 @@
 """Training of the multi-label heads on the HIP kernels (reference tools/mlc_train.py:58-90 `Model`,
 :241-283 loop, :116-189 spherical k-means; tools/mlc_eval.py reuses the same model with biased prototypes).
 
-    feats [B, 4096] -> S per-label Linear(4096, D) (src/models/projector.py:65-78) -> stack [S, B, D]
+    feats [B, 4096] -> S label projectors (--mlc-proj, src/models/projector.py) -> stack [S, B, D]
     -> nn.TransformerEncoderLayer(D, nhead, ff, dropout) in TRAIN mode over the S label tokens of each sample
     -> optional L2 norm -> per-label prototype Linear -> logits
+
+Label projectors (mlc_train.py:352-361):
+    v4      one biased Linear(4096, D) per label (S = 8): one GEMM + bias per label.
+    v1-v3   per-label BN-MLPs (bias-free Linear -> BatchNorm1d -> ReLU, ..., BatchNorm1d(affine=False)).  A layer's
+            activations for all labels are kept as ONE [B, S*C] tensor, label-major in the columns, so its S BatchNorm1d are
+            one plain BatchNorm over S*C channels (bn_stats_reduce / bn_finalize / bn_act; backward bn_bwd_reduce /
+            bn_bwd_apply) with the labels' gamma / beta / running buffers packed into banks (running statistics and
+            num_batches_tracked written back to every label's module).  The first layer of all labels is ONE GEMM against the
+            stacked [S*C, 4096] weights (every label reads the same features; its data gradient one GEMM with K = S*C); the
+            per-label layers behind it are grouped GEMMs (sm3_grouped_gemm / sm3_grouped_wgrad_det: S groups, one launch).
+            Each BatchNorm1d's own .training decides batch or running statistics (mlc_eval --finetune fc keeps the projectors
+            in eval mode while the prototypes train; mlc_train's init_memory runs everything in eval mode).  Statistics are
+            per rank, as in the reference (no SyncBatchNorm).
+    v0      nn.Identity: ONE label token, the features themselves (S = 1, D = 4096).
 
 Every Linear (forward, data gradient, weight gradient) is the exact-f32 MFMA gather-GEMM / weight-gradient kernel; the
 attention over the 8 tokens, the two residual LayerNorms with their dropouts, bias + ReLU + dropout, the prototype heads
@@ -23,6 +37,27 @@ def _st():
     return ops._stream()
 
 
+def _projector_kind(projectors):
+    """'v0' (nn.Identity), 'v4' (one biased Linear per label) or 'mlp' (v1 / v2 / v3) plus, for 'mlp', the layer list
+    [(linear index, bn index, relu)] of one label's nn.Sequential."""
+    if isinstance(projectors, torch.nn.Identity):
+        return "v0", None
+    seq = projectors.projectors[0]
+    mods = list(seq)
+    if len(mods) == 1 and isinstance(mods[0], torch.nn.Linear) and mods[0].bias is not None:
+        return "v4", None
+    layers, i = [], 0
+    while i < len(mods):
+        lin = mods[i]
+        bn = mods[i + 1] if i + 1 < len(mods) else None
+        if not isinstance(lin, torch.nn.Linear) or lin.bias is not None or not isinstance(bn, torch.nn.BatchNorm1d):
+            raise NotImplementedError("label projectors: MultiLabelProjector{,2,3,4} of src/models/projector.py or nn.Identity")
+        relu = i + 2 < len(mods) and isinstance(mods[i + 2], torch.nn.ReLU)
+        layers.append((i, i + 1, relu))
+        i += 3 if relu else 2
+    return "mlp", layers
+
+
 class MLCHeads:
     """Kernel sequencing for one `Model` (its projectors / mlc_sa / prototypes own the parameters)."""
 
@@ -31,8 +66,18 @@ class MLCHeads:
         sa = model.mlc_sa
         if sa.norm_first or getattr(sa, "activation_relu_or_gelu", 1) != 1:
             raise NotImplementedError("only the post-norm ReLU TransformerEncoderLayer of mlc_train.py is built")
-        self.S = len(model.projectors.projectors)
+        self.kind, self.layers = _projector_kind(model.projectors)
+        self.S = 1 if self.kind == "v0" else len(model.projectors.projectors)
         self.D = sa.self_attn.embed_dim
+        if self.kind == "mlp":
+            for s, seq in enumerate(model.projectors.projectors):
+                for li, bi, _ in self.layers:
+                    bn = seq[bi]
+                    if not bn.track_running_stats or bn.momentum is None:
+                        raise NotImplementedError("label projector BatchNorm1d: running statistics with a momentum")
+            if model.projectors.projectors[0][self.layers[-1][0]].out_features != self.D:
+                raise ValueError("label projector width must equal mlc_sa's d_model")
+        self._bank_key, self._banks = None, None
         self.nhead = sa.self_attn.num_heads
         self.p = float(sa.dropout.p)
         if float(sa.self_attn.dropout) != self.p or float(sa.dropout1.p) != self.p or float(sa.dropout2.p) != self.p:
@@ -40,11 +85,23 @@ class MLCHeads:
         self.sizes = [l.weight.shape[0] for l in model.prototypes]
         self.has_pbias = model.prototypes[0].bias is not None
 
+    def proj_params(self):
+        m = self.model
+        if self.kind == "v0":
+            return []
+        if self.kind == "v4":
+            return [q for l in m.projectors.projectors for q in (l[0].weight, l[0].bias)]
+        ps = []
+        for seq in m.projectors.projectors:
+            for li, bi, _ in self.layers:
+                ps.append(seq[li].weight)
+                if seq[bi].affine:
+                    ps += [seq[bi].weight, seq[bi].bias]
+        return ps
+
     def params(self):
         m, sa = self.model, self.model.mlc_sa
-        ps = []
-        for l in m.projectors.projectors:
-            ps += [l[0].weight, l[0].bias]
+        ps = list(self.proj_params())
         ps += [sa.self_attn.in_proj_weight, sa.self_attn.in_proj_bias, sa.self_attn.out_proj.weight, sa.self_attn.out_proj.bias,
                sa.linear1.weight, sa.linear1.bias, sa.linear2.weight, sa.linear2.bias, sa.norm1.weight, sa.norm1.bias,
                sa.norm2.weight, sa.norm2.bias]
@@ -79,6 +136,131 @@ class MLCHeads:
     def _colsum(dy, db):
         check(_lib.load().sm3_mlc_colsum(_P(dy), _P(db), dy.shape[0], dy.shape[1], _st()), "sm3_mlc_colsum")
 
+    # ---- BN-MLP label projectors (v1 / v2 / v3) --------------------------------------------------------------------
+    def _mlp_banks(self):
+        """Per layer: the labels' Linear weights stacked [S*C, Cin] (layer 0: the one-GEMM form) or as S banks [S, C, Cin]
+        (grouped), their transposes for the data gradient, and gamma / beta banks [S*C]; rebuilt when a parameter changes."""
+        seqs = self.model.projectors.projectors
+        ps = self.proj_params()
+        key = tuple(q._version for q in ps) + tuple(q.data_ptr() for q in ps)
+        if key == self._bank_key:
+            return self._banks
+        banks = []
+        for j, (li, bi, relu) in enumerate(self.layers):
+            w = torch.stack([seq[li].weight.detach() for seq in seqs], 0).contiguous()          # [S, C, Cin]
+            S, C, Cin = w.shape
+            wt = w.transpose(1, 2).contiguous()                                                   # [S, Cin, C]
+            if j == 0:
+                wt = w.reshape(S * C, Cin).t().contiguous()                                       # [Cin, S*C]
+            aff = seqs[0][bi].affine
+            g = torch.cat([seq[bi].weight.detach() for seq in seqs]).contiguous() if aff else None
+            b = torch.cat([seq[bi].bias.detach() for seq in seqs]).contiguous() if aff else None
+            banks.append(dict(w=w, wt=wt, C=C, Cin=Cin, gamma=g, beta=b, relu=relu))
+        self._bank_key, self._banks = key, banks
+        return banks
+
+    def _mlp_forward(self, feats):
+        """feats [B, in] -> [B, S*D] (label-major columns) and what the backward pass needs."""
+        seqs, S, B, dev = self.model.projectors.projectors, self.S, feats.shape[0], feats.device
+        banks, h, recs = self._mlp_banks(), feats, []
+        for j, (li, bi, relu) in enumerate(self.layers):
+            bk = banks[j]
+            SC = S * bk["C"]
+            bns = [seq[bi] for seq in seqs]
+            train = bns[0].training
+            if any(bn.training != train for bn in bns) or any(bn.eps != bns[0].eps for bn in bns):
+                raise NotImplementedError("the labels' BatchNorm1d of one projector layer share mode and eps")
+            y = torch.empty(B, SC, dtype=torch.float32, device=dev)
+            prow = (B + 127) // 128
+            part = torch.empty(prow, 2, SC, dtype=torch.float32, device=dev) if train else None
+            if j == 0:
+                ops.conv_gemm(ops.fwd_desc(SM3_F32, B, 1, 1, bk["Cin"], SC, 1, 1, 0), h, bk["w"].view(SC, bk["Cin"]), y, None, part)
+            else:
+                ops.grouped_gemm(h, bk["w"], y, S, part)
+            scale = torch.empty(SC, dtype=torch.float32, device=dev)
+            shift = torch.empty_like(scale)
+            mean = invstd = None
+            if train:
+                if B < 2:
+                    raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d)")
+                rm = torch.cat([bn.running_mean for bn in bns]).contiguous()
+                rv = torch.cat([bn.running_var for bn in bns]).contiguous()
+                nbt = torch.zeros(1, dtype=torch.int64, device=dev)
+                mean, invstd = torch.empty_like(scale), torch.empty_like(scale)
+                ws, groups = ops.bn_stats_reduce(part, prow, SC, None)
+                ops.bn_finalize(ws, B, SC, bk["gamma"], bk["beta"], bns[0].eps, float(bns[0].momentum), rm, rv, nbt, scale,
+                                shift, mean, invstd, groups=groups)
+                C = bk["C"]
+                with torch.no_grad():
+                    for s, bn in enumerate(bns):  # the running buffers stay in the labels' own modules
+                        bn.running_mean.copy_(rm[s * C:(s + 1) * C])
+                        bn.running_var.copy_(rv[s * C:(s + 1) * C])
+                        bn.num_batches_tracked.add_(1)
+            else:
+                rm = torch.cat([bn.running_mean for bn in bns]).contiguous()
+                rv = torch.cat([bn.running_var for bn in bns]).contiguous()
+                ops.bn_eval_scale_shift(bk["gamma"], bk["beta"], rm, rv, bns[0].eps, SC, scale, shift)
+            out = torch.empty_like(y)
+            ops.bn_act(SM3_F32, y, scale, shift, None, relu, out, B, SC)
+            recs.append(dict(x=h, y=y, out=out, mean=mean, invstd=invstd, train=train))
+            h = out
+        return h, recs
+
+    def _mlp_backward(self, recs, dh, need_dfeats, need_params):
+        """dh [B, S*D] (label-major) -> projector parameter gradients (list in proj_params order, or None) and dfeats."""
+        S, B, dev = self.S, dh.shape[0], dh.device
+        banks = self._mlp_banks()
+        grads_w, grads_g, grads_b = [None] * len(self.layers), [None] * len(self.layers), [None] * len(self.layers)
+        dfeats = None
+        for j in range(len(self.layers) - 1, -1, -1):
+            bk, r = banks[j], recs[j]
+            C, Cin = bk["C"], bk["Cin"]
+            SC = S * C
+            if not r["train"]:
+                raise NotImplementedError("backward through a label projector whose BatchNorm1d is in eval mode "
+                                          "(the reference freezes such projectors: mlc_eval.py --finetune fc)")
+            prow = ops.bn_bwd_partial_rows(B, SC)
+            bpart = torch.empty(prow, 2, SC, dtype=torch.float32, device=dev)
+            dz = torch.empty_like(dh)
+            ops.bn_bwd_reduce(SM3_F32, dh, r["out"] if bk["relu"] else None, r["y"], r["mean"], r["invstd"], dz, B, SC, bpart)
+            lsums = torch.empty(2 * SC, dtype=torch.float64, device=dev)
+            ops.bn_stats_reduce(bpart, prow, SC, lsums)
+            dgam = torch.zeros(SC, dtype=torch.float32, device=dev) if bk["gamma"] is not None else None
+            dbet = torch.zeros(SC, dtype=torch.float32, device=dev) if bk["gamma"] is not None else None
+            dy = torch.empty_like(dz)
+            ops.bn_bwd_apply(SM3_F32, dz, r["y"], r["mean"], r["invstd"], bk["gamma"], lsums, B, lsums, dgam, dbet, dy, B, SC)
+            grads_g[j], grads_b[j] = dgam, dbet
+            if j == 0:
+                if need_params:
+                    dw = torch.zeros(SC, Cin, dtype=torch.float32, device=dev)
+                    cap = ops.grouped_wgrad_slab_cap(B, SC * Cin)
+                    # (capacity 1: one slice adds its tiles to dw itself and the slab buffer is never written)
+                    slabs = dw if cap == 1 else torch.empty(cap * SC * Cin, dtype=torch.float32, device=dev)
+                    ops.conv_wgrad_det(ops.fwd_desc(SM3_F32, B, 1, 1, Cin, SC, 1, 1, 0), r["x"], dy, dw, slabs, cap)
+                    grads_w[j] = dw.view(S, C, Cin)
+                if need_dfeats:
+                    dfeats = torch.empty(B, Cin, dtype=torch.float32, device=dev)
+                    ops.conv_gemm(ops.fwd_desc(SM3_F32, B, 1, 1, SC, Cin, 1, 1, 0), dy, bk["wt"], dfeats)
+            else:
+                if need_params:
+                    dw = torch.zeros(S, C, Cin, dtype=torch.float32, device=dev)
+                    cap = ops.grouped_wgrad_slab_cap(B, C * Cin)
+                    slabs = dw if cap == 1 else None  # (see above)
+                    ops.grouped_wgrad_det(r["x"], dy, dw, S, slabs)
+                    grads_w[j] = dw
+                dh = torch.empty(B, S * Cin, dtype=torch.float32, device=dev)
+                ops.grouped_gemm(dy, bk["wt"], dh, S)
+        if not need_params:
+            return None, dfeats
+        out = []
+        for s in range(S):
+            for j, (li, bi, relu) in enumerate(self.layers):
+                C = banks[j]["C"]
+                out.append(grads_w[j][s])
+                if banks[j]["gamma"] is not None:
+                    out += [grads_g[j][s * C:(s + 1) * C], grads_b[j][s * C:(s + 1) * C]]
+        return out, dfeats
+
     # ---- forward / backward ---------------------------------------------------------------------------------------
     def forward(self, feats, seed, train=True):
         m, sa, lib = self.model, self.model.mlc_sa, _lib.load()
@@ -89,11 +271,20 @@ class MLCHeads:
         R, p = S * B, (self.p if train else 0.0)
         seed = int(seed) & 0x7FFFFFFF
         ones = torch.ones(max(3 * D, sa.linear1.out_features), dtype=torch.float32, device=dev)
-        x0 = torch.empty(R, D, dtype=torch.float32, device=dev)          # row = s*B + b (the reference's [S, B, D])
-        for s, l in enumerate(m.projectors.projectors):
-            blk = x0[s * B:(s + 1) * B]
-            self._gemm(feats, l[0].weight.detach(), blk)
-            self._bias(blk, l[0].bias.detach(), ones)
+        mlp = None
+        if self.kind == "v4":
+            x0 = torch.empty(R, D, dtype=torch.float32, device=dev)          # row = s*B + b (the reference's [S, B, D])
+            for s, l in enumerate(m.projectors.projectors):
+                blk = x0[s * B:(s + 1) * B]
+                self._gemm(feats, l[0].weight.detach(), blk)
+                self._bias(blk, l[0].bias.detach(), ones)
+        elif self.kind == "v0":
+            if feats.shape[1] != D:
+                raise ValueError(f"--mlc-proj v0: features of width {feats.shape[1]} for d_model {D}")
+            x0 = feats                                                        # the one label token (mlc_train.py:76-79)
+        else:
+            h, mlp = self._mlp_forward(feats)
+            x0 = h.view(B, S, D).transpose(0, 1).contiguous().view(R, D)     # label-major columns -> [S, B, D] rows
         att = sa.self_attn
         qkv = self._gemm(x0, att.in_proj_weight.detach())
         self._bias(qkv, att.in_proj_bias.detach(), ones)
@@ -121,21 +312,22 @@ class MLCHeads:
         logits = torch.empty(B, T, dtype=torch.float32, device=dev)
         check(lib.sm3_mlc_heads_fwd(_P(x2), _P(wp), _P(bp), _P(tok), int(bool(m.l2_norm)), _P(logits), B, S, D, T, 1, _st()),
               "sm3_mlc_heads_fwd")
-        saved = dict(feats=feats, x0=x0, qkv=qkv, a=a, o=o, x1=x1, st1=st1, h=h, hd=hd, fo=fo, x2=x2, st2=st2, wp=wp, tok=tok,
+        saved = dict(feats=feats, mlp=mlp, x0=x0, qkv=qkv, a=a, o=o, x1=x1, st1=st1, h=h, hd=hd, fo=fo, x2=x2, st2=st2, wp=wp, tok=tok,
                      B=B, p=p, seed=seed)
         sa_feats = x2.view(S, B, D)
         if m.l2_norm:
             sa_feats = torch.nn.functional.normalize(sa_feats, dim=-1, p=2)
         return sa_feats, logits, saved
 
-    def backward(self, sv, dlogits, need_dfeats):
+    def backward(self, sv, dlogits, need_dfeats, need_proj=True):
         m, sa, lib = self.model, self.model.mlc_sa, _lib.load()
         att = sa.self_attn
         B, S, D, p, seed = sv["B"], self.S, self.D, sv["p"], sv["seed"]
         R = S * B
         dev = dlogits.device
         z = lambda t: torch.zeros_like(t, dtype=torch.float32)
-        g = {id(q): z(q) for q in self.params()}
+        skip = {id(q) for q in self.proj_params()} if self.kind == "mlp" else set()  # (filled by _mlp_backward, or None)
+        g = {id(q): (None if id(q) in skip else z(q)) for q in self.params()}
         G = lambda q: g[id(q)]
         dlogits = dlogits.contiguous().float()
         T = sv["wp"].shape[0]
@@ -181,6 +373,17 @@ class MLCHeads:
         self._gemm(dqkv, att.in_proj_weight.detach().t().contiguous(), out=dx0, addend=dx0)
         # label projectors
         dfeats = None
+        if self.kind == "v0":
+            return [g[id(q)] for q in self.params()], (dx0 if need_dfeats else None)
+        if self.kind == "mlp":
+            if not (need_proj or need_dfeats):
+                return [g[id(q)] for q in self.params()], None
+            dh = dx0.view(S, B, D).transpose(0, 1).contiguous().view(B, S * D)
+            pg, dfeats = self._mlp_backward(sv["mlp"], dh, need_dfeats, need_proj)
+            if pg is not None:
+                for q, t in zip(self.proj_params(), pg):
+                    g[id(q)] = t
+            return [g[id(q)] for q in self.params()], dfeats
         for s, l in enumerate(m.projectors.projectors):
             blk = dx0[s * B:(s + 1) * B]
             self._colsum(blk, G(l[0].bias))
@@ -200,13 +403,14 @@ class _HeadsFn(torch.autograd.Function):
         sa_feats, logits, saved = heads.forward(feats, seed, train)
         ctx.heads, ctx.saved = heads, saved
         ctx.need_dfeats = feats.requires_grad
+        ctx.need_proj = any(q.requires_grad for q in heads.proj_params())
         ctx.mark_non_differentiable(sa_feats)  # the memory bank takes it detached (mlc_train.py:268-271)
         return sa_feats, logits
 
     @staticmethod
     def backward(ctx, _dsa, dlogits):
         with ops.stream_scope():
-            grads, dfeats = ctx.heads.backward(ctx.saved, dlogits, ctx.need_dfeats)
+            grads, dfeats = ctx.heads.backward(ctx.saved, dlogits, ctx.need_dfeats, ctx.need_proj)
         ctx.saved = None
         return (None, None, None, dfeats) + tuple(grads)
 

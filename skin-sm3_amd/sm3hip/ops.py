@@ -507,6 +507,53 @@ def slab_reduce(slabs, nslabs, n, out, accumulate=False):
               "sm3_slab_reduce")
 
 
+def grouped_gemm(x, w, y, groups, partials=None):
+    """y[:, g*N:(g+1)*N] = x[:, g*K:(g+1)*K] @ w[g]^T for g < groups, one exact-f32 launch (sm3_grouped_gemm).  x: [rows, G*K],
+    w: [G, N, K] (or [G*N, K]), y: [rows, G*N] fp32; partials: [ceil(rows / 128), 2, G*N] BatchNorm sums of y, or None.
+    The data gradient is the same call with the transposed banks [G, K, N]."""
+    for t, n in ((x, "x"), (w, "w"), (y, "y")):
+        _chk(t, torch.float32, n)
+    _chk(partials, torch.float32, "partials")
+    rows = x.shape[0]
+    K, N = x.shape[1] // groups, y.shape[1] // groups
+    if x.dim() != 2 or y.dim() != 2 or y.shape[0] != rows or K * groups != x.shape[1] or N * groups != y.shape[1]:
+        raise ValueError("grouped_gemm: x [rows, G*K] and y [rows, G*N]")
+    if w.numel() != groups * N * K:
+        raise ValueError("grouped_gemm: w must hold G banks [N, K]")
+    if K % K_CHUNK[SM3_F32] or N % 4:
+        raise ValueError(f"grouped_gemm: K a multiple of {K_CHUNK[SM3_F32]}, N of 4")
+    if partials is not None and partials.numel() < ((rows + 127) // 128) * 2 * groups * N:
+        raise ValueError("grouped_gemm: partials too small")
+    with _prof("grouped_gemm", 2.0 * rows * groups * N * K, 4.0 * (x.numel() + w.numel() + y.numel())):
+        check(_lib.load().sm3_grouped_gemm(SM3_F32, _ptr(x), _ptr(w), _ptr(y), _ptr(partials), rows, groups, K, N, _stream()),
+              "sm3_grouped_gemm")
+
+
+def grouped_wgrad_slab_cap(rows, n):
+    """Slabs sm3_grouped_wgrad_det may fill for one group of n floats: wgrad_det_cap(n), and never more than the slices a
+    1x1 f32 product of `rows` pixels is cut into (32 pixels per K-group pair x 8) -- a function of (rows, n) alone."""
+    return max(1, min(wgrad_det_cap(n), (rows + 255) // 256))
+
+
+def grouped_wgrad_det(x, dy, dw, groups, slabs=None):
+    """dw[g] += dy[:, g*N:(g+1)*N]^T @ x[:, g*K:(g+1)*K], fixed order (sm3_grouped_wgrad_det).  dw: [G, N, K] fp32."""
+    for t, n in ((x, "x"), (dy, "dy"), (dw, "dw")):
+        _chk(t, torch.float32, n)
+    rows = x.shape[0]
+    K, N = x.shape[1] // groups, dy.shape[1] // groups
+    if dy.shape[0] != rows or K * groups != x.shape[1] or N * groups != dy.shape[1] or dw.numel() != groups * N * K:
+        raise ValueError("grouped_wgrad_det: x [rows, G*K], dy [rows, G*N], dw [G, N, K]")
+    cap = grouped_wgrad_slab_cap(rows, N * K)
+    if slabs is None:
+        slabs = torch.empty(cap * groups * N * K, dtype=torch.float32, device=x.device)
+    _chk(slabs, torch.float32, "slabs")
+    if slabs.numel() < cap * groups * N * K:
+        raise ValueError("grouped_wgrad_det: slab buffer too small")
+    with _prof("grouped_wgrad", 2.0 * rows * groups * N * K, 4.0 * (x.numel() + dy.numel() + dw.numel())):
+        check(_lib.load().sm3_grouped_wgrad_det(SM3_F32, _ptr(x), _ptr(dy), _ptr(dw), _ptr(slabs), int(cap), rows, groups, K, N,
+                                                _stream()), "sm3_grouped_wgrad_det")
+
+
 def conv_wgrad_cat(desc, x, dy, dw, dy1=None, dw1=None, views=1):
     """P[v] = dy_v^T x_v -> dw [views][Co][Ci] (and, with dy1, G[v] = dy1_v^T x_v -> dw1 [views][Co1][Ci]) in one launch
     (sm3_conv_wgrad_cat), accumulated into fp32 buffers the caller zeroed."""

@@ -103,6 +103,22 @@ def require_mlc_arch(arch, tool):
                          f"features (one of {', '.join(MLC_ARCHS)}); resnet18/34 run in backbone_train / backbone_eval")
 
 
+MLC_FEAT_DIM = 2 * 2048  # cat(derm, clinic) pooled features of the Bottleneck encoders the multi-label tools take
+
+
+def require_mlc_proj(args, tool):
+    """--mlc-proj v0..v4 (mlc_train.py:352-361) with --num-labels 8; v0 (nn.Identity) needs --mlc-proj-dim equal to the
+    feature width, which the reference only finds out when its first batch fails.  Checked before any kernel runs."""
+    from src.models.projector import MLC_PROJ_KINDS
+    if args.mlc_proj not in MLC_PROJ_KINDS:
+        raise SystemExit(f"{tool}: --mlc-proj {args.mlc_proj} is not one of {', '.join(MLC_PROJ_KINDS)}")
+    if args.num_labels != 8:
+        raise SystemExit(f"{tool}: the native head path builds 8 labels (--num-labels 8, run.sh:39-61)")
+    if args.mlc_proj == "v0" and args.mlc_proj_dim != MLC_FEAT_DIM:
+        raise SystemExit(f"{tool}: --mlc-proj v0 passes the {MLC_FEAT_DIM}-wide features to the label attention unchanged, "
+                         f"so --mlc-proj-dim must be {MLC_FEAT_DIM} (got {args.mlc_proj_dim})")
+
+
 def describe_ignored(args, parser):
     """Names of the compatibility-only flags the caller set to something other than their default."""
     out = []

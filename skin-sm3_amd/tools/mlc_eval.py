@@ -9,7 +9,9 @@ trains with the weighted cross-entropy sum / 8 against the real labels, reports 
 
 --finetune fc: extractor and label projectors frozen; projector: extractor frozen; all: encoder stages layer1-4 of both
 backbones trainable as well (stem frozen), gradient flowing into the HIP encoders through the autograd bridge.  The heads
-train on sm3hip/mlc.py in every mode.  The derm7pt dataset is out of scope: synthetic images and labels."""
+train on sm3hip/mlc.py in every mode.  The derm7pt dataset is out of scope: synthetic images and labels.
+
+--mlc-proj picks the label projectors as the reference does (default v4): v0 nn.Identity (--mlc-proj-dim must be 4096), v1 / v2 / v3 the per-label BN-MLPs of src/models/projector.py, v4 one biased Linear per label; unknown kinds are refused before anything runs."""
 import argparse
 import os
 import sys
@@ -25,7 +27,7 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
-from src.models.projector import MultiLabelProjector4  # noqa: E402
+from src.models.projector import build_mlc_projectors  # noqa: E402
 from src.models.simclr import SimCLRSkinV32  # noqa: E402
 
 
@@ -136,11 +138,11 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train):
 def main(argv=None):
     args = get_parser().parse_args(argv)
     from src.utils.misc import require_mlc_arch
+    from src.utils.misc import require_mlc_proj
     require_mlc_arch(args.arch, "mlc_eval")
+    require_mlc_proj(args, "mlc_eval")
     if args.data_name != "synthetic":
         raise SystemExit("only --data-name synthetic is available in this build (dataset pipeline is out of scope)")
-    if args.mlc_proj != "v4" or args.num_labels != 8:
-        raise SystemExit("the native head path builds --mlc-proj v4 with 8 labels (run.sh:49-61)")
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", 0)
     extractor = SimCLRSkinV32(arch=args.arch, proj_dim=args.extractor_proj_dim)
@@ -151,7 +153,7 @@ def main(argv=None):
     extractor.sm3_dtype = amp_dtype(args)
     args.scaler = torch.amp.GradScaler("cuda", enabled=amp_dtype(args) == torch.float16)  # mlc_eval.py:331
     feat_dim = extractor.derm_feat_dim + extractor.clinic_feat_dim
-    evaluator = Model(extractor, MultiLabelProjector4(feat_dim, args.mlc_proj_dim, args.num_labels), args.mlc_proj_dim,
+    evaluator = Model(extractor, build_mlc_projectors(args.mlc_proj, feat_dim, args.mlc_proj_dim, args.num_labels), args.mlc_proj_dim,
                       args.l2_norm, args.num_heads, args.sa_dim_ff, args.sa_dropout)
     if args.pretrain_path and os.path.isfile(args.pretrain_path):
         state = torch.load(args.pretrain_path, map_location="cpu", weights_only=False)["state_dict"]

@@ -12,7 +12,9 @@ the heads and their training through sm3hip/mlc.py, the k-means through csrc/hea
 reference's own (nn.CrossEntropyLoss on the predictions / temperature, torch.optim.AdamW on the trainable parameters).
 Differences, stated: the derm7pt dataset and its PIL pipeline are out of scope, `--data-name synthetic` generates a fixed
 set of learnable image pairs on the device; data parallelism gathers the memory bank with torch.distributed as the
-reference does (:136-143,185-186)."""
+reference does (:136-143,185-186).
+
+--mlc-proj picks the label projectors as the reference does (default v4): v0 nn.Identity (--mlc-proj-dim must be 4096), v1 / v2 / v3 the per-label BN-MLPs of src/models/projector.py, v4 one biased Linear per label; unknown kinds are refused before anything runs."""
 import argparse
 import os
 import sys
@@ -30,7 +32,7 @@ import torch.distributed as dist  # noqa: E402
 import torch.multiprocessing as mp  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from src.models.projector import MultiLabelProjector4  # noqa: E402
+from src.models.projector import build_mlc_projectors  # noqa: E402
 from src.models.simclr import SimCLRSkinV32  # noqa: E402
 
 NUM_CLASSES = [5, 3, 2, 3, 3, 3, 3, 2]
@@ -136,7 +138,9 @@ def cluster_memory(args, prototype, K, local_index, local_emb, nmb_kmeans_iters=
 
 def main(local_rank, args):
     from src.utils.misc import require_mlc_arch
+    from src.utils.misc import require_mlc_proj
     require_mlc_arch(args.arch, "mlc_train")
+    require_mlc_proj(args, "mlc_train")
     world = args.world_size
     args.rank = local_rank
     # test knobs, as in bench.py (a 2-rank rehearsal on a one-GPU box: both ranks on device 0 over gloo)
@@ -149,8 +153,6 @@ def main(local_rank, args):
     torch.manual_seed(args.seed)
     if args.data_name != "synthetic":
         raise SystemExit("only --data-name synthetic is available in this build (dataset pipeline is out of scope)")
-    if args.mlc_proj != "v4" or args.num_labels != 8:
-        raise SystemExit("the native head path builds --mlc-proj v4 with 8 labels (run.sh:39-47)")
     bs = args.batch_size // world
 
     extractor = SimCLRSkinV32(arch=args.arch, proj_dim=args.extractor_proj_dim)
@@ -165,7 +167,7 @@ def main(local_rank, args):
         for p in extractor.parameters():
             p.requires_grad = False
     feat_dim = extractor.derm_feat_dim + extractor.clinic_feat_dim
-    model = Model(extractor, MultiLabelProjector4(feat_dim, args.mlc_proj_dim, args.num_labels), args.mlc_proj_dim,
+    model = Model(extractor, build_mlc_projectors(args.mlc_proj, feat_dim, args.mlc_proj_dim, args.num_labels), args.mlc_proj_dim,
                   args.l2_norm, args.num_heads, args.sa_dim_ff, args.sa_dropout).to(dev)
     wrapped = nn.parallel.DistributedDataParallel(model, device_ids=[dev_index]) if world > 1 else model
     parameters = [p for p in model.parameters() if p.requires_grad]
