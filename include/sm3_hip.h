@@ -613,6 +613,30 @@ int sm3_grouped_gemm(int dtype, const void* x, const void* w, void* y, float* st
 int sm3_grouped_wgrad_det(int dtype, const void* x, const void* dy, float* dw, float* slabs, int slab_capacity, int rows,
                           int groups, int K, int N, void* stream);
 
+/* ---- grouped 3x3 convolution: ResNeXt's conv2 (reference src/models/resnet.py:142-146, conv3x3(width, width, stride, groups)),
+ * csrc/gconv.hip ---------------------------------------------------------------------------------------------------------------
+ * NHWC activations [N][H][W][C] (rows = pixels), pad 1, stride 1 or 2, `groups` groups of cg = C / groups channels with cg in
+ * {4, 8, 16, 32, 64} and C a multiple of 64; all three dtypes (f32 accumulation).  Sizes and dtypes are checked on the host
+ * (SM3_EINVAL / SM3_EALIGN / SM3_EDTYPE) before anything is launched; every pointer must be 16-byte aligned.
+ * Weight prep: master [C][3][3][cg] fp32 (OHWI) -> w_fwd [9][cg][C] (w_fwd[t][k][co] = w[co][t][k]) and w_dgrad [9][cg][C]
+ * (w_dgrad[t][j][g*cg + k] = w[g*cg + j][t][k]), `dtype`; only_if (nullable device int): skip when *only_if == 0.
+ * Forward: y [N][Ho][Wo][C], Ho = (H - 1) / stride + 1; stat_partials (nullable): the BatchNorm partial rows of
+ * sm3_conv_gather_gemm ([ceil(N*Ho*Wo / 128)][2][C] sums and sums of squares of the rounded outputs), for the unchanged
+ * sm3_bn_stats_reduce / sm3_bn_finalize path.
+ * Data gradient: dx [N][H][W][C] from dy [N][Ho][Wo][C] (H, W: the forward input's map).
+ * Weight gradient, a function of its inputs: dw [C][3][3][cg] += dy^T x, as sm3_gconv_wgrad_slabs(N, H, W, stride, capacity)
+ * plain-store slabs of C*9*cg floats (the pixel partition depends on the geometry and the capacity only) and one
+ * sm3_slab_reduce; no float atomics. */
+int sm3_gconv_weight_prep(int dtype, const float* master, void* w_fwd, void* w_dgrad, int C, int groups, const int* only_if,
+                          void* stream);
+int sm3_gconv_fwd(int dtype, const void* x, const void* w_fwd, void* y, float* stat_partials, int N, int H, int W, int C,
+                  int groups, int stride, void* stream);
+int sm3_gconv_dgrad(int dtype, const void* dy, const void* w_dgrad, void* dx, int N, int H, int W, int C, int groups, int stride,
+                    void* stream);
+int sm3_gconv_wgrad_slabs(int N, int H, int W, int stride, int slab_capacity);
+int sm3_gconv_wgrad_det(int dtype, const void* x, const void* dy, float* dw, float* slabs, int slab_capacity, int N, int H,
+                        int W, int C, int groups, int stride, void* stream);
+
 /* ---- peer-to-peer SyncBatchNorm statistics exchange on one node (csrc/p2p.hip; opt-in, RCCL is the default) ----------------
  * Replaces the all-reduce torch.nn.SyncBatchNorm performs per BatchNorm and direction (tools/backbone_train.py:510) for the
  * fp64 [views][2C] sums of sm3_bn_stats_reduce / sm3_linbn_fold / sm3_linbn_stats.

@@ -83,9 +83,10 @@ class Model(nn.Module):
 
 def build_model(arch="resnet50", mlc_proj_dim=512, num_labels=8, l2_norm=False, num_heads=1, sa_dim_ff=128,
                 sa_dropout=0.1):
-    if arch not in ("resnet50", "resnet101", "resnet152"):
+    from src.utils.misc import MLC_ARCHS
+    if arch not in MLC_ARCHS:
         raise NotImplementedError(f"arch {arch!r}: the multi-label model is built on 2048-wide Bottleneck features "
-                                  "(resnet50/101/152)")
+                                  f"({', '.join(MLC_ARCHS)})")
     extractor = Extractor(arch)
     feat_dim = extractor.derm_feat_dim + extractor.clinic_feat_dim
     return Model(extractor, MultiLabelProjector(feat_dim, mlc_proj_dim, num_labels), mlc_proj_dim, l2_norm, num_heads,

@@ -161,6 +161,11 @@ SIGNATURES = {
     "sm3_mlc_kmeans_update": [_P, _P, _P, _I, _I, _P],
     "sm3_grouped_gemm": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "sm3_grouped_wgrad_det": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sm3_gconv_weight_prep": [_I, _P, _P, _P, _I, _I, _P, _P],
+    "sm3_gconv_fwd": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "sm3_gconv_dgrad": [_I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "sm3_gconv_wgrad_slabs": [_I, _I, _I, _I, _I],
+    "sm3_gconv_wgrad_det": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 
 _lib = None

@@ -98,8 +98,15 @@ class ParamStore:
 # layer units
 # ------------------------------------------------------------------------------------------
 class ConvUnit:
-    def __init__(self, name, Ci, Co, k, stride, pad, stem=False):
+    """groups > 1: a grouped 3x3 convolution (ResNeXt conv2, Ci == Co) on the kernels of csrc/gconv.hip, whose banks are
+    [9][Co / groups][Co] in forward and in data-gradient order (sm3_gconv_weight_prep); none of the dense-kernel forms
+    (halo-resident A image, SM3_CONV_BNIN, nine-tap owner weight gradient, fused data-gradient epilogues) applies to it."""
+
+    def __init__(self, name, Ci, Co, k, stride, pad, stem=False, groups=1):
         self.name, self.Ci, self.Co, self.k, self.stride, self.pad, self.stem = name, Ci, Co, k, stride, pad, stem
+        self.groups = groups
+        if groups > 1 and (k != 3 or pad != 1 or Ci != Co or stem):
+            raise ValueError("grouped convolutions: 3x3, pad 1, Ci == Co only")
         self.taps = k * k
         self.w_fwd = self.w_dgrad = None
         self._fd, self._dd = {}, {}
@@ -108,13 +115,19 @@ class ConvUnit:
         tdt = ops.TORCH_DTYPE[dtype]
         if self.stem:
             self.w_fwd = torch.empty(self.Co, ops.STEM_KDIRECT if direct_stem else STEM_KPAD, dtype=tdt, device=device)
+        elif self.groups > 1:
+            n = self.taps * self.Co * (self.Ci // self.groups)
+            self.w_fwd = torch.empty(n, dtype=tdt, device=device)
+            self.w_dgrad = torch.empty(n, dtype=tdt, device=device)
         else:
             self.w_fwd = torch.empty(self.Co, self.taps * self.Ci, dtype=tdt, device=device)
             if need_dgrad:
                 self.w_dgrad = torch.empty(self.Ci, self.taps, self.Co, dtype=tdt, device=device)
 
     def refresh(self, dtype, master2d):
-        if self.stem:
+        if self.groups > 1:
+            ops.gconv_weight_prep(dtype, master2d, self.Co, self.groups, self.w_fwd, self.w_dgrad)
+        elif self.stem:
             ops.weight_prep(dtype, master2d, self.Co, 1, 147, self.w_fwd, STEM_KPAD, None)
         else:
             ops.weight_prep(dtype, master2d, self.Co, self.taps, self.Ci, self.w_fwd, self.taps * self.Ci,
@@ -224,9 +237,13 @@ class EncoderPlan:
     s) where the block changes the stride or the width (reference resnet.py:251-262) -- every stage entry of a Bottleneck
     network, layer2..4 of a BasicBlock one.  The last unit of a block is always its join (bn + identity + ReLU)."""
 
-    def __init__(self, prefix, block_counts=(3, 4, 6, 3), block="bottleneck"):
+    def __init__(self, prefix, block_counts=(3, 4, 6, 3), block="bottleneck", groups=1, width_per_group=64):
+        """groups / width_per_group (Bottleneck only): a ResNeXt -- c1 / c2 / c3 are inplanes -> width -> width -> 4 * planes,
+        width = int(planes * width_per_group / 64) * groups, c2 grouped (reference resnet.py:142-148)."""
         if block not in ("bottleneck", "basic"):
             raise ValueError(block)
+        if block == "basic" and (groups != 1 or width_per_group != 64):
+            raise ValueError("BasicBlock only supports groups=1 and base_width=64")
         self.prefix = prefix
         self.basic = block == "basic"
         self.stem = ConvUnit(prefix + "conv1", 3, 64, 7, 2, 3, stem=True)
@@ -244,10 +261,11 @@ class EncoderPlan:
                         "c2": ConvUnit(p + "conv2", planes, planes, 3, 1, 1), "b2": BNUnit(p + "bn2", planes),
                     }
                 else:
+                    wd = int(planes * (width_per_group / 64.0)) * groups
                     blk = {
-                        "c1": ConvUnit(p + "conv1", inpl, planes, 1, 1, 0), "b1": BNUnit(p + "bn1", planes),
-                        "c2": ConvUnit(p + "conv2", planes, planes, 3, s, 1), "b2": BNUnit(p + "bn2", planes),
-                        "c3": ConvUnit(p + "conv3", planes, planes * 4, 1, 1, 0), "b3": BNUnit(p + "bn3", planes * 4),
+                        "c1": ConvUnit(p + "conv1", inpl, wd, 1, 1, 0), "b1": BNUnit(p + "bn1", wd),
+                        "c2": ConvUnit(p + "conv2", wd, wd, 3, s, 1, groups=groups), "b2": BNUnit(p + "bn2", wd),
+                        "c3": ConvUnit(p + "conv3", wd, planes * 4, 1, 1, 0), "b3": BNUnit(p + "bn3", planes * 4),
                     }
                 if s != 1 or inpl != planes * exp:
                     blk["cd"] = ConvUnit(p + "downsample.0", inpl, planes * exp, 1, s, 0)
@@ -290,6 +308,12 @@ def enc_block(enc_mod):
     return getattr(enc_mod, "block_type", "bottleneck")
 
 
+def enc_plan(prefix, enc_mod):
+    """The EncoderPlan of a src.models.resnet.ResNet: block type, block counts, groups and width per group from the module."""
+    return EncoderPlan(prefix, enc_mod.block_counts, enc_block(enc_mod), getattr(enc_mod, "groups", 1),
+                       getattr(enc_mod, "base_width", 64))
+
+
 class SM3Engine:
     """Runs SimCLRSkinV3 / V32 (and a bare encoder) on the HIP kernels.
 
@@ -322,7 +346,7 @@ class SM3Engine:
             proj_dim = module.proj_dim
             for key in ("derm", "clinic"):
                 enc_mod = getattr(module, key + "_backbone").encoder
-                self.branches[key] = (EncoderPlan(f"{key}_backbone.encoder.", enc_mod.block_counts, enc_block(enc_mod)),
+                self.branches[key] = (enc_plan(f"{key}_backbone.encoder.", enc_mod),
                                       ProjectorPlan(f"{key}_backbone.projector.", enc_mod_out_dim(enc_mod), proj_dim))
             dims = [self.branches[k][0].out_dim for k in ("derm", "clinic")]
             if kind == "v3":
@@ -334,10 +358,10 @@ class SM3Engine:
             if getattr(module, "meta_proj", None) is not None:  # metadata-MLP extension (src/models/simclr.py)
                 self.meta = ProjectorPlan("meta_proj.", module.meta_proj[0].in_features, proj_dim)
         elif kind == "simclr":
-            self.branches["main"] = (EncoderPlan("encoder.", module.encoder.block_counts, enc_block(module.encoder)),
+            self.branches["main"] = (enc_plan("encoder.", module.encoder),
                                      ProjectorPlan("projector.", module.encoder_out_dim, module.proj_dim))
         elif kind == "encoder":
-            self.branches["main"] = (EncoderPlan("", module.block_counts, enc_block(module)), None)
+            self.branches["main"] = (enc_plan("", module), None)
         else:
             raise ValueError(kind)
         self._ws = {}
@@ -434,22 +458,25 @@ class SM3Engine:
         key = (self.store.flat_p.data_ptr(), len(self.store.names), self.dtype)
         cache = self.__dict__.setdefault("_wprep_cache", {})
         if key not in cache:
-            groups = {k: ([], []) for k in list(self.branches) + [None]}
+            groups = {k: ([], [], []) for k in list(self.branches) + [None]}
             for cu in self._all_conv_units():
                 wname = cu.name + ".weight"
                 if wname not in self.store.offsets:
                     continue  # projector dropped by the caller (mlc_train.py:344-346 sets them to None)
                 owner = next((k for k in self.branches if k != "main" and wname.startswith(k + "_")), None)
-                items, stems = groups[owner]
+                items, stems, gconvs = groups[owner]
                 m = self.store.flat2d(self.store.flat_p, wname)
-                if cu.stem and self.direct_stem:
+                if cu.groups > 1:
+                    gconvs.append((m, cu))
+                elif cu.stem and self.direct_stem:
                     stems.append((m, cu.w_fwd))
                 elif cu.stem:
                     items.append((m, cu.w_fwd, None, cu.Co, 1, 147, STEM_KPAD))
                 else:
                     items.append((m, cu.w_fwd, cu.w_dgrad, cu.Co, cu.taps, cu.Ci, cu.taps * cu.Ci))
             dev = self.store.flat_p.device
-            tables = {k: (ops.weight_prep_table(items, dev) if items else None, stems) for k, (items, stems) in groups.items()}
+            tables = {k: (ops.weight_prep_table(items, dev) if items else None, stems, gconvs)
+                      for k, (items, stems, gconvs) in groups.items()}
             cache[key] = (tables, torch.zeros(2, dtype=torch.int64, device=dev), torch.ones(1, dtype=torch.int32, device=dev))
         tables, hstate, changed = cache[key]
         # Frozen masters (linear probe, multi-label heads, inference: the same encoders forward after forward) keep their
@@ -466,17 +493,19 @@ class SM3Engine:
             self._hash_tracks_banks = False  # unconditional re-layout: the remembered hash no longer describes the banks
         self._wprep_key, self.weights_dirty = key, False
         self._lane_prep = {}
-        for k, (table, stems) in tables.items():
+        for k, (table, stems, gconvs) in tables.items():
             if defer_lanes and k is not None:
-                self._lane_prep[k] = (table, stems, only_if)
+                self._lane_prep[k] = (table, stems, gconvs, only_if)
             else:
-                self._prep(table, stems, only_if)
+                self._prep(table, stems, gconvs, only_if)
 
-    def _prep(self, table, stems, only_if):
+    def _prep(self, table, stems, gconvs, only_if):
         if table is not None:
             ops.weight_prep_batch(self.dtype, table, only_if)
         for m, w in stems:
             ops.stem_weight_prep(self.dtype, m, w, only_if)
+        for m, cu in gconvs:  # grouped 3x3 banks: one launch per unit
+            ops.gconv_weight_prep(self.dtype, m, cu.Co, cu.groups, cu.w_fwd, cu.w_dgrad, only_if)
 
     def prep_lane(self, key):
         """The filter banks of branch `key`, on the current (= that branch's lane) stream; see refresh_weights."""
@@ -630,6 +659,8 @@ class SM3Engine:
             partials = self._work("partials", prow * 2 * C)
             if direct:
                 (ops.stem_conv_fwd16 if isinstance(x, ops.StemImage) else ops.stem_conv_fwd)(self.dtype, x, cu.w_fwd, xo, partials)
+            elif cu.groups > 1:
+                ops.gconv_fwd(self.dtype, x, cu.w_fwd, xo, partials, N, H, W, C, cu.groups, cu.stride)
             elif bn_in is not None:
                 ops.conv3x3_bnin(d, bn_in[0], bn_in[1], bn_in[2], x, bn_in[3], cu.w_fwd, xo, partials, views=V)
             else:
@@ -691,8 +722,9 @@ class SM3Engine:
                 pending.append((V * 2 * C, finalize))
             else:
                 finalize()
-        elif save is None and not out_f32 and apply:
+        elif save is None and not out_f32 and apply and cu.groups == 1:
             # inference: conv + running-statistics BN (+residual) (+ReLU) in ONE launch, no pre-BN tensor in HBM
+            # (a grouped unit takes the two-pass form below: grouped convolution, then the BatchNorm apply pass)
             if y_out is None:
                 y_out = xo
             ops.conv_bn_eval(d, x, cu.w_fwd, gamma, beta, rm, rv, BN_EPS, residual, relu, y_out)
@@ -700,6 +732,8 @@ class SM3Engine:
         else:
             if direct:
                 (ops.stem_conv_fwd16 if isinstance(x, ops.StemImage) else ops.stem_conv_fwd)(self.dtype, x, cu.w_fwd, xo, None)
+            elif cu.groups > 1:
+                ops.gconv_fwd(self.dtype, x, cu.w_fwd, xo, None, N, H, W, C, cu.groups, cu.stride)
             else:
                 ops.conv_gemm(d, x, cu.w_fwd, xo, None, None)
             ops.bn_eval_scale_shift(gamma, beta, rm, rv, BN_EPS, C, scale, shift)
@@ -1103,6 +1137,22 @@ class SM3Engine:
         """Weight gradient on the lane's side stream: nothing on the critical path (data gradient -> BN backward ->
         ...) depends on it, so it overlaps with those HBM-bound kernels and fills their tails."""
         side = self._side_stream()
+        if cu.groups > 1:
+            gw = self._g(cu.name + ".weight")
+            n = gw.numel()
+            cap = ops.wgrad_det_cap(n)
+            if side is None:
+                ops.gconv_wgrad_det(self.dtype, r.x_in, dxo, gw, self._work("wgrad_slabs", cap * n), cap, r.N, r.H, r.W, cu.Co,
+                                    cu.groups, cu.stride)
+                return
+            cur = torch.cuda.current_stream()
+            side.wait_stream(cur)
+            for t in (dxo, r.x_in):
+                t.record_stream(side)
+            with torch.cuda.stream(side), ops.stream_scope():
+                ops.gconv_wgrad_det(self.dtype, r.x_in, dxo, gw, self._work("wgrad_slabs_side", cap * n), cap, r.N, r.H, r.W,
+                                    cu.Co, cu.groups, cu.stride)
+            return
         desc = cu.wgrad_desc(self.dtype, r.N, r.H, r.W)
         gw = self._g(cu.name + ".weight")
         if side is None:
@@ -1154,6 +1204,14 @@ class SM3Engine:
         self._wgrad(cu, r, dxo)
         if not need_dx:
             return None, None
+        if cu.groups > 1:
+            # grouped 3x3 (ResNeXt conv2): one data-gradient launch, stride 1 or 2; no fused BatchNorm-backward epilogue --
+            # the caller's bn_backward runs its phase 1 (fused_rows None)
+            if addend is not None or addend_sparse is not None or into is not None:
+                raise NotImplementedError("grouped convolutions take no data-gradient addend")
+            dx = torch.empty(r.N * r.H * r.W, cu.Ci, dtype=self.tdt, device=dxo.device)
+            ops.gconv_dgrad(self.dtype, dxo, cu.w_dgrad, dx, r.N, r.H, r.W, cu.Co, cu.groups, cu.stride)
+            return dx, None
         descs, full = cu.dgrad_descs(self.dtype, r.N, r.H, r.W)
         if into is not None:  # accumulate into an existing gradient
             for dd in descs:
@@ -1305,7 +1363,8 @@ class SM3Engine:
             # ReLU happens on conv2's staged input image: conv1 stops after its statistics, conv2 reads conv1's RAW output
             # and writes the activation + ReLU bits that its weight gradient and bn1's backward need on the side
             bn_in = None
-            if self.bnin and train and save is not None and self.dtype != ops.SM3_F32 and blk["c2"].stride == 1:
+            if (self.bnin and train and save is not None and self.dtype != ops.SM3_F32 and blk["c2"].stride == 1
+                    and blk["c2"].groups == 1):
                 d1 = blk["c1"].fwd_desc(self.dtype, N, h, w)
                 if ops.conv3x3_bnin_ok(blk["c2"].fwd_desc(self.dtype, N, d1.Ho, d1.Wo), Vt):
                     C1 = blk["c1"].Co

@@ -554,6 +554,78 @@ def grouped_wgrad_det(x, dy, dw, groups, slabs=None):
                                                 _stream()), "sm3_grouped_wgrad_det")
 
 
+# ------------------------------------------------------------------------------------------
+# grouped 3x3 convolution (ResNeXt conv2, csrc/gconv.hip): NHWC, pad 1, G groups of C / G channels
+# ------------------------------------------------------------------------------------------
+def _gconv_chk(dtype, N, H, W, C, groups, stride):
+    if C % groups or (C // groups) not in (4, 8, 16, 32, 64) or C % 64 or stride not in (1, 2):
+        raise ValueError(f"grouped 3x3 conv: C={C}, groups={groups}, stride={stride} not supported")
+    return (H - 1) // stride + 1, (W - 1) // stride + 1
+
+
+def gconv_weight_prep(dtype, master, C, groups, w_fwd, w_dgrad, only_if=None):
+    """fp32 master [C][3][3][C/groups] (OHWI) -> `dtype` banks w_fwd / w_dgrad [9][C/groups][C] (sm3_gconv_weight_prep)."""
+    tdt = TORCH_DTYPE[dtype]
+    _chk(master, torch.float32, "master"); _chk(w_fwd, tdt, "w_fwd"); _chk(w_dgrad, tdt, "w_dgrad")
+    _chk(only_if, torch.int32, "only_if")
+    n = C * 9 * (C // groups)
+    if master.numel() != n or w_fwd.numel() != n or w_dgrad.numel() != n:
+        raise ValueError("gconv_weight_prep: size mismatch")
+    with _prof("weight_prep", 0.0, n * (4.0 + 2 * _sz(dtype))):
+        check(_lib.load().sm3_gconv_weight_prep(dtype, _ptr(master), _ptr(w_fwd), _ptr(w_dgrad), C, groups, _ptr(only_if),
+                                                _stream()), "sm3_gconv_weight_prep")
+
+
+def gconv_fwd(dtype, x, w_fwd, y, partials, N, H, W, C, groups, stride):
+    """y [N*Ho*Wo, C] = grouped 3x3 conv of x [N*H*W, C]; partials: [ceil(rows / 128)][2][C] BatchNorm sums, or None."""
+    tdt = TORCH_DTYPE[dtype]
+    Ho, Wo = _gconv_chk(dtype, N, H, W, C, groups, stride)
+    _chk(x, tdt, "x"); _chk(w_fwd, tdt, "w_fwd"); _chk(y, tdt, "y"); _chk(partials, torch.float32, "partials")
+    M = N * Ho * Wo
+    if x.numel() != N * H * W * C or y.numel() != M * C or w_fwd.numel() != 9 * C * (C // groups):
+        raise ValueError("gconv_fwd: size mismatch")
+    if partials is not None and partials.numel() < (M + 127) // 128 * 2 * C:
+        raise ValueError("gconv_fwd: partials workspace too small")
+    sz = _sz(dtype)
+    with _prof("gconv_fwd", 2.0 * M * C * 9 * (C // groups), sz * (x.numel() + y.numel() + w_fwd.numel())):
+        check(_lib.load().sm3_gconv_fwd(dtype, _ptr(x), _ptr(w_fwd), _ptr(y), _ptr(partials), N, H, W, C, groups, stride,
+                                        _stream()), "sm3_gconv_fwd")
+
+
+def gconv_dgrad(dtype, dy, w_dgrad, dx, N, H, W, C, groups, stride):
+    """dx [N*H*W, C] = data gradient of the grouped 3x3 conv from dy [N*Ho*Wo, C] (sm3_gconv_dgrad)."""
+    tdt = TORCH_DTYPE[dtype]
+    Ho, Wo = _gconv_chk(dtype, N, H, W, C, groups, stride)
+    _chk(dy, tdt, "dy"); _chk(w_dgrad, tdt, "w_dgrad"); _chk(dx, tdt, "dx")
+    if dy.numel() != N * Ho * Wo * C or dx.numel() != N * H * W * C or w_dgrad.numel() != 9 * C * (C // groups):
+        raise ValueError("gconv_dgrad: size mismatch")
+    sz = _sz(dtype)
+    with _prof("gconv_dgrad", 2.0 * N * Ho * Wo * C * 9 * (C // groups), sz * (dy.numel() + dx.numel() + w_dgrad.numel())):
+        check(_lib.load().sm3_gconv_dgrad(dtype, _ptr(dy), _ptr(w_dgrad), _ptr(dx), N, H, W, C, groups, stride, _stream()),
+              "sm3_gconv_dgrad")
+
+
+def gconv_wgrad_slabs(N, H, W, stride, cap):
+    """Slabs a grouped weight gradient over this geometry uses with `cap` slabs of room."""
+    return _lib.load().sm3_gconv_wgrad_slabs(N, H, W, stride, cap)
+
+
+def gconv_wgrad_det(dtype, x, dy, dw, slabs, cap, N, H, W, C, groups, stride):
+    """dw [C, 9*C/groups] += dy^T x of the grouped 3x3 conv, fixed-order slab sum (sm3_gconv_wgrad_det): bit-reproducible."""
+    tdt = TORCH_DTYPE[dtype]
+    Ho, Wo = _gconv_chk(dtype, N, H, W, C, groups, stride)
+    _chk(x, tdt, "x"); _chk(dy, tdt, "dy"); _chk(dw, torch.float32, "dw"); _chk(slabs, torch.float32, "slabs")
+    n = C * 9 * (C // groups)
+    if x.numel() != N * H * W * C or dy.numel() != N * Ho * Wo * C or dw.numel() != n:
+        raise ValueError("gconv_wgrad_det: size mismatch")
+    if cap < 1 or slabs.numel() < gconv_wgrad_slabs(N, H, W, stride, cap) * n:
+        raise ValueError("gconv_wgrad_det: slab buffer too small")
+    sz = _sz(dtype)
+    with _prof("gconv_wgrad", 2.0 * N * Ho * Wo * C * 9 * (C // groups), sz * (x.numel() + dy.numel()) + 4 * n):
+        check(_lib.load().sm3_gconv_wgrad_det(dtype, _ptr(x), _ptr(dy), _ptr(dw), _ptr(slabs), int(cap), N, H, W, C, groups,
+                                              stride, _stream()), "sm3_gconv_wgrad_det")
+
+
 def conv_wgrad_cat(desc, x, dy, dw, dy1=None, dw1=None, views=1):
     """P[v] = dy_v^T x_v -> dw [views][Co][Ci] (and, with dy1, G[v] = dy1_v^T x_v -> dw1 [views][Co1][Ci]) in one launch
     (sm3_conv_wgrad_cat), accumulated into fp32 buffers the caller zeroed."""

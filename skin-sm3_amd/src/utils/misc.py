@@ -92,15 +92,27 @@ def amp_dtype(args):
     return torch.float16 if args.amp_dtype == "fp16" else torch.bfloat16
 
 
-MLC_ARCHS = ("resnet50", "resnet101", "resnet152")
+MLC_ARCHS = ("resnet50", "resnet101", "resnet152", "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d")
 
 
 def require_mlc_arch(arch, tool):
     """The multi-label tools (mlc_train / mlc_eval / inference) build their heads on 2 x 2048 pooled features, i.e. on
-    Bottleneck encoders; the BasicBlock ones (resnet18/34, 512-wide) are rejected here, before any kernel runs."""
+    Bottleneck encoders (the ResNets and the ResNeXts); the BasicBlock ones (resnet18/34, 512-wide) are rejected here, before
+    any kernel runs."""
     if arch not in MLC_ARCHS:
         raise SystemExit(f"{tool}: -a {arch} is not supported: the multi-label heads are built on 2048-wide Bottleneck "
                          f"features (one of {', '.join(MLC_ARCHS)}); resnet18/34 run in backbone_train / backbone_eval")
+
+
+BASELINE_ARCHS = ("resnet18", "resnet34", "resnet50", "resnet101", "resnet152")
+
+
+def require_baseline_arch(arch, tool):
+    """The linear-probe / fine-tune model (src/models/baseline.py) is built on the plain ResNets only, as the reference's
+    Baseline; a ResNeXt is refused here, before any kernel runs."""
+    if arch not in BASELINE_ARCHS:
+        raise SystemExit(f"{tool}: -a {arch} is not supported: the evaluation model is built on the plain ResNets "
+                         f"({', '.join(BASELINE_ARCHS)}); ResNeXt encoders run in backbone_train and the multi-label tools")
 
 
 MLC_FEAT_DIM = 2 * 2048  # cat(derm, clinic) pooled features of the Bottleneck encoders the multi-label tools take

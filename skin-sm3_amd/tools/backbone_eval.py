@@ -99,7 +99,8 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train):
 def main():
     parser = get_parser()
     args = parser.parse_args()
-    from src.utils.misc import amp_dtype, describe_ignored
+    from src.utils.misc import amp_dtype, describe_ignored, require_baseline_arch
+    require_baseline_arch(args.arch, "backbone_eval")
     if describe_ignored(args, parser):
         print("accepted for compatibility, without effect in this build:", " ".join(describe_ignored(args, parser)), flush=True)
     if args.data_name != "synthetic":
