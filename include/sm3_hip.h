@@ -528,6 +528,15 @@ int sm3_check_finite(const float* g, int64_t n, int32_t* found_inf, void* stream
  * out [B,3,H,W] fp32 in [0,1]. */
 int sm3_aug_resized_crop(const uint8_t* src, int B, int Hs, int Ws, const int32_t* box, const uint8_t* flip, float* out,
                          int H, int W, void* stream);
+/* The same resample over images of DIFFERENT sizes (ABI 8 addition): the images lie HWC uint8, one after another, in
+ * `arena` (arena_bytes long, device memory); image k starts at byte offset[k] and is img_h[k] x img_w[k].  Sample b reads
+ * image index[b] (0 <= index[b] < n_images) with crop box[b] = (top, left, height, width) inside that image and flip[b];
+ * out [B,3,H,W] fp32 in [0,1].  offset / img_h / img_w / index / box / flip are HOST arrays: every box and image is checked
+ * against its own image and the arena (SM3_EINVAL) before anything is launched, and the per-sample geometry travels in the
+ * kernel arguments.  Arithmetic identical to sm3_aug_resized_crop: on an equal-sized batch the two agree bit for bit. */
+int sm3_aug_resized_crop_ragged(const uint8_t* arena, int64_t arena_bytes, const int64_t* offset, const int32_t* img_h,
+                                const int32_t* img_w, int n_images, const int32_t* index, const int32_t* box,
+                                const uint8_t* flip, int B, float* out, int H, int W, void* stream);
 /* One position of ColorJitter's randomly ordered chain, in place on img [B,3,H,W]: op[b] = 0 none, 1 brightness, 2 contrast,
  * 3 saturation, 4 hue, with factor[b] (torchvision functional_tensor: _blend / rgb_to_grayscale / _rgb2hsv / _hsv2rgb).
  * gray_mean: [B] scratch (the per-image grayscale mean the contrast blend needs, recomputed by every call). */

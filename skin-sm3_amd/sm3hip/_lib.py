@@ -142,6 +142,7 @@ SIGNATURES = {
     "sm3_ema_update": [_P, _P, _L, _F, _P],
     "sm3_check_finite": [_P, _L, _P, _P],
     "sm3_aug_resized_crop": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P],
+    "sm3_aug_resized_crop_ragged": [_P, _L, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _P],
     "sm3_aug_color_op": [_P, _I, _I, _I, _P, _P, _P, _P],
     "sm3_aug_finish": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "sm3_token_attention": [_I, _P, _P, _I, _I, _I, _I, _P],

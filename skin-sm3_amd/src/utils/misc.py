@@ -38,7 +38,7 @@ _OPTIM = [
 ]
 _OTHER = [
     (("--seed",), dict(type=int, default=3407)),
-    (("-j", "--workers"), dict(default=8, type=int, help="data-loading workers (no loader here: parsed, ignored)")),
+    (("-j", "--workers"), dict(default=8, type=int, help="image decode threads (at most 16) with a real dataset; no effect on synthetic data")),
     (("--save-freq",), dict(type=int, default=50)),
     (("--print-freq",), dict(type=int, default=50)),
     (("--amp",), dict(action="store_true", help="fp16 + dynamic loss scaling, as in the reference")),
@@ -138,3 +138,29 @@ def describe_ignored(args, parser):
         if hasattr(args, name) and getattr(args, name) != parser.get_default(name):
             out.append("--" + name.replace("_", "-"))
     return out
+
+
+DATASETS = ("synthetic", "SevenPCBaseDataset")
+
+
+def require_data(args, tool):
+    """--data-name synthetic (generated on the device) or SevenPCBaseDataset (derm7pt under --data-path, read by
+    src/utils/data/datasets.py); True for the real dataset.  Missing files are refused here, before any kernel runs."""
+    if args.data_name not in DATASETS:
+        raise SystemExit(f"{tool}: --data-name {args.data_name} is not available in this build (one of {', '.join(DATASETS)})")
+    if args.data_name == "synthetic":
+        return False
+    root = args.data_path
+    missing = [f for f in ("meta.csv", "train_indexes.csv", "valid_indexes.csv", "test_indexes.csv")
+               if not os.path.isfile(os.path.join(root, f))]
+    if not os.path.isdir(os.path.join(root, "images")):
+        missing.append("images/")
+    if missing:
+        raise SystemExit(f"{tool}: --data-path {root} is not a derm7pt directory: missing {', '.join(missing)}")
+    return True
+
+
+def ignored_line(args, parser, real_data):
+    """describe_ignored's flags, without --workers when a real dataset is read (-j then sizes the decode threads)."""
+    out = describe_ignored(args, parser)
+    return [f for f in out if f != "--workers"] if real_data else out

@@ -6,8 +6,13 @@ tools/backbone_eval.py (train :65-142, validate :145-212, checkpoint key split :
 
 `--finetune fc`: encoders frozen and in eval mode (one fused conv+BN+ReLU kernel per layer), the 8 heads trained
 with AdamW on the weighted cross-entropy sum/8; AUROC "8 avg" (sm3hip.metrics.auc_avg) on the validation pass.
-Any other value fine-tunes everything through the autograd bridge.  The derm7pt dataset is out of scope: synthetic
-images and labels (see tools/backbone_train.py).
+Any other value fine-tunes everything through the autograd bridge.
+
+`--data-name SevenPCBaseDataset --data-path DIR`: derm7pt's train and test splits decoded once into the device image store
+(sm3hip/imagestore.py); training one pass over the train split per epoch with the reference's chain (backbone_eval.py:234-262:
+RandomResizedCrop(img_sz, scale=(0.5, 1)) -> flip -> Normalize) on the GPU, validation on the test split with Resize(img_sz)
+-> Normalize and its real labels; the validation predictions of the last epoch are saved as val_predictions.pt.
+`--data-name synthetic`: random images and labels, --steps-per-epoch / --val-steps steps.
 """
 import argparse
 import os
@@ -63,14 +68,26 @@ def synthetic(bs, size, dev, gen):
     return derm, clinic, labels
 
 
-def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train):
+def real_batches(store, split, aug, batches, gen, whole):
+    """(derm, clinic, labels) of each batch of case indices: one augmented view per modality, labels from the device."""
+    for sel in batches:
+        derm = store.augment(aug, split.derm_ids[sel], gen, whole=whole)[0]
+        clinic = store.augment(aug, split.clinic_ids[sel], gen, whole=whole)[0]
+        yield derm, clinic, split.labels.index_select(0, sel.to(split.labels.device, non_blocking=True))
+
+
+def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, data=None):
     if train and args.finetune != "fc":
         evaluator.train()
     else:
         evaluator.eval()
     all_preds, all_targets, total, t0 = [], [], 0.0, time.time()
-    for it in range(steps):
-        derm, clinic, labels = synthetic(args.batch_size, args.img_sz, dev, gen)
+    if data is None:
+        data = (synthetic(args.batch_size, args.img_sz, dev, gen) for _ in range(steps))
+    steps, pairs = 0, 0
+    for derm, clinic, labels in data:
+        steps += 1
+        pairs += labels.shape[0]
         with torch.set_grad_enabled(train):
             outputs = evaluator([derm, clinic])
             loss = sum(args.label_weights[i] * criterion(outputs[i], labels[:, i]) for i in range(args.num_labels))
@@ -92,19 +109,19 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train):
     per, avg = auc_avg(preds, torch.cat(all_targets))
     stat = {f"AUC_{n}": float(v) for n, v in zip(CLASSES_NAME, per)}
     stat.update({"AUC_AVG": float(avg), "loss": total / steps,
-                 "pairs_per_s": steps * args.batch_size / (time.time() - t0)})
+                 "pairs_per_s": pairs / (time.time() - t0)})
+    stat["preds"], stat["targets"] = preds, torch.cat(all_targets)
     return stat
 
 
-def main():
+def main(argv=None):
     parser = get_parser()
-    args = parser.parse_args()
-    from src.utils.misc import amp_dtype, describe_ignored, require_baseline_arch
+    args = parser.parse_args(argv)
+    from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
     require_baseline_arch(args.arch, "backbone_eval")
-    if describe_ignored(args, parser):
-        print("accepted for compatibility, without effect in this build:", " ".join(describe_ignored(args, parser)), flush=True)
-    if args.data_name != "synthetic":
-        raise SystemExit("only --data-name synthetic is available in this build (dataset pipeline is out of scope)")
+    real = require_data(args, "backbone_eval")
+    if ignored_line(args, parser, real):
+        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", 0)
     evaluator = Baseline(args.arch, args.arch_weights)
@@ -121,17 +138,34 @@ def main():
     optimizer = torch.optim.AdamW(params, lr=args.base_lr, weight_decay=args.wd)
     criterion = nn.CrossEntropyLoss()
     gen = torch.Generator(device=dev).manual_seed(args.seed)
-    best = -1.0
+    train_data = val_data = lambda epoch: None
+    if real:
+        from sm3hip.augment import chain
+        from sm3hip.imagestore import build_for
+        from src.utils.data.sampler import eval_batches, train_batches
+        store = build_for(args, ["train", "test"], dev)
+        tsplit, vsplit = store.splits["train"], store.splits["test"]
+        aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
+        aug_gen = torch.Generator().manual_seed(args.seed + 1000)
+        train_data = lambda epoch: real_batches(store, tsplit, aug, train_batches(len(tsplit), 1, 0, epoch, args.batch_size),
+                                                aug_gen, False)
+        val_data = lambda epoch: real_batches(store, vsplit, aug, eval_batches(len(vsplit), args.batch_size), None, True)
+    best, history = -1.0, []
     os.makedirs(args.log_path, exist_ok=True)
     for epoch in range(args.epochs):
-        tr = run_epoch(args, evaluator, criterion, optimizer, args.steps_per_epoch, gen, dev, True)
-        va = run_epoch(args, evaluator, criterion, None, args.val_steps, gen, dev, False)
+        tr = run_epoch(args, evaluator, criterion, optimizer, args.steps_per_epoch, gen, dev, True, train_data(epoch))
+        va = run_epoch(args, evaluator, criterion, None, args.val_steps, gen, dev, False, val_data(epoch))
+        history.append((tr, va))
+        if real:
+            torch.save({"epoch": epoch + 1, "preds": [p.cpu() for p in va["preds"]], "targets": va["targets"].cpu(),
+                        "AUC_AVG": va["AUC_AVG"]}, os.path.join(args.log_path, "val_predictions.pt"))
         print(f"epoch {epoch}: train loss {tr['loss']:.4f} AUC_AVG {tr['AUC_AVG']:.4f} {tr['pairs_per_s']:.0f} pairs/s | "
               f"val loss {va['loss']:.4f} AUC_AVG {va['AUC_AVG']:.4f} {va['pairs_per_s']:.0f} pairs/s", flush=True)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG (backbone_eval.py:386,405-411)
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},
                        os.path.join(args.log_path, "best_linear.pth"))
+    return history
 
 
 if __name__ == "__main__":

@@ -5,8 +5,14 @@ recipe of run.sh:3-12 uses; one process per GPU; same checkpoint wire format, ba
     python tools/backbone_train.py --data-name synthetic --data-path - -a resnet50 --arch-version v32 \
         -b 512 -lr 1e-6 --temperature 0.1 --proj-dim 128 --epochs 1 --steps-per-epoch 20
 
-Differences, stated: the derm7pt dataset and its PIL augmentation pipeline are host-side and out of scope
-(SURVEY.md 2.1 #9-10), so `--data-name synthetic` generates normalised image pairs on the device; `--engine fused`
+    python tools/backbone_train.py --data-name SevenPCBaseDataset --data-path ./data/7PC -a resnet50 --arch-version v32 \
+        -b 96 -lr 1e-6 --temperature 0.1 --img-sz 224 224 -j 8 --epochs 400 --amp
+
+`--data-name SevenPCBaseDataset` reads derm7pt from --data-path (src/utils/data/datasets.py), decodes every training image
+once into the device image store (sm3hip/imagestore.py, -j decode threads) and runs the reference's SimCLR chain with two
+views per modality on the GPU (sm3hip/augment.py); an epoch is one pass over the train split in DistributedSampler order
+(src/utils/data/sampler.py), the last, partial batch included.  `--data-name synthetic` generates normalised image pairs
+on the device (an epoch is --steps-per-epoch steps); `--engine fused`
 (default) runs the fused step of sm3hip.trainer.SM3Trainer, `--engine compat` runs the reference's literal loop
 (model(...) -> CrossEntropyLoss -> backward -> torch.optim.AdamW, backbone_train.py:98-127) on the same kernels.
 `--amp` means what the reference's means (fp16 autocast + GradScaler, backbone_train.py:27,98,125-127,480): fp16 storage
@@ -87,6 +93,8 @@ def synthetic_batch(bs, size, device, gen, kind="noise"):
 
 
 def main(local_rank, args):
+    from src.utils.misc import require_data
+    real = require_data(args, "backbone_train")
     world = args.world_size
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
@@ -94,8 +102,6 @@ def main(local_rank, args):
         dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{args.port}", world_size=world, rank=local_rank)
     torch.manual_seed(args.seed)
     bs = args.batch_size // world  # src/utils/misc.py:400
-    if args.data_name != "synthetic":
-        raise SystemExit("only --data-name synthetic is available in this build (dataset pipeline is out of scope)")
     cls = SimCLRSkinV3 if args.arch_version in ("v3", "v311", "v312") else SimCLRSkinV32
     model = cls(arch=args.arch, weights=args.arch_weights, proj_dim=args.proj_dim, temperature=args.temperature,
                 use_checkpoint=args.use_checkpoint)
@@ -131,19 +137,33 @@ def main(local_rank, args):
                 scaler.load_state_dict(ckpt["scaler"])
 
     gen = torch.Generator(device=dev).manual_seed(args.seed + local_rank)
-    augment = None
-    if args.gpu_augment:
+    augment = store = None
+    if real:
+        # derm7pt: decoded once into the device store; the reference's SimCLR chain (backbone_train.py:447-470), two views
+        from sm3hip.augment import chain
+        from sm3hip.imagestore import build_for
+        from src.utils.data.sampler import train_batches
+        store = build_for(args, ["train"], dev)
+        train = store.splits["train"]
+        augment = chain("backbone_train", tuple(args.img_sz), args.mean, args.std)
+        aug_gen = torch.Generator().manual_seed(args.seed + 1000 + local_rank)
+    elif args.gpu_augment:
         # the reference's transform chain (backbone_train.py:448-466) on the GPU: decoded uint8 source images in HBM ->
         # two augmented, normalised views per modality (sm3hip/augment.py, csrc/augment.hip)
         from sm3hip.augment import SimCLRAugment
         augment = SimCLRAugment(tuple(args.img_sz), args.mean, args.std)
         aug_gen = torch.Generator().manual_seed(args.seed + 1000 + local_rank)
     os.makedirs(args.log_path, exist_ok=True)
+    history = []
     for epoch in range(start_epoch, args.epochs):
         model.train()
         t0, seen, running = time.time(), 0, None
-        for it in range(args.steps_per_epoch):
-            if augment is not None:
+        batches = train_batches(len(train), world, local_rank, epoch, bs) if real else [None] * args.steps_per_epoch
+        for it, sel in enumerate(batches):
+            if real:
+                derm = store.augment(augment, train.derm_ids[sel], aug_gen, n_views=2)
+                clinic = store.augment(augment, train.clinic_ids[sel], aug_gen, n_views=2)
+            elif augment is not None:
                 src_hw = (2 * args.img_sz[0] + 14, 3 * args.img_sz[1] + 46)  # ~ derm7pt's 462 x 718 at 224
                 d_src = torch.randint(0, 256, (bs,) + src_hw + (3,), device=dev, generator=gen, dtype=torch.uint8)
                 c_src = torch.randint(0, 256, (bs,) + src_hw + (3,), device=dev, generator=gen, dtype=torch.uint8)
@@ -160,12 +180,13 @@ def main(local_rank, args):
                 scaler.scale(loss).backward()  # backbone_train.py:125-127 (identity when not fp16)
                 scaler.step(optimizer)
                 scaler.update()
-            seen += bs * world
+            seen += (len(sel) if real else bs) * world
             if local_rank == 0 and it % args.print_freq == 0:
                 running = float(loss)  # the only host sync, every print_freq steps
                 dt = time.time() - t0
-                print(f"Train epoch: [{epoch}][{it}/{args.steps_per_epoch}] Loss {running:.4f} "
+                print(f"Train epoch: [{epoch}][{it}/{len(batches)}] Loss {running:.4f} "
                       f"{seen / max(dt, 1e-9):.1f} pairs/s", flush=True)
+        history.append(float(loss.detach()))  # the epoch's last loss (one host sync per epoch)
         if local_rank == 0:
             state = {"epoch": epoch + 1, "state_dict": model.state_dict(),
                      "optimizer": trainer.optimizer_state_dict() if args.engine == "fused" else optimizer.state_dict(),
@@ -176,14 +197,16 @@ def main(local_rank, args):
                 torch.save(state, os.path.join(args.log_path, f"ckp_{epoch + 1}.pth"))
     if world > 1:
         dist.destroy_process_group()
+    return history
 
 
 if __name__ == "__main__":
     parser = get_parser()
     args = parser.parse_args()
-    from src.utils.misc import describe_ignored
-    if describe_ignored(args, parser):
-        print("accepted for compatibility, without effect in this build:", " ".join(describe_ignored(args, parser)), flush=True)
+    from src.utils.misc import ignored_line, require_data
+    real = require_data(args, "backbone_train")  # unknown data names and missing files: before any kernel runs
+    if ignored_line(args, parser, real):
+        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
     args.world_size = int(os.environ.get("SM3_WORLD_SIZE", torch.cuda.device_count()))
     try:
         if args.world_size > 1:

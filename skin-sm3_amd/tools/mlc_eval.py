@@ -9,7 +9,13 @@ trains with the weighted cross-entropy sum / 8 against the real labels, reports 
 
 --finetune fc: extractor and label projectors frozen; projector: extractor frozen; all: encoder stages layer1-4 of both
 backbones trainable as well (stem frozen), gradient flowing into the HIP encoders through the autograd bridge.  The heads
-train on sm3hip/mlc.py in every mode.  The derm7pt dataset is out of scope: synthetic images and labels.
+train on sm3hip/mlc.py in every mode.
+
+`--data-name SevenPCBaseDataset --data-path DIR`: derm7pt's train and test splits decoded once into the device image store
+(sm3hip/imagestore.py); training one pass over the train split per epoch with the reference's chain (mlc_eval.py:294-322:
+RandomResizedCrop(train_sz, scale=(0.3, 1)) -> flip -> Normalize) on the GPU, validation on the test split with
+Resize(test_sz) -> Normalize and its real labels.  `--data-name synthetic`: random images and labels at --img-sz,
+--steps-per-epoch / --val-steps steps.
 
 --mlc-proj picks the label projectors as the reference does (default v4): v0 nn.Identity (--mlc-proj-dim must be 4096), v1 / v2 / v3 the per-label BN-MLPs of src/models/projector.py, v4 one biased Linear per label; unknown kinds are refused before anything runs."""
 import argparse
@@ -103,14 +109,18 @@ def set_train_modes(evaluator, finetune):
         evaluator.mlc_sa.eval()
 
 
-def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train):
+def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, data=None):
     if train:  # the reference's mode matrix, tools/mlc_eval.py:124-138
         set_train_modes(evaluator, args.finetune)
     else:
         evaluator.eval()
     preds_all, targets_all, total, t0 = [], [], 0.0, time.time()
-    for _ in range(steps):
-        derm, clinic, labels = synthetic(args.batch_size, args.img_sz, dev, gen)
+    if data is None:
+        data = (synthetic(args.batch_size, args.img_sz, dev, gen) for _ in range(steps))
+    steps, pairs = 0, 0
+    for derm, clinic, labels in data:
+        steps += 1
+        pairs += labels.shape[0]
         with torch.set_grad_enabled(train):
             outputs = evaluator(derm, clinic)
             loss = sum(args.label_weights[i] * criterion(outputs[i], labels[:, i]) for i in range(args.num_labels))
@@ -131,18 +141,19 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train):
     preds = [torch.cat([p[i] for p in preds_all]) for i in range(args.num_labels)]
     per, avg = auc_avg(preds, torch.cat(targets_all))
     stat = {f"AUC_{n}": float(v) for n, v in zip(CLASSES_NAME, per)}
-    stat.update({"AUC_AVG": float(avg), "loss": total / steps, "pairs_per_s": steps * args.batch_size / (time.time() - t0)})
+    stat.update({"AUC_AVG": float(avg), "loss": total / steps, "pairs_per_s": pairs / (time.time() - t0)})
     return stat
 
 
 def main(argv=None):
-    args = get_parser().parse_args(argv)
-    from src.utils.misc import require_mlc_arch
-    from src.utils.misc import require_mlc_proj
+    parser = get_parser()
+    args = parser.parse_args(argv)
+    from src.utils.misc import ignored_line, require_data, require_mlc_arch, require_mlc_proj
     require_mlc_arch(args.arch, "mlc_eval")
     require_mlc_proj(args, "mlc_eval")
-    if args.data_name != "synthetic":
-        raise SystemExit("only --data-name synthetic is available in this build (dataset pipeline is out of scope)")
+    real = require_data(args, "mlc_eval")
+    if real and ignored_line(args, parser, real):
+        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", 0)
     extractor = SimCLRSkinV32(arch=args.arch, proj_dim=args.extractor_proj_dim)
@@ -175,11 +186,30 @@ def main(argv=None):
     optimizer = torch.optim.AdamW(params, lr=args.base_lr, weight_decay=args.wd)
     criterion = nn.CrossEntropyLoss()
     gen = torch.Generator(device=dev).manual_seed(args.seed)
+    train_data = val_data = lambda epoch: None
+    if real:
+        from sm3hip.augment import chain
+        from sm3hip.imagestore import build_for
+        from src.utils.data.sampler import eval_batches, train_batches
+        store = build_for(args, ["train", "test"], dev)
+        tsplit, vsplit = store.splits["train"], store.splits["test"]
+        taug = chain("mlc_eval", (args.train_sz, args.train_sz), args.mean, args.std)
+        vaug = chain("mlc_eval", (args.test_sz, args.test_sz), args.mean, args.std)
+        aug_gen = torch.Generator().manual_seed(args.seed + 1000)
+
+        def batches(split, aug, order, g, whole):
+            for sel in order:
+                derm = store.augment(aug, split.derm_ids[sel], g, whole=whole)[0]
+                clinic = store.augment(aug, split.clinic_ids[sel], g, whole=whole)[0]
+                yield derm, clinic, split.labels.index_select(0, sel.to(dev, non_blocking=True))
+        train_data = lambda epoch: batches(tsplit, taug, train_batches(len(tsplit), 1, 0, epoch, args.batch_size), aug_gen,
+                                           False)
+        val_data = lambda epoch: batches(vsplit, vaug, eval_batches(len(vsplit), args.batch_size), None, True)
     os.makedirs(args.log_path, exist_ok=True)
     best, history = -1.0, []
     for epoch in range(args.epochs):
-        tr = run_epoch(args, evaluator, criterion, optimizer, args.steps_per_epoch, gen, dev, True)
-        va = run_epoch(args, evaluator, criterion, None, args.val_steps, gen, dev, False)
+        tr = run_epoch(args, evaluator, criterion, optimizer, args.steps_per_epoch, gen, dev, True, train_data(epoch))
+        va = run_epoch(args, evaluator, criterion, None, args.val_steps, gen, dev, False, val_data(epoch))
         history.append((tr, va))
         print(f"epoch {epoch}: train loss {tr['loss']:.4f} AUC_AVG {tr['AUC_AVG']:.4f} {tr['pairs_per_s']:.0f} pairs/s | "
               f"val loss {va['loss']:.4f} AUC_AVG {va['AUC_AVG']:.4f}", flush=True)

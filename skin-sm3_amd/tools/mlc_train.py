@@ -10,8 +10,12 @@ Everything arithmetic runs on the HIP kernels: the two ResNet-50 encoders throug
 fused conv + BN + ReLU kernels when frozen; train mode with autograd through sm3hip.bridge under --finetune-backbone),
 the heads and their training through sm3hip/mlc.py, the k-means through csrc/heads_train.hip.  The loop is the
 reference's own (nn.CrossEntropyLoss on the predictions / temperature, torch.optim.AdamW on the trainable parameters).
-Differences, stated: the derm7pt dataset and its PIL pipeline are out of scope, `--data-name synthetic` generates a fixed
-set of learnable image pairs on the device; data parallelism gathers the memory bank with torch.distributed as the
+`--data-name SevenPCBaseDataset --data-path DIR` reads derm7pt's train split (return_index=True, as mlc_train.py:309-330),
+decodes it once into the device image store (sm3hip/imagestore.py) and runs the reference's chain on the GPU
+(RandomResizedCrop(img_sz, (0.5, 1)) -> RandomApply(ColorJitter(.8, .8, .8, .2), p=0.5) -> flip -> Normalize, one view); an
+epoch is one pass over the split in DistributedSampler order, the memory bank is filled by dataset index and clustered over
+the split.  `--data-name synthetic` generates a fixed set of --num-samples learnable image pairs on the device instead.
+Data parallelism gathers the memory bank with torch.distributed as the
 reference does (:136-143,185-186).
 
 --mlc-proj picks the label projectors as the reference does (default v4): v0 nn.Identity (--mlc-proj-dim must be 4096), v1 / v2 / v3 the per-label BN-MLPs of src/models/projector.py, v4 one biased Linear per label; unknown kinds are refused before anything runs."""
@@ -72,7 +76,8 @@ def get_parser():
     p.add_argument("--l2-norm", action="store_true")
     p.add_argument("--finetune-backbone", action="store_true")
     # this build
-    p.add_argument("--num-samples", type=int, default=413, help="size of the synthetic training split (derm7pt: 413)")
+    p.add_argument("--num-samples", type=int, default=413, help="size of the synthetic training split (derm7pt: 413); "
+                   "synthetic data only")
     p.set_defaults(arch="resnet50", batch_size=256, base_lr=1e-4, epochs=150, print_freq=10, log_path="./logs/mlc_train",
                    port=29512)
     return p
@@ -141,6 +146,8 @@ def main(local_rank, args):
     from src.utils.misc import require_mlc_proj
     require_mlc_arch(args.arch, "mlc_train")
     require_mlc_proj(args, "mlc_train")
+    from src.utils.misc import require_data
+    real = require_data(args, "mlc_train")
     world = args.world_size
     args.rank = local_rank
     # test knobs, as in bench.py (a 2-rank rehearsal on a one-GPU box: both ranks on device 0 over gloo)
@@ -151,8 +158,6 @@ def main(local_rank, args):
         dist.init_process_group(os.environ.get("SM3_DIST_BACKEND", "nccl"), init_method=f"tcp://127.0.0.1:{args.port}",
                                 world_size=world, rank=local_rank)
     torch.manual_seed(args.seed)
-    if args.data_name != "synthetic":
-        raise SystemExit("only --data-name synthetic is available in this build (dataset pipeline is out of scope)")
     bs = args.batch_size // world
 
     extractor = SimCLRSkinV32(arch=args.arch, proj_dim=args.extractor_proj_dim)
@@ -174,16 +179,33 @@ def main(local_rank, args):
     optimizer = torch.optim.AdamW(parameters, lr=args.base_lr, weight_decay=args.wd)
     criterion = nn.CrossEntropyLoss(ignore_index=-100)
 
-    n_local = args.num_samples // world
-    derm_all, clinic_all = synthetic_split(n_local, args.img_sz, dev, args.seed + local_rank)
-    index_all = torch.arange(local_rank * n_local, (local_rank + 1) * n_local, device=dev)
-    n_batches = n_local // bs  # drop_last, as the reference's train loader
+    if real:
+        from sm3hip.augment import chain
+        from sm3hip.imagestore import build_for
+        from src.utils.data.sampler import train_batches
+        store = build_for(args, ["train"], dev, return_index=True)
+        split = store.splits["train"]
+        aug = chain("mlc_train", tuple(args.img_sz), args.mean, args.std)
+        aug_gen = torch.Generator().manual_seed(args.seed + 1000 + local_rank)
+        n_batches = len(train_batches(len(split), world, local_rank, 0, bs))
 
-    def loader(perm=None):
-        order = perm if perm is not None else torch.arange(n_local, device=dev)
-        for i in range(n_batches):
-            sel = order[i * bs:(i + 1) * bs]
-            yield index_all[sel], derm_all[sel], clinic_all[sel]
+        def loader(epoch=0):
+            """the DistributedSampler order of `epoch` (the memory pass: epoch 0), every batch, the partial last one too"""
+            for sel in train_batches(len(split), world, local_rank, epoch, bs):
+                derm = store.augment(aug, split.derm_ids[sel], aug_gen)[0]
+                clinic = store.augment(aug, split.clinic_ids[sel], aug_gen)[0]
+                yield sel.to(dev, non_blocking=True), derm, clinic
+    else:
+        n_local = args.num_samples // world
+        derm_all, clinic_all = synthetic_split(n_local, args.img_sz, dev, args.seed + local_rank)
+        index_all = torch.arange(local_rank * n_local, (local_rank + 1) * n_local, device=dev)
+        n_batches = n_local // bs  # drop_last, as the reference's train loader
+
+        def loader(perm=None):
+            order = perm if perm is not None else torch.arange(n_local, device=dev)
+            for i in range(n_batches):
+                sel = order[i * bs:(i + 1) * bs]
+                yield index_all[sel], derm_all[sel], clinic_all[sel]
 
     model.eval() if not args.finetune_backbone else model.train()
     local_memory_index, local_memory_embeddings = init_memory(loader, model)
@@ -205,9 +227,9 @@ def main(local_rank, args):
             model.projectors.train()
             model.mlc_sa.train()
             model.prototypes.train()
-        perm = torch.randperm(n_local, device=dev)
+        batches = loader(epoch) if real else loader(torch.randperm(n_local, device=dev))
         start_idx, total, seen = 0, 0.0, 0
-        for it, (idx, derm, clinic) in enumerate(loader(perm)):
+        for it, (idx, derm, clinic) in enumerate(batches):
             proj_feats, preds = wrapped(derm, clinic)
             loss = 0
             for pred, assignment in zip(preds, all_assignments):
@@ -243,9 +265,10 @@ def main(local_rank, args):
 if __name__ == "__main__":
     parser = get_parser()
     args = parser.parse_args()
-    from src.utils.misc import describe_ignored
-    if describe_ignored(args, parser):
-        print("accepted for compatibility, without effect in this build:", " ".join(describe_ignored(args, parser)), flush=True)
+    from src.utils.misc import ignored_line, require_data
+    real = require_data(args, "mlc_train")  # unknown data names and missing files: before any kernel runs
+    if ignored_line(args, parser, real):
+        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
     args.world_size = int(os.environ.get("SM3_WORLD_SIZE", torch.cuda.device_count()))
     try:
         if args.world_size > 1:
