@@ -41,7 +41,7 @@ int sm3_abi_version(void);
  * Gather-GEMM convolution: forward conv, data-gradient of a conv, and bias-free Linear.
  *   replaces nn.Conv2d forward/backward-data  (src/models/resnet.py:49-67 conv3x3/conv1x1, used at
  *   :144-148,:260; the 7x7 stem :208-210 runs on sm3_stem_conv_fwd straight from the images in all three arithmetic
- *   modes -- sm3_stem_im2col + this GEMM remain as the SM3_DIRECT_STEM=0 A/B path) and nn.Linear(bias=False)
+ *   modes) and nn.Linear(bias=False)
  *   (src/models/simclr.py:17-27).
  *
  *   y[n, oy*osy+ooy, ox*osx+oox, co] = sum_t sum_ci x[n, oy*sy+dy[t], ox*sx+dx[t], ci]
@@ -153,7 +153,7 @@ int sm3_conv_bn_eval(const sm3_conv_desc* d, const void* x, const void* w, const
  *   dw[co*w_row_stride + wtap[t]*Ci + ci] += sum_{n,oy,ox} dy[(n,oy,ox), co] * x[n, oy*sy+dy[t], ox*sx+dx[t], ci]
  * dy is dense [N*Ho*Wo, Co]; dw is fp32 and is accumulated into (float atomics, split over pixels: run-to-run
  * differences of 1 ulp; sm3_conv_wgrad_det below is the fixed-order form).
- * Columns wtap[t]*Ci+ci >= w_row_stride are dropped (the zero-padded K tail of the stem im2col). */
+ * Columns wtap[t]*Ci+ci >= w_row_stride are dropped (a zero-padded K tail). */
 int sm3_conv_wgrad(const sm3_conv_desc* d, const void* x, const void* dy, float* dw, void* stream);
 /* The same product over `views` equal pixel ranges that accumulate into dw + v * dw_view_stride (per-view weight-gradient
  * products: P_v = dz_v^T x_v, or with dy = x the Gram matrix G_v = x_v^T x_v), and optionally with dY the channel
@@ -205,16 +205,6 @@ int sm3_bn_finalize(const double* sums, int groups /* sums is [views][groups][2C
                     float eps, float momentum, float* running_mean, float* running_var,
                     int64_t* num_batches_tracked /* += views */, float* scale, float* shift, float* save_mean,
                     float* save_invstd /* all four [views][C]; running statistics updated view by view */, void* stream);
-/* sm3_bn_stats_reduce (stage A) + sm3_bn_finalize in ONE launch, for a single rank (no exchange between the two): replaces
- * the same nn.BatchNorm2d / BatchNorm1d train-mode statistics (src/models/resnet.py:145-149, src/models/simclr.py:20-26) with one
- * dependent launch fewer per BatchNorm.  The block that draws the last arrival ticket of a 32-channel block finalizes it: same
- * association, same bits as the two-launch form.  workspace: views * SM3_BN_REDUCE_GROUPS * 2C doubles; tickets: (C + 31) / 32
- * uint32, ZERO before the first use and left zero by every launch; both private to the stream (launches on one stream reuse them
- * in order). */
-int sm3_bn_stats_finalize(const float* partials, int rows, int C, int views, double* workspace, uint32_t* tickets, double count,
-                          const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                          float* running_var, int64_t* num_batches_tracked, float* scale, float* shift, float* save_mean,
-                          float* save_invstd, void* stream);
 /* eval mode: scale/shift from the running statistics */
 int sm3_bn_eval_scale_shift(const float* gamma, const float* beta, const float* running_mean,
                             const float* running_var, float eps, int C, float* scale, float* shift,
@@ -338,9 +328,6 @@ int sm3_linbn_banks_post(int dtype, const void* w_dgrad, const float* coef, void
 /* ------------------------------------------------------------------------------------------
  * Stem, pooling.  replaces resnet.py:208-213,224,294-305.
  * ------------------------------------------------------------------------------------------ */
-/* 7x7/2 pad-3 im2col of an NCHW fp32 image batch into rows [N*Ho*Wo, Kpad] of dtype,
- * k = (kh*7+kw)*3 + c for k < 147, zero for 147 <= k < Kpad. */
-int sm3_stem_im2col(int dtype, const float* x_nchw, void* cols, int N, int H, int W, int Kpad, void* stream);
 /* Direct stem (bf16 / fp16 on the 16-bit MFMA; SM3_F32 on v_mfma_f32_32x32x2_f32, fp32 patch fragments and filter bank):
  * the 7x7/2 pad-3 convolution straight from the NCHW fp32 images, no im2col matrix in HBM.
  *   w_stem: dtype [64][176] from sm3_stem_weight_prep (K order (kh, c, kw padded to 8); master is [64][kh][kw][c]);
@@ -427,19 +414,6 @@ int sm3_weight_prep_batch_if(int dtype, const sm3_wprep_item* items_device, int 
 /* elementwise cast fp32 -> dtype */
 int sm3_cast_from_f32(int dtype, const float* src, void* dst, int64_t n, void* stream);
 int sm3_cast_to_f32(int dtype, const void* src, float* dst, int64_t n, void* stream);
-
-/* conv2 of a Bottleneck reading conv1's RAW output (resnet.py:144-150: conv1 -> bn1 -> relu -> conv2): ONE launch computes
- *   act = relu(x_raw * in_scale[v] + in_shift[v])  (bn1's train-mode apply + ReLU, the arithmetic of sm3_bn_act),
- *   y = conv3x3(act) + BatchNorm partial sums of y (as sm3_conv_gather_gemm),
- * writing act (same layout as x_raw) and its ReLU bits (1 byte per 16-byte vector, as sm3_bn_act's mask) on the side: the
- * affine runs on the halo-resident A image in LDS, so bn1's separate apply pass (one read of x_raw, one launch) disappears.
- * Bit-identical to sm3_bn_act followed by sm3_conv_gather_gemm.  Only for launches the halo-resident kernel takes --
- * stride-1 full 3 x 3, 16-bit, more than 256 workgroups, the A image within a quarter of a CU's LDS:
- * sm3_conv3x3_bnin_ok(d, views) == 1; anything else returns SM3_EINVAL and the caller keeps the two-pass form.
- * in_scale / in_shift: [views][Ci]; views = 2: two views back to back, each a multiple of 128 rows. */
-int sm3_conv3x3_bnin_ok(const sm3_conv_desc* d, int views);
-int sm3_conv3x3_bnin(const sm3_conv_desc* d, const void* x_raw, const float* in_scale, const float* in_shift, int views,
-                     void* act_out, uint8_t* mask_out, const void* w, void* y, float* stat_partials, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * NT-Xent.  replaces F.normalize + matmul + mask/select + /T (simclr.py:62-88, 294-320) and

@@ -84,27 +84,21 @@ struct StampRec {
 //              tap falls outside the image read the zero row); only the B tile is staged per K-step.  18 - 22 KB of A per
 //              nine K-steps instead of 144: these launches drew ~15 TB/s through L2 -> LDS, 85 % of what LDS-DMA delivers
 //              from L2 (MI355X_MICROARCH.md, "Indexed rows: gather into LDS").  K order: chunk outer, tap inner.
-//   kVarHaloBn (with kVarHalo, plain epilogue): the A tensor is the RAW output of the producer convolution; every thread
-//              applies the producer's BatchNorm affine + ReLU to the LDS-DMA pieces IT staged (after its own vmcnt wait,
-//              before the barrier that publishes the image: no extra barrier), in the arithmetic of bn_act_kernel, and
-//              writes the activation and its ReLU bits for the tile's own 128 rows -- the producer's separate apply pass
-//              (one read of that tensor and one launch per Bottleneck) disappears (forward half).
 // (bits 1 and 8 were the loader / consumer split and the 16 x 16 x 32 MFMA shape of round 4: measured slower two rounds
 // running and removed in round 6 -- profiles/r04a_split_ab_*.txt, r04a_mfma_16x16x32_ab_single_lane.txt, scratch/r6_pruned_variants.patch)
 //   kVarGrp    grouped 1x1 launches (sm3_grouped_gemm, exact-f32 general epilogue): workgroup row blockIdx.y is group g, whose
 //              operands and outputs sit at the byte offsets g * g_{x,w,y}_bytes; everything inside a group -- tiles, K order,
 //              epilogue -- is the single-group launch's, so a grouped launch equals G separate launches bit for bit.
-constexpr int kVarPw = 2, kVarNoX = 4, kVarHalo = 16, kVarHaloBn = 32, kVarGrp = 64;
+constexpr int kVarPw = 2, kVarNoX = 4, kVarHalo = 16, kVarGrp = 64;
 template <typename T, int BM, int BN, int WM, int WN, int STAGES, int EPI, bool SEG = false, int VAR = 0>
 // registers: the 1-stage kernels (34 KB of LDS) run 4 workgroups per CU = 4 waves per SIMD, so their epilogues must fit 128
 // registers; the 2- and 4-stage kernels are limited to 2 / 1 workgroups per CU by their LDS and may use 256
 __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) void conv_igemm_kernel(const ConvParams p) {
     static_assert(STAGES == 1 || STAGES == 4, "one-stage loop, or the 4-stage ring of the small-grid launches");
     constexpr bool PW = (VAR & kVarPw) != 0, NOX = (VAR & kVarNoX) != 0;
-    constexpr bool HALO = (VAR & kVarHalo) != 0, HALOBN = (VAR & kVarHaloBn) != 0;
+    constexpr bool HALO = (VAR & kVarHalo) != 0;
     constexpr bool GRP = (VAR & kVarGrp) != 0;
     static_assert(!GRP || (EPI == 0 && !SEG && VAR == kVarGrp), "kVarGrp: the general epilogue, one K segment");
-    static_assert(!HALOBN || (HALO && EPI == 1), "kVarHaloBn: the plain forward epilogue of the halo kernel");
     static_assert(!HALO || (EPI >= 1 && STAGES == 1 && !SEG && !(VAR & kVarPw) && sizeof(T) == 2 && WM * WN == 4),
                   "kVarHalo: 16-bit lean one-stage kernels, 4 waves");
     static_assert(!NOX || EPI == 3, "kVarNoX: the fused BN-backward epilogue");
@@ -364,17 +358,6 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
                 const unsigned long long q1 = SM3_STAMP_NOW();
 #endif
                 if (tt == 0) halo_issue((uint32_t)c * 128u);
-                // kVarHaloBn: the producer's scale / shift of this lane's 8 channels of the chunk, requested before the wait
-                float4 bsc0 = make_float4(0.f, 0.f, 0.f, 0.f), bsc1 = bsc0, bsh0 = bsc0, bsh1 = bsc0;
-                if constexpr (HALOBN) {
-                    if (tt == 0) {
-                        const int ch0 = tile_view * p.Ci + c * (128 / SZ) + (int)(a_chunk >> 4) * (16 / SZ);
-                        bsc0 = *reinterpret_cast<const float4*>(p.in_scale + ch0);
-                        bsc1 = *reinterpret_cast<const float4*>(p.in_scale + ch0 + 4);
-                        bsh0 = *reinterpret_cast<const float4*>(p.in_shift + ch0);
-                        bsh1 = *reinterpret_cast<const float4*>(p.in_shift + ch0 + 4);
-                    }
-                }
                 const uint32_t soff_b = (uint32_t)p.wtap[tt] * row_bytes + (uint32_t)c * 128u;
 #pragma unroll
                 for (int i = 0; i < BI; ++i) dma16(rw, sBw + i * (RPP * 128), b_off[i], soff_b);
@@ -393,47 +376,6 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
                 const unsigned long long q2 = SM3_STAMP_NOW();
 #endif
                 dma_drain();
-                if constexpr (HALOBN) {
-                    if (tt == 0) {
-                        // y = relu(x * scale + shift) on the pieces THIS thread staged (they have landed: vmcnt(0) above), in
-                        // place, before the barrier publishes the image.  Rows outside the tensor keep their zero fill (no tap
-                        // that is inside its image ever reads them); rows HR.. are the zero rows.
-                        const float sc[8] = {bsc0.x, bsc0.y, bsc0.z, bsc0.w, bsc1.x, bsc1.y, bsc1.z, bsc1.w};
-                        const float sh[8] = {bsh0.x, bsh0.y, bsh0.z, bsh0.w, bsh1.x, bsh1.y, bsh1.z, bsh1.w};
-                        char* const lbase = smem + wave * (8 * 128) + lane * 16;
-                        const long gch = (long)c * 128 + (long)a_chunk;  // byte offset of the lane's vector inside a row
-                        // (one pass at a time: unrolled, the eight passes' vectors and products are all live at once and the
-                        // kernel spills 57 registers into its K loop's neighbourhood)
-#pragma unroll 1
-                        for (int i = 0; i < npass; ++i) {
-                            {
-                                const int j = (tid >> 3) + i * 32, q = q0 + j;
-                                if (j < HR && (unsigned)q < (unsigned)p.M) {
-                                    uint4* lp = reinterpret_cast<uint4*>(lbase + i * 4096);
-                                    float v[8];
-                                    unpack16<T>(*lp, v);
-#pragma unroll
-                                    for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[e] + sh[e];
-                                    // the activation / mask of a row leave from ONE workgroup: the tile of column block 0 (every
-                                    // column block transforms its own LDS copy; ADVICE r5: 2-4 x the stores otherwise)
-                                    const bool own = n0 == 0 && j >= hoff && j < hoff + BM;
-                                    const long goff = (long)q * row_bytes + gch;
-                                    if (own) {
-                                        unsigned mk = 0;
-#pragma unroll
-                                        for (int e = 0; e < 8; ++e) mk |= (v[e] > 0.f ? 1u : 0u) << e;
-                                        p.in_mask[goff >> 4] = (uint8_t)mk;
-                                    }
-#pragma unroll
-                                    for (int e = 0; e < 8; ++e) v[e] = relu_f32(v[e]);
-                                    const uint4 pk = pack16<T>(v);
-                                    *lp = pk;
-                                    if (own) stg16<true>(p.in_act + goff, pk);
-                                }
-                            }
-                        }
-                    }
-                }
 #ifdef SM3_STAMP
                 const unsigned long long q3 = SM3_STAMP_NOW();
 #endif
@@ -707,8 +649,8 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
         __syncthreads();
         SM3_MARK(3);
         if (p.partials && tid < BN && n0 + tid < p.Co) {
-            // one partial row per 128 tile rows, summed over their wave rows in wave order: a 256-row tile (kVarHalo, tall)
-            // leaves the same two rows, bit for bit, as the two 128-row tiles it replaces
+            // one partial row per 128 tile rows, summed over their wave rows in wave order: a taller tile would leave the same
+            // rows, bit for bit, as the 128-row tiles it replaces
             constexpr int G = BM / 128 > 0 ? BM / 128 : 1, WPG = WM / G;
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -1059,7 +1001,6 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
 }
 
 constexpr int kHaloLdsMax = 40960;  // a quarter of a CU's LDS: the halo kernels keep 4 workgroups per CU
-constexpr int kHaloLdsMaxTall = 53248;  // 256-row tiles (SM3_CONV_HALO_TALL): a third of a CU's LDS, 3 workgroups per CU
 
 // SM3_CONV_HALO (A/B switch, read at every launch): the halo-resident A image (kVarHalo) for the launches it fits:
 // nine taps at (-1..1, -1..1) over one tensor, stride 1, same geometry in and out, dense output and addend.
@@ -1087,16 +1028,7 @@ template <int BM, int BN>
 static bool conv_halo_ok(const ConvParams& p) {
     if (!p.kord) return false;
     const int rows = BM + 2 * (p.Wi + 1) + 2;
-    return ((rows + 31) / 32) * 4096 + BN * 128 <= (BM == 256 ? kHaloLdsMaxTall : kHaloLdsMax);
-}
-// SM3_CONV_HALO_TALL (A/B switch, read at every launch): the plain-epilogue 3x3 forward launches on 256 x 64 tiles (4 x 1
-// waves of 64 x 64: the same wave tile, accumulators and fragment traffic as 128 x 128) -- per nine K-steps a workgroup stages
-// an A image of 256 + 2 (W + 1) rows once and nine 8 KB B tiles, 108 - 112 KB for the FLOPs the 128 x 128 tile stages 168 KB
-// for (the B tiles are the larger stream since the image became resident, and L2 -> LDS bytes are what these launches and
-// their co-runners contend for: profiles/r05_corun_regs.txt), at three workgroups per CU instead of four.
-static int conv_halo_tall_mode() {
-    const char* v = getenv("SM3_CONV_HALO_TALL");
-    return v ? atoi(v) : 0;
+    return ((rows + 31) / 32) * 4096 + BN * 128 <= kHaloLdsMax;
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int STAGES, int EPI, bool SEG = false, int VAR = 0>
@@ -1121,7 +1053,7 @@ int launch_conv_st(const ConvParams& p0, hipStream_t st) {
         p.halo_a_bytes = ((p.halo_rows + 2 + 31) / 32) * 4096;  // + two zero rows (one 256-byte bank row)
         const int image = p.halo_a_bytes + BN * 128;
         LDS = image > C_BYTES + STAT ? image : C_BYTES + STAT;
-        if (LDS > (BM == 256 ? kHaloLdsMaxTall : kHaloLdsMax)) return SM3_EINVAL;  // (conv_halo_ok() is asked first)
+        if (LDS > kHaloLdsMax) return SM3_EINVAL;  // (conv_halo_ok() is asked first)
         p.halo_stat_off = LDS - STAT;
     }
     p.tilesM = (p.M + BM - 1) / BM;
@@ -1133,7 +1065,7 @@ int launch_conv_st(const ConvParams& p0, hipStream_t st) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 31) dev = 0;
     if (!(attr_set.load(std::memory_order_acquire) & (1u << dev))) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (VAR & kVarHalo) ? (BM == 256 ? kHaloLdsMaxTall : kHaloLdsMax) : LDS_STATIC);
+                                           (VAR & kVarHalo) ? kHaloLdsMax : LDS_STATIC);
         if (e != hipSuccess) return (int)e;
         attr_set.fetch_or(1u << dev, std::memory_order_release);
     }
@@ -1162,15 +1094,6 @@ static bool conv_is_pointwise(const ConvParams& p) {
 // K length measured in round 4, profiles/r04a_stage_choice_*; the double-buffered loop of rounds 1-3 was removed in round 6)
 template <typename T, int BM, int BN, int WM, int WN, int EPI, bool SEG>
 int launch_conv_lean(const ConvParams& p, hipStream_t st) {
-    if constexpr (!SEG && EPI == 1 && BM == 128 && WM == 2 && WN == 2) {
-        // 256 x 64 tiles: whole 64-column tiles only, and at least two rounds of them (3 workgroups x 256 CUs)
-        if (conv_halo_tall_mode() && p.Co % 64 == 0 && conv_halo_ok<256, 64>(p) &&
-            (long)((p.M + 255) / 256) * (p.Co / 64) >= 1536) {  // (784 tiles on 768 slots: +16 % alone, profiles/r05_tall_tiles.txt)
-            ConvParams q = p;
-            if (q.fz_view_tiles) q.fz_view_tiles = (q.fz_view_tiles % 2) ? 0 : q.fz_view_tiles / 2;  // (unused by this epilogue)
-            return launch_conv_st<T, 256, 64, 4, 1, 1, 1, false, kVarHalo>(q, st);
-        }
-    }
     if constexpr (!SEG && (EPI == 1 || EPI == 3) && WM * WN == 4) {
         if (conv_halo_ok<BM, BN>(p)) return launch_conv_st<T, BM, BN, WM, WN, 1, EPI, false, kVarHalo>(p, st);
     }
@@ -1276,48 +1199,10 @@ struct EvalBn {  // BatchNorm folded into the epilogue: precomputed vectors ([vi
     int views = 1;
 };
 
-struct BnIn {  // sm3_conv3x3_bnin: the producer's BatchNorm + ReLU applied to the A image in LDS (kVarHaloBn)
-    const float *scale, *shift;
-    int views;
-    void* act;
-    uint8_t* mask;
-    bool probe;  // true: launch nothing, return 0 iff the launch would take the halo kernel
-};
-
-// the launches sm3_conv3x3_bnin can take: what launch_conv would route to the halo-resident kernel with the plain epilogue
-template <typename T>
-static int launch_bnin(const ConvParams& p_in, int Co, bool probe, hipStream_t st) {
-    if constexpr (sizeof(T) != 2) {
-        return SM3_EDTYPE;
-    } else {
-        ConvParams p = p_in;
-        const char* lv = getenv("SM3_CONV_LEAN");
-        if (lv && atoi(lv) == 0) return SM3_EINVAL;
-        p.kord = conv_halo_geometry(p) ? 1 : 0;
-        const long tiles128 = (long)((p.M + kBM - 1) / kBM) * ((Co + 127) / 128);
-        const bool narrow = Co <= 64 || (tiles128 <= 96 && p.ntaps * p.kchunks >= 6);
-        const long nblocks = (long)((p.M + kBM - 1) / kBM) * ((Co + (narrow ? 63 : 127)) / (narrow ? 64 : 128));
-        const char* dv = getenv("SM3_CONV_DEEP");
-        const bool deep = !(dv && atoi(dv) == 0) && nblocks <= 256 && p.ntaps * p.kchunks >= 6;
-        if (deep || !p.kord) return SM3_EINVAL;
-        // SM3_CONV_BNIN (A/B, read at every launch): 2 = only the 64-column launches (layer 1: no spills, the largest tensors),
-        // 3 = only the 128-column ones
-        const char* bv = getenv("SM3_CONV_BNIN");
-        const int bmode = bv ? atoi(bv) : 1;
-        if ((bmode == 2 && !narrow) || (bmode == 3 && narrow)) return SM3_EINVAL;
-        if (narrow) {
-            if (!conv_halo_ok<kBM, 64>(p)) return SM3_EINVAL;
-            return probe ? 0 : launch_conv_st<T, kBM, 64, 2, 2, 1, 1, false, kVarHalo | kVarHaloBn>(p, st);
-        }
-        if (!conv_halo_ok<kBM, 128>(p)) return SM3_EINVAL;
-        return probe ? 0 : launch_conv_st<T, kBM, 128, 2, 2, 1, 1, false, kVarHalo | kVarHaloBn>(p, st);
-    }
-}
-
 static int conv_gather_gemm_impl(const sm3_conv_desc* d, const void* x, const void* w, void* y, const void* addend,
                                  float* stat_partials, const sm3_bn_bwd_fuse* fuse, void* stream,
-                                 const EvalBn* ebn = nullptr, const sm3_conv_seg* seg = nullptr, const BnIn* bnin = nullptr) {
-    if (!d || ((!x || !w || !y) && !(bnin && bnin->probe))) return SM3_EINVAL;
+                                 const EvalBn* ebn = nullptr, const sm3_conv_seg* seg = nullptr) {
+    if (!d || !x || !w || !y) return SM3_EINVAL;
     // fuse->x NULL: ReLU mask + sum(dz) only (the sum(dz * xhat) slot of the partial rows is written as 0)
     if (fuse && ((fuse->x && (!fuse->mean || !fuse->invstd)) || !fuse->partials || fuse->partial_row_offset < 0))
         return SM3_EINVAL;
@@ -1409,23 +1294,6 @@ static int conv_gather_gemm_impl(const sm3_conv_desc* d, const void* x, const vo
         p.col_bias = seg->col_bias;
     }
     hipStream_t st = (hipStream_t)stream;
-    p.in_scale = p.in_shift = nullptr;
-    p.in_act = nullptr;
-    p.in_mask = nullptr;
-    if (bnin) {
-        if (addend || fuse || ebn || seg) return SM3_EINVAL;
-        if (bnin->views > 1) {
-            if (bnin->views != 2 || (p.M % 2) || ((p.M / 2) % kBM)) return SM3_EALIGN;
-            p.fz_view_tiles = p.M / 2 / kBM;
-        }
-        p.in_scale = bnin->scale;
-        p.in_shift = bnin->shift;
-        p.in_act = (char*)bnin->act;
-        p.in_mask = bnin->mask;
-        if (d->dtype == SM3_BF16) return launch_bnin<bf16_t>(p, d->Co, bnin->probe, st);
-        if (d->dtype == SM3_F16) return launch_bnin<f16_t>(p, d->Co, bnin->probe, st);
-        return SM3_EDTYPE;
-    }
     // 64-column tiles for Co <= 64, and for the small-M Linears whose 128-column grid would leave most CUs idle
     const long tiles128 = (long)((p.M + kBM - 1) / kBM) * ((d->Co + 127) / 128);
     // SM3_CONV_FORCE_NARROW=1 (experiment switch, scratch/r5_corun_regs.py): 64-column tiles everywhere -- 74-83 registers per
@@ -1462,22 +1330,6 @@ extern "C" int sm3_conv_gather_gemm_seg(const sm3_conv_desc* d, const void* x0, 
     return conv_gather_gemm_impl(d, x0, w0, y, addend, nullptr, nullptr, stream, nullptr, seg);
 }
 
-// conv2 of a Bottleneck reading conv1's RAW output: y = conv3x3(relu(x_raw * in_scale[v] + in_shift[v])) with the activation
-// and its ReLU bits written on the side (kVarHaloBn).  Only for the launches the halo-resident kernel takes
-// (sm3_conv3x3_bnin_ok: stride-1 3 x 3, 16-bit, more than 256 workgroups, the A image within a quarter of a CU's LDS);
-// everything else returns SM3_EINVAL and the caller keeps the two-pass form (sm3_bn_act, then sm3_conv_gather_gemm).
-extern "C" int sm3_conv3x3_bnin_ok(const sm3_conv_desc* d, int views) {
-    const BnIn b{nullptr, nullptr, views, nullptr, nullptr, true};
-    return conv_gather_gemm_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &b) == 0 ? 1 : 0;
-}
-extern "C" int sm3_conv3x3_bnin(const sm3_conv_desc* d, const void* x_raw, const float* in_scale, const float* in_shift,
-                                int views, void* act_out, uint8_t* mask_out, const void* w, void* y, float* stat_partials,
-                                void* stream) {
-    if (!in_scale || !in_shift || !act_out || !mask_out || views < 1) return SM3_EINVAL;
-    const BnIn b{in_scale, in_shift, views, act_out, mask_out, false};
-    return conv_gather_gemm_impl(d, x_raw, w, y, nullptr, stat_partials, nullptr, stream, nullptr, nullptr, &b);
-}
-
 // Grouped 1x1 GEMM (exact f32): y[:, g*N:(g+1)*N] = x[:, g*K:(g+1)*K] @ w[g]^T for g < groups, one launch.  Each group is the
 // single-group gather-GEMM over a strided view: x as an image [rows][1][groups][K] read at column 0 with a column stride of
 // `groups` (base shifted to group g's K block), y as [rows][1][groups][N] written at column 0 (base shifted likewise) -- the same
@@ -1512,7 +1364,6 @@ extern "C" int sm3_grouped_gemm(int dtype, const void* x, const void* w, void* y
     p.x1_bytes = p.w1_bytes = p.w_view_bytes = p.w1_view_bytes = 0;
     p.Ci1 = p.kchunks1 = p.w1_row_stride = p.nsteps_seg = 0;
     for (int t = 0; t < SM3_MAX_TAPS; ++t) p.tap_src[t] = 0;
-    p.in_scale = p.in_shift = nullptr; p.in_act = nullptr; p.in_mask = nullptr;
     p.kord = 0;
     p.groups = groups;
     p.g_x_bytes = (long)K * 4;

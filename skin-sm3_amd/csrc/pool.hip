@@ -1,8 +1,7 @@
-// Stem im2col, max / average pooling (NHWC), weight layout preparation, casts.  HBM-bound
+// Max / average pooling (NHWC), weight layout preparation, casts.  HBM-bound
 // helpers around the MFMA kernels: 16-byte vector accesses along the channel axis.
 //
-// Reference call sites replaced: stem nn.Conv2d(3,64,7,2,3) input gather (src/models/resnet.py:208-210,294),
-// nn.MaxPool2d(3,2,1) (:213,297), nn.AdaptiveAvgPool2d(1)+flatten (:224,304-305) and their autograd.
+// Reference call sites replaced: nn.MaxPool2d(3,2,1) (:213,297), nn.AdaptiveAvgPool2d(1)+flatten (:224,304-305) and their autograd.
 #include "common.h"
 
 namespace {
@@ -16,7 +15,6 @@ __device__ __forceinline__ void store_elem<bf16_t>(bf16_t* p, float v) { p->v = 
 template <>
 __device__ __forceinline__ void store_elem<f16_t>(f16_t* p, float v) { p->v = f32_to_f16(v); }
 
-// cols[m][k], m = (n, oy, ox), k = (kh*7 + kw)*3 + c ; one thread per 16-byte chunk of a row
 // Index decomposition of the element-wise kernels below: 32-bit with precomputed multipliers (the host rejects
 // tensors of 2^31 vectors or more).  The 64-bit divisions by run-time values this replaces cost more than the
 // memory traffic of these kernels (im2col: 3.3 -> 1.x ms per step).
@@ -37,50 +35,6 @@ __device__ __forceinline__ void split_index(uint32_t idx, const PixDiv& d, int& 
     const uint32_t rem = pix - (uint32_t)n * d.hw.d;
     y = (int)fdiv(rem, d.w);
     x = (int)(rem - (uint32_t)y * d.w.d);
-}
-
-// One block per output row (n, oy): the 7 input rows x 3 planes that row needs are staged in LDS with coalesced
-// reads (zero padding included), then every thread composes 16-byte chunks of cols from LDS and writes them
-// contiguously (the row's Wo x Kpad block of cols is one contiguous range).  The direct gather it replaces issued 8
-// scattered 4-byte global loads per 16 bytes of output and ran at 1.7 TB/s.
-template <typename T>
-__global__ __launch_bounds__(256) void stem_im2col_kernel(const float* __restrict__ x, T* __restrict__ cols, int H,
-                                                          int W, int Ho, int Wo, int Kpad, const FastDiv div_cpr) {
-    constexpr int E = ElemTraits<T>::kPer16B;
-    extern __shared__ float tile[];  // [3][7][TW], TW = 2*Wo + 5: column j holds ix = j - 3
-    const int TW = 2 * Wo + 5;
-    const int oy = blockIdx.x % Ho, n = blockIdx.x / Ho;
-    const float* xn = x + (int64_t)n * 3 * H * W;
-    for (int r = threadIdx.x >> 6; r < 21; r += 4) {  // one wave per (plane, kh) row at a time
-        const int c = r / 7, kh = r - c * 7;
-        const int iy = oy * 2 - 3 + kh;
-        const bool rowok = (unsigned)iy < (unsigned)H;
-        const float* src = xn + ((int64_t)c * H + iy) * W;
-        for (int j = threadIdx.x & 63; j < TW; j += 64) {
-            const int ix = j - 3;
-            tile[r * TW + j] = (rowok && (unsigned)ix < (unsigned)W) ? src[ix] : 0.f;
-        }
-    }
-    __syncthreads();
-    const int cpr = Kpad / E;
-    T* out = cols + ((int64_t)blockIdx.x * Wo) * Kpad;
-    for (uint32_t idx = threadIdx.x; idx < (uint32_t)(Wo * cpr); idx += 256) {
-        const uint32_t ox = fdiv(idx, div_cpr);
-        const int ch = (int)(idx - ox * (uint32_t)cpr);
-        float v[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int k = ch * E + e;
-            float val = 0.f;
-            if (k < 147) {
-                const int tap = k / 3, c = k - tap * 3;
-                const int kh = tap / 7, kw = tap - kh * 7;
-                val = tile[(c * 7 + kh) * TW + 2 * (int)ox + kw];
-            }
-            v[e] = val;
-        }
-        stg16<true>(out + (int64_t)idx * E, pack16<T>(v));
-    }
 }
 
 template <typename T>
@@ -553,25 +507,6 @@ inline unsigned grid_for(int64_t total, int per_block = 256, int64_t cap = 8192)
     else if ((dtype) == SM3_BF16) { CALL_BF16; } \
     else if ((dtype) == SM3_F16) { CALL_F16; } \
     else return SM3_EDTYPE;
-
-extern "C" int sm3_stem_im2col(int dtype, const float* x_nchw, void* cols, int N, int H, int W, int Kpad,
-                               void* stream) {
-    if (!x_nchw || !cols || N <= 0 || H <= 0 || W <= 0 || Kpad < 147) return SM3_EINVAL;
-    const int E = dtype == SM3_F32 ? 4 : 8;
-    if (Kpad % E) return SM3_EALIGN;
-    const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-    if ((int64_t)N * Ho >= 0x7fffffffLL || (int64_t)Wo * (Kpad / E) >= 0x7fffffffLL) return SM3_EINVAL;
-    const size_t lds = (size_t)21 * (2 * Wo + 5) * sizeof(float);
-    if (lds > 64 * 1024) return SM3_EINVAL;  // image wider than ~1500 pixels
-    hipStream_t st = (hipStream_t)stream;
-    const FastDiv dc = make_fastdiv((uint32_t)(Kpad / E));
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(stem_im2col_kernel<float>, dim3(N * Ho), dim3(256), lds, st, x_nchw, (float*)cols, H, W, Ho, Wo, Kpad, dc),
-               hipLaunchKernelGGL(stem_im2col_kernel<bf16_t>, dim3(N * Ho), dim3(256), lds, st, x_nchw, (bf16_t*)cols, H, W, Ho, Wo, Kpad, dc),
-               hipLaunchKernelGGL(stem_im2col_kernel<f16_t>, dim3(N * Ho), dim3(256), lds, st, x_nchw, (f16_t*)cols, H, W, Ho, Wo, Kpad, dc));
-    SM3_CHECK_LAUNCH();
-    return 0;
-}
 
 extern "C" int sm3_maxpool3x3s2_fwd(int dtype, const void* x, void* y, uint8_t* argmax, int N, int H, int W, int C,
                                     void* stream) {

@@ -64,8 +64,6 @@ SIGNATURES = {
     "sm3_linbn_fold": [_P, _I, _I, _I, _P, _P],
     "sm3_p2p_mailbox_bytes": [],
     "sm3_p2p_max_elems": [],
-    "sm3_conv3x3_bnin_ok": [_P, _I],
-    "sm3_conv3x3_bnin": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "sm3_p2p_max_world": [],
     "sm3_p2p_layout": [_I, _I, _I, _P, _P, _P, _P],
     "sm3_p2p_alloc": [_P, _P, _P],
@@ -96,7 +94,6 @@ SIGNATURES = {
     "sm3_bn_stats_reduce": [_P, _I, _I, _P, _P, _I, _P],
     "sm3_bn_reduce_groups": [_I],
     "sm3_bn_finalize": [_P, _I, _I, _D, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],
-    "sm3_bn_stats_finalize": [_P, _I, _I, _I, _P, _P, _D, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],
     "sm3_bn_eval_scale_shift": [_P, _P, _P, _P, _F, _I, _P, _P, _P],
     "sm3_bn_act": [_I, _P, _P, _P, _P, _I, _I, _P, _P, _L, _I, _I, _P],
     "sm3_bn_add_bn_act": [_I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _I, _I, _P],
@@ -107,7 +104,6 @@ SIGNATURES = {
     "sm3_bn_bwd_partial_rows": [_L, _I],
     "sm3_bn_bwd_reduce": [_I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _I, _P],
     "sm3_bn_bwd_apply": [_I, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _L, _I, _I, _P],
-    "sm3_stem_im2col": [_I, _P, _P, _I, _I, _I, _I, _P],
     "sm3_stem_partial_rows": [_I, _I, _I],
     "sm3_stem_weight_prep": [_I, _P, _P, _P],
     "sm3_stem_weight_prep_if": [_I, _P, _P, _P, _P],

@@ -24,10 +24,8 @@ from . import ops
 from ._lib import SM3_BF16, SM3_F16, SM3_F32
 
 import os as _os
-_APPLY_OUT_OF_PLACE = _os.environ.get("SM3_BN_APPLY_OOP", "0") == "1"
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
-STEM_KPAD = 192  # 7*7*3 = 147 padded to a multiple of the 128-byte K chunk for both dtypes
 RESNET50_LAYERS = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))
 
 
@@ -100,7 +98,8 @@ class ParamStore:
 class ConvUnit:
     """groups > 1: a grouped 3x3 convolution (ResNeXt conv2, Ci == Co) on the kernels of csrc/gconv.hip, whose banks are
     [9][Co / groups][Co] in forward and in data-gradient order (sm3_gconv_weight_prep); none of the dense-kernel forms
-    (halo-resident A image, SM3_CONV_BNIN, nine-tap owner weight gradient, fused data-gradient epilogues) applies to it."""
+    (halo-resident A image, nine-tap owner weight gradient, fused data-gradient epilogues) applies to it.
+    The stem unit (stem=True) only holds the direct stem's filter bank (csrc/stem.hip); its kernels take no descriptor."""
 
     def __init__(self, name, Ci, Co, k, stride, pad, stem=False, groups=1):
         self.name, self.Ci, self.Co, self.k, self.stride, self.pad, self.stem = name, Ci, Co, k, stride, pad, stem
@@ -111,10 +110,10 @@ class ConvUnit:
         self.w_fwd = self.w_dgrad = None
         self._fd, self._dd = {}, {}
 
-    def alloc(self, dtype, device, need_dgrad=True, direct_stem=False):
+    def alloc(self, dtype, device, need_dgrad=True):
         tdt = ops.TORCH_DTYPE[dtype]
         if self.stem:
-            self.w_fwd = torch.empty(self.Co, ops.STEM_KDIRECT if direct_stem else STEM_KPAD, dtype=tdt, device=device)
+            self.w_fwd = torch.empty(self.Co, ops.STEM_KDIRECT, dtype=tdt, device=device)
         elif self.groups > 1:
             n = self.taps * self.Co * (self.Ci // self.groups)
             self.w_fwd = torch.empty(n, dtype=tdt, device=device)
@@ -127,8 +126,6 @@ class ConvUnit:
     def refresh(self, dtype, master2d):
         if self.groups > 1:
             ops.gconv_weight_prep(dtype, master2d, self.Co, self.groups, self.w_fwd, self.w_dgrad)
-        elif self.stem:
-            ops.weight_prep(dtype, master2d, self.Co, 1, 147, self.w_fwd, STEM_KPAD, None)
         else:
             ops.weight_prep(dtype, master2d, self.Co, self.taps, self.Ci, self.w_fwd, self.taps * self.Ci,
                             self.w_dgrad)
@@ -136,21 +133,7 @@ class ConvUnit:
     def fwd_desc(self, dtype, N, H, W):
         key = (dtype, N, H, W)
         if key not in self._fd:
-            if self.stem:  # GEMM over the im2col rows: N here is the row count
-                d = ops.fwd_desc(dtype, N, 1, 1, STEM_KPAD, self.Co, 1, 1, 0)
-            else:
-                d = ops.fwd_desc(dtype, N, H, W, self.Ci, self.Co, self.k, self.stride, self.pad)
-            self._fd[key] = d
-        return self._fd[key]
-
-    def wgrad_desc(self, dtype, N, H, W):
-        if not self.stem:
-            return self.fwd_desc(dtype, N, H, W)
-        key = ("wg", dtype, N)
-        if key not in self._fd:
-            d = ops.fwd_desc(dtype, N, 1, 1, STEM_KPAD, self.Co, 1, 1, 0)
-            d.w_row_stride = 147  # gradient rows are the unpadded [64][147] master layout
-            self._fd[key] = d
+            self._fd[key] = ops.fwd_desc(dtype, N, H, W, self.Ci, self.Co, self.k, self.stride, self.pad)
         return self._fd[key]
 
     def compact_dgrad_desc(self, dtype, N, Hs, Ws):
@@ -332,10 +315,6 @@ class SM3Engine:
         self.kind = kind
         self.store = None
         self.stat_sync = None
-        # one-launch BatchNorm statistics (single rank): bit-identical, 124 launches fewer per step -- and 0.8 % SLOWER in the
-        # two-lane step (62.3 vs 61.7 ms, gpurun_out r4e4): the agent-scope release fence of every block writes back an L2 that
-        # the other lane's convolution keeps dirty.  Opt-in.
-        self.fused_stats = _os.environ.get("SM3_BN_FUSED_STATS", "0") == "1"
         self.world_size = 1
         self.grad_ready = None  # callback(first_param_name, last_param_name) for gradient-bucket overlap
         self.fuse_bn_bwd = True  # BN-backward phase 1 inside the data-gradient epilogue (sm3_conv_dgrad_bnfuse)
@@ -367,28 +346,16 @@ class SM3Engine:
         self._ws = {}
         self._allocated = False
         self._lane = "main"
-        self._view = 0
         self._V = 1  # views in the batch of the encoder pass being enqueued (1, or 2 back to back)
         # Both views of a branch through the encoder as ONE batch of 2B images -- half the convolution /
         # weight-gradient / BatchNorm launches, longer K loops per weight-gradient workgroup, one SyncBN statistics
         # all-reduce per BatchNorm for both views -- with BatchNorm statistics still per view (simclr.py:58-59).
         # Needs every feature map of a view to be a multiple of 128 rows (B a multiple of 128 at 224x224).
         self.pair_views = _os.environ.get("SM3_PAIR_VIEWS", "1") != "0"
-        # the two views of a branch on two more streams (BN running statistics stay ordered through events): correct
-        # (GPU test suite passes with it on) but measured slower -- 2 700 vs 2 780 pairs/s -- so off: two lanes
-        # already keep HBM and MFMA busy, four only add contention
-        self.view_lanes = _os.environ.get("SM3_VIEW_LANES", "0") == "1"
-        self._lane_g = {}  # view lane -> (its own gradient buffer, first slot): see _lane_grad_begin
-        self._bn_ev = {}
-        self._ordered_bn = False  # set while the two views of a branch run on two lanes
-        self.side_wgrad = _os.environ.get("SM3_SIDE_WGRAD", "0") == "1"  # round 1: slower (2600 vs 2790 pairs/s); round 6, fixed-order sums on the side stream too: 4 631-4 651 vs 4 601-4 632 (+0.5 %, noise) on the default 4 hardware queues, 4 465 vs 4 590 with GPU_MAX_HW_QUEUES=8 -- stays opt-in
-        self._side = {}
         self.two_streams = True
         self._streams, self._streams_dev = None, None
-        # 7x7 stem straight from the NCHW images (csrc/stem.hip): no im2col matrix, BN-backward apply fused into the
-        # stem weight gradient; 16-bit MFMA in the throughput modes, v_mfma_f32_32x32x2_f32 in the exact-f32 mode
-        # (SM3_DIRECT_STEM=0: the round-1 im2col + gather-GEMM path, kept for A/B runs).
-        self.direct_stem = _os.environ.get("SM3_DIRECT_STEM", "1") != "0"  # all three arithmetic modes (csrc/stem.hip)
+        # The 7x7 stem reads the NCHW images directly (csrc/stem.hip): no im2col matrix, BN-backward apply fused into the
+        # stem weight gradient; 16-bit MFMA in the throughput modes, v_mfma_f32_32x32x2_f32 in the exact-f32 mode.
         # BatchNorm backward by linearity for conv3 -> bn3 of every Bottleneck (csrc/linbn.hip): no bn3 backward-apply
         # pass and no backward read of conv3's output.  16-bit modes only; the exact-f32 parity mode keeps two passes.
         self.linbn = self.dtype in (SM3_BF16, SM3_F16) and _os.environ.get("SM3_LINBN", "1") != "0"
@@ -399,12 +366,6 @@ class SM3Engine:
         self.linbn_ds = _os.environ.get("SM3_LINBN_DS", "1") != "0"
         self.linbn_join = _os.environ.get("SM3_LINBN_JOIN", "1") != "0"
         self.linbn_merge = _os.environ.get("SM3_LINBN_MERGE", "1") != "0"  # banks + post in one launch (A/B switch)
-        # bn1's apply + ReLU inside conv2's halo-resident A image (sm3_conv3x3_bnin; VERDICT r4 item 2, forward half).
-        # Bit-identical to the two-pass form and MEASURED SLOWER (profiles/r05_bnin_ab.txt: 26 bn_act launches / 0.5 ms of
-        # HBM-bound work less, but the 3x3 forward launches drop from 740-1 013 to 538-817 TFLOP/s -- every wave transforms
-        # its pieces between their landing and the barrier, where no MFMA can overlap it; two-lane step -0.3 ... -1.1 %):
-        # opt-in, SM3_CONV_BNIN=1 (2 / 3: only the 64- / 128-column launches)
-        self.bnin = _os.environ.get("SM3_CONV_BNIN", "0") != "0"
         self.lane_cross = _os.environ.get("SM3_LANE_CROSS", "1") != "0"  # cross-modal projector passes inside the lanes
         if self.cross is not None and self.cross[0] is self.cross[1]:
             # SimCLRSkinV3: ONE cross projector for both modalities -- inside the lanes its parameter gradients would receive
@@ -416,8 +377,7 @@ class SM3Engine:
         self.det_wgrad = _os.environ.get("SM3_WGRAD_DET", "1") != "0"
         # 16-bit modes: direct stem kernels on images rounded once per step and staged by LDS-DMA (sm3_stem_image_prep,
         # sm3_stem_conv_fwd16, sm3_stem_wgrad_bn16; bit-identical to the fp32-image kernels).  SM3_STEM16=0: the round-3 kernels.
-        self.stem16 = (self.direct_stem and self.dtype in (SM3_BF16, SM3_F16)
-                       and _os.environ.get("SM3_STEM16", "1") != "0")
+        self.stem16 = self.dtype in (SM3_BF16, SM3_F16) and _os.environ.get("SM3_STEM16", "1") != "0"
 
     # ---- setup ---------------------------------------------------------------------------
     def _all_conv_units(self):
@@ -441,7 +401,7 @@ class SM3Engine:
             self.store.rebind_if_needed()
         if not self._allocated:
             for cu in self._all_conv_units():
-                cu.alloc(self.dtype, device, direct_stem=self.direct_stem)
+                cu.alloc(self.dtype, device)
             self._allocated = True
         self.buffers = dict(self.module.named_buffers())
         for name, b in self.buffers.items():
@@ -468,10 +428,8 @@ class SM3Engine:
                 m = self.store.flat2d(self.store.flat_p, wname)
                 if cu.groups > 1:
                     gconvs.append((m, cu))
-                elif cu.stem and self.direct_stem:
-                    stems.append((m, cu.w_fwd))
                 elif cu.stem:
-                    items.append((m, cu.w_fwd, None, cu.Co, 1, 147, STEM_KPAD))
+                    stems.append((m, cu.w_fwd))
                 else:
                     items.append((m, cu.w_fwd, cu.w_dgrad, cu.Co, cu.taps, cu.Ci, cu.taps * cu.Ci))
             dev = self.store.flat_p.device
@@ -530,8 +488,6 @@ class SM3Engine:
             return None
         if self._streams is None or self._streams_dev != device:
             keys = list(self.branches)
-            if self.view_lanes:  # second view of every branch on a lane of its own
-                keys += [k + "#1" for k in self.branches]
             self._streams = dict(zip(keys, lane_stream_pool(device, len(keys))))
             self._streams_dev = device
         return self._streams
@@ -543,8 +499,6 @@ class SM3Engine:
         def __enter__(self):
             self.prev = self.eng._lane
             self.eng._lane = self.key
-            self.prev_view = self.eng._view
-            self.eng._view = 1 if self.key.endswith("#1") else 0
             if self.stream is not None:
                 self.stream.wait_stream(torch.cuda.current_stream())  # everything enqueued so far is visible
                 self.ctx = torch.cuda.stream(self.stream)
@@ -558,7 +512,6 @@ class SM3Engine:
                 self.pin.__exit__(*exc)
                 self.ctx.__exit__(*exc)
             self.eng._lane = self.prev
-            self.eng._view = self.prev_view
             return False
 
     def lane(self, key, streams):
@@ -585,62 +538,30 @@ class SM3Engine:
         return self.store.flat2d(self.store.flat_p, name)
 
     def _g(self, name):
-        lg = self._lane_g.get(self._lane)
-        if lg is None:
-            return self.store.flat2d(self.store.flat_g, name)
-        buf, lo = lg  # a view lane's own gradient buffer over the slots [lo, lo + buf.numel()) of the flat one
-        shape, off = self.store.shapes[name], self.store.offsets[name] - lo
-        n = math.prod(shape)
-        if off < 0 or off + n > buf.numel():
-            raise RuntimeError(f"{name} is outside the gradient range of lane {self._lane}")
-        v = buf[off: off + n]
-        return v.view(shape[0], -1) if len(shape) >= 2 else v
-
-    # With SM3_VIEW_LANES=1 the two views of a branch run encoder_backward on two streams at once, and every gradient
-    # kernel adds into its target by read-modify-write (fixed-order slab sums, BatchNorm parameter sums): on one buffer the
-    # two lanes would lose each other's addends.  View lane #1 therefore accumulates into a buffer of its own, which is
-    # added into the flat gradient after the join, behind view 0's addends: a fixed order, so the step stays
-    # bit-reproducible.
-    def _lane_grad_begin(self, plan):
-        """On the current (view-1) lane: a zeroed private gradient buffer over the slots of `plan`'s parameters."""
-        names = [n for n in self.store.names if n.startswith(plan.prefix)]
-        lo = min(self.store.offsets[n] for n in names)
-        hi = max(self.store.offsets[n] + math.prod(self.store.shapes[n]) for n in names)
-        buf = self._work("lane_grad", hi - lo)[: hi - lo]
-        buf.zero_()
-        self._lane_g[self._lane] = (buf, lo)
-
-    def _lane_grad_end(self, lane):
-        """On the branch's lane, after it waited for `lane`: flat gradient += that lane's buffer."""
-        buf, lo = self._lane_g.pop(lane)
-        self.store.flat_g[lo: lo + buf.numel()].add_(buf)
+        return self.store.flat2d(self.store.flat_g, name)
 
     # ---- conv + BN (+residual) (+ReLU) ---------------------------------------------------
     def conv_bn(self, cu, bu, x, N, H, W, relu, residual=None, train=True, save=None, out_f32=False, y_out=None,
-                apply=True, scale_shift=None, res_affine=None, pending=None, colsum=None, bn_in=None):
+                apply=True, scale_shift=None, res_affine=None, pending=None, colsum=None):
         """One conv + BatchNorm (+residual) (+ReLU) unit on N images.  With self._V == 2 the batch is two views back
         to back (N = 2B): one convolution launch, BatchNorm statistics / running-statistics updates per view.
         apply=False: stop after the statistics -- returns the pre-BatchNorm tensor, scale/shift are left in
         `scale_shift` for the consumer that applies them (the join of a downsample block, the stem's fused
         BN+ReLU+maxpool).  res_affine=(scale2, shift2): `residual` is such a pre-BatchNorm tensor and is normalised
         inside this unit's apply pass.
-        bn_in=(x_raw, scale, shift, mask): x is still EMPTY -- it is the activation relu(x_raw * scale[v] + shift[v]) of the
-        producer unit (called with apply=False), which this unit's convolution computes on its staged input image and writes
-        to x / mask on the side (sm3_conv3x3_bnin: the producer's apply pass disappears).
         pending (data parallel only): a list shared by the two BatchNorms that meet at a residual join.  The unit called
         with apply=False (the downsample branch) leaves its per-rank statistic sums in the first half of a shared buffer
         and queues its finalize there instead of synchronising; the unit called next with the same list (conv3) puts
         its sums behind them, all-reduces BOTH in one collective and runs the queued finalize before its own."""
         dev = x.t.device if isinstance(x, ops.StemImage) else x.device
-        direct = cu.stem and self.direct_stem  # x is the NCHW fp32 image batch (or its StemImage), N / H / W its geometry
+        direct = cu.stem  # x is the NCHW fp32 image batch (or its StemImage), N / H / W its geometry
         if direct:
             d = None
             Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-            rows = N * Ho * Wo
         else:
             d = cu.fwd_desc(self.dtype, N, H, W)
-            Ho, Wo = (1, 1) if cu.stem else (d.Ho, d.Wo)
-            rows = N if cu.stem else N * Ho * Wo
+            Ho, Wo = d.Ho, d.Wo
+        rows = N * Ho * Wo
         C = cu.Co
         V = self._V if train else 1
         rows_v = rows // V
@@ -661,8 +582,6 @@ class SM3Engine:
                 (ops.stem_conv_fwd16 if isinstance(x, ops.StemImage) else ops.stem_conv_fwd)(self.dtype, x, cu.w_fwd, xo, partials)
             elif cu.groups > 1:
                 ops.gconv_fwd(self.dtype, x, cu.w_fwd, xo, partials, N, H, W, C, cu.groups, cu.stride)
-            elif bn_in is not None:
-                ops.conv3x3_bnin(d, bn_in[0], bn_in[1], bn_in[2], x, bn_in[3], cu.w_fwd, xo, partials, views=V)
             else:
                 ops.conv_gemm(d, x, cu.w_fwd, xo, None, partials)
             count, groups = rows_v, 1
@@ -690,34 +609,14 @@ class SM3Engine:
                     sums = self._work("sums", 2 * 2 * 2048, torch.float64)
                     ops.bn_stats_reduce(partials, prow // V, C, sums, views=V)
                     self.stat_sync(sums[:n])  # one all-reduce for both views
-            elif self.fused_stats:
-                # single rank: the whole statistics chain (row-group sums, their total, mean / var / scale / shift, running
-                # statistics) is ONE launch -- the last block to arrive finalizes (sm3_bn_stats_finalize)
-                sums, groups = None, 0
-            else:  # ... or two: stage B of the reduction folded into bn_finalize (SM3_BN_FUSED_STATS=0)
+            else:  # single rank: stage B of the reduction folded into bn_finalize
                 sums, groups = ops.bn_stats_reduce(partials, prow // V, C, None, views=V)
-            ordered = self._ordered_bn and dev.type == "cuda"
 
             def finalize(sums=sums, groups=groups):
-                if ordered and self._view == 1:
-                    # running_mean/var/num_batches_tracked are updated view 0 first, then view 1, as in the reference's
-                    # sequential encoder(x1); encoder(x2): the view-1 lane waits for view 0's update of THIS BatchNorm
-                    torch.cuda.current_stream().wait_event(self._bn_ev[bu.name])
-                if sums is None:
-                    ops.bn_stats_finalize(partials, prow // V, count, C, gamma, beta, BN_EPS, BN_MOMENTUM,
-                                          rm if track else None, rv if track else None,
-                                          self.buffers[bu.name + ".num_batches_tracked"] if track else None,
-                                          scale, shift, mean, invstd, views=V)
-                else:
-                    ops.bn_finalize(sums, count, C, gamma, beta, BN_EPS, BN_MOMENTUM, rm if track else None,
-                                    rv if track else None,
-                                    self.buffers[bu.name + ".num_batches_tracked"] if track else None,
-                                    scale, shift, mean, invstd, groups=groups, views=V)
-                if ordered and self._view == 0:
-                    ev = self._bn_ev.get(bu.name)
-                    if ev is None:
-                        ev = self._bn_ev[bu.name] = torch.cuda.Event()
-                    ev.record()
+                ops.bn_finalize(sums, count, C, gamma, beta, BN_EPS, BN_MOMENTUM, rm if track else None,
+                                rv if track else None,
+                                self.buffers[bu.name + ".num_batches_tracked"] if track else None,
+                                scale, shift, mean, invstd, groups=groups, views=V)
             if deferred:
                 pending.append((V * 2 * C, finalize))
             else:
@@ -788,7 +687,7 @@ class SM3Engine:
         else:  # [V][fused_rows][2][C], left by the data-gradient launches
             prow, bpart = fused_rows, self._ws[(self._lane, "fz_partials")]
         lsums, gsums, count = self._bn_backward_sums(r, bpart, prow)
-        dxo = torch.empty_like(r.xo) if (keep_dz or _APPLY_OUT_OF_PLACE) else dy
+        dxo = torch.empty_like(r.xo) if keep_dz else dy
         gamma = self._p(r.bu.name + ".weight") if r.bu.affine else None
         dgamma = self._g(r.bu.name + ".weight") if r.bu.affine else None
         dbeta = self._g(r.bu.name + ".bias") if r.bu.affine else None
@@ -1134,66 +1033,22 @@ class SM3Engine:
         return dz2, nrows // V, ds
 
     def _wgrad(self, cu, r, dxo):
-        """Weight gradient on the lane's side stream: nothing on the critical path (data gradient -> BN backward ->
-        ...) depends on it, so it overlaps with those HBM-bound kernels and fills their tails."""
-        side = self._side_stream()
+        """Weight gradient of a unit, accumulated into the flat gradient buffer on the lane's stream."""
+        gw = self._g(cu.name + ".weight")
         if cu.groups > 1:
-            gw = self._g(cu.name + ".weight")
             n = gw.numel()
             cap = ops.wgrad_det_cap(n)
-            if side is None:
-                ops.gconv_wgrad_det(self.dtype, r.x_in, dxo, gw, self._work("wgrad_slabs", cap * n), cap, r.N, r.H, r.W, cu.Co,
-                                    cu.groups, cu.stride)
-                return
-            cur = torch.cuda.current_stream()
-            side.wait_stream(cur)
-            for t in (dxo, r.x_in):
-                t.record_stream(side)
-            with torch.cuda.stream(side), ops.stream_scope():
-                ops.gconv_wgrad_det(self.dtype, r.x_in, dxo, gw, self._work("wgrad_slabs_side", cap * n), cap, r.N, r.H, r.W,
-                                    cu.Co, cu.groups, cu.stride)
+            ops.gconv_wgrad_det(self.dtype, r.x_in, dxo, gw, self._work("wgrad_slabs", cap * n), cap, r.N, r.H, r.W, cu.Co,
+                                cu.groups, cu.stride)
             return
-        desc = cu.wgrad_desc(self.dtype, r.N, r.H, r.W)
-        gw = self._g(cu.name + ".weight")
-        if side is None:
-            if self.det_wgrad and desc.w_row_stride == desc.ntaps * desc.Ci:
-                # fixed-order split-K sum (plain-store slabs + sm3_slab_reduce): the gradient is a function of the inputs
-                n = desc.Co * desc.w_row_stride
-                cap = ops.wgrad_det_cap(n)
-                ops.conv_wgrad_det(desc, r.x_in, dxo, gw, self._work("wgrad_slabs", cap * n), cap)
-            else:
-                ops.conv_wgrad(desc, r.x_in, dxo, gw)
-            return
-        cur = torch.cuda.current_stream()
-        side.wait_stream(cur)  # dxo is ready
-        for t in (dxo, r.x_in):
-            t.record_stream(side)  # keep the allocator from recycling them while the side stream still reads
-        with torch.cuda.stream(side), ops.stream_scope():
-            if self.det_wgrad and desc.w_row_stride == desc.ntaps * desc.Ci:
-                n = desc.Co * desc.w_row_stride
-                cap = ops.wgrad_det_cap(n)
-                slabs = self._work("wgrad_slabs_side", cap * n)  # the side stream's own slabs (its launches are in order)
-                ops.conv_wgrad_det(desc, r.x_in, dxo, gw, slabs, cap)
-            else:
-                ops.conv_wgrad(desc, r.x_in, dxo, gw)
-
-    def _side_stream(self):
-        if not self.side_wgrad or self.store.flat_p.device.type != "cuda":
-            return None
-        st = self._side.get(self._lane)
-        if st is None:
-            # behind the lane streams in the measured pool (needs GPU_MAX_HW_QUEUES >= 6 to get queues of their own)
-            dev = self.store.flat_p.device
-            nl = len(self._streams or {}) or len(self.branches)
-            st = lane_stream_pool(dev, nl + len(self._side) + 1)[nl + len(self._side)]
-            self._side[self._lane] = st
-        return st
-
-    def _sync_side(self):
-        """Current lane waits for its weight-gradient stream (before gradients are declared final)."""
-        st = self._side.get(self._lane)
-        if st is not None:
-            torch.cuda.current_stream().wait_stream(st)
+        desc = cu.fwd_desc(self.dtype, r.N, r.H, r.W)
+        if self.det_wgrad:
+            # fixed-order split-K sum (plain-store slabs + sm3_slab_reduce): the gradient is a function of the inputs
+            n = desc.Co * desc.w_row_stride
+            cap = ops.wgrad_det_cap(n)
+            ops.conv_wgrad_det(desc, r.x_in, dxo, gw, self._work("wgrad_slabs", cap * n), cap)
+        else:
+            ops.conv_wgrad(desc, r.x_in, dxo, gw)
 
     def conv_backward(self, r, dxo, need_dx=True, addend=None, into=None, fuse=None, addend_sparse=None):
         """Weight gradient (accumulated into the flat gradient buffer) and, if need_dx, the data gradient.
@@ -1295,33 +1150,22 @@ class SM3Engine:
         N, _, H, W = x.shape
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         recs = [] if save is not None else None
-        if self.direct_stem:
-            stem_in, sN, sH, sW = x, N, H, W  # the 7x7 convolution reads the NCHW images directly
-        else:
-            cols = torch.empty(N * Ho * Wo, STEM_KPAD, dtype=self.tdt, device=dev0)
-            ops.stem_im2col(self.dtype, x, cols, STEM_KPAD)
-            stem_in, sN, sH, sW = cols, N * Ho * Wo, 1, 1
-            del cols
         Hp, Wp = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
         p = torch.empty(N * Hp * Wp, 64, dtype=self.tdt, device=dev0)
         amax = torch.empty(N * Hp * Wp * 64, dtype=torch.uint8, device=dev0) if save is not None else None
         lazy = train or save is not None  # not the single-launch conv+evalBN inference path
-        if lazy or self.direct_stem:
-            # stem BatchNorm + ReLU + max-pool in ONE pass over the pre-BN stem output: the post-ReLU map (the largest
-            # activation of the network) and its ReLU mask are never stored; backward recomputes the mask
-            V = self._V if train else 1
-            sc = torch.empty(V * 64, dtype=torch.float32, device=dev0)
-            sh = torch.empty(V * 64, dtype=torch.float32, device=dev0)
-            xo, _, _ = self.conv_bn(plan.stem, plan.stem_bn, stem_in, sN, sH, sW, True, None, train, recs,
-                                    apply=False, scale_shift=(sc, sh))
-            if recs is not None:
-                recs[0].scale, recs[0].shift = sc, sh
-            ops.bn_relu_maxpool_fwd(self.dtype, xo, sc, sh, p, N, Ho, Wo, 64, amax, views=V)
-            del xo
-        else:
-            y, _, _ = self.conv_bn(plan.stem, plan.stem_bn, stem_in, sN, sH, sW, True, None, train, recs)
-            ops.maxpool_fwd(self.dtype, y, p, N, Ho, Wo, 64, amax)
-        del stem_in
+        # the 7x7 convolution reads the NCHW images directly; stem BatchNorm + ReLU + max-pool in ONE pass over the pre-BN
+        # stem output: the post-ReLU map (the largest activation of the network) and its ReLU mask are never stored;
+        # backward recomputes the mask
+        V = self._V if train else 1
+        sc = torch.empty(V * 64, dtype=torch.float32, device=dev0)
+        sh = torch.empty(V * 64, dtype=torch.float32, device=dev0)
+        xo, _, _ = self.conv_bn(plan.stem, plan.stem_bn, x, N, H, W, True, None, train, recs, apply=False,
+                                scale_shift=(sc, sh))
+        if recs is not None:
+            recs[0].scale, recs[0].shift = sc, sh
+        ops.bn_relu_maxpool_fwd(self.dtype, xo, sc, sh, p, N, Ho, Wo, 64, amax, views=V)
+        del xo
         cur, h, w = p, Hp, Wp
         if taps is not None:
             taps["x"] = [p.clone()]
@@ -1359,32 +1203,15 @@ class SM3Engine:
                 if taps is not None:
                     taps["x"].append(cur.clone())
                 continue
-            # conv1 -> bn1 -> relu -> conv2 (resnet.py:144-150).  Where conv2 runs on the halo-resident kernel, bn1's apply +
-            # ReLU happens on conv2's staged input image: conv1 stops after its statistics, conv2 reads conv1's RAW output
-            # and writes the activation + ReLU bits that its weight gradient and bn1's backward need on the side
-            bn_in = None
-            if (self.bnin and train and save is not None and self.dtype != ops.SM3_F32 and blk["c2"].stride == 1
-                    and blk["c2"].groups == 1):
-                d1 = blk["c1"].fwd_desc(self.dtype, N, h, w)
-                if ops.conv3x3_bnin_ok(blk["c2"].fwd_desc(self.dtype, N, d1.Ho, d1.Wo), Vt):
-                    C1 = blk["c1"].Co
-                    sc1 = torch.empty(Vt * C1, dtype=torch.float32, device=dev0)
-                    sh1 = torch.empty(Vt * C1, dtype=torch.float32, device=dev0)
-                    x1, h1, w1 = self.conv_bn(blk["c1"], blk["b1"], cur, N, h, w, True, None, train, br, apply=False,
-                                              scale_shift=(sc1, sh1))
-                    y1 = torch.empty_like(x1)
-                    mk1 = torch.empty(x1.numel() // (16 // ops._sz(self.dtype)), dtype=torch.uint8, device=dev0)
-                    br[0].y, br[0].mask = y1, mk1
-                    bn_in = (x1, sc1, sh1, mk1)
-            if bn_in is None:
-                y1, h1, w1 = self.conv_bn(blk["c1"], blk["b1"], cur, N, h, w, True, None, train, br)
+            # conv1 -> bn1 -> relu -> conv2 (resnet.py:144-150)
+            y1, h1, w1 = self.conv_bn(blk["c1"], blk["b1"], cur, N, h, w, True, None, train, br)
             pp = blk["c3"].Ci
             cs = crow = None
             if lin:
                 d2 = blk["c2"].fwd_desc(self.dtype, N, h1, w1)
                 crow = ops.bn_act_colsum_rows(self.dtype, N * d2.Ho * d2.Wo // Vt, pp)
                 cs = self._work("linbn_cs", Vt * crow * pp)
-            y2, h2, w2 = self.conv_bn(blk["c2"], blk["b2"], y1, N, h1, w1, True, None, train, br, colsum=cs, bn_in=bn_in)
+            y2, h2, w2 = self.conv_bn(blk["c2"], blk["b2"], y1, N, h1, w1, True, None, train, br, colsum=cs)
             if lin:
                 slabs, cap = self._slab_buf(pp * pp, Vt)
                 ns = ops.conv_wgrad_slabs(self._lin_conv_desc(self.dtype, N, h2, w2, pp, pp), y2, y2, slabs, views=Vt, cap=cap)
@@ -1395,8 +1222,8 @@ class SM3Engine:
             ra = None
             pend = None
             # the join by linearity needs what its backward needs (conv3_backward_linbn, lin_d)
-            join_lin = (lin and "cd" in blk and self.linbn_fwd and self.linbn_ds and self.linbn_join and not self._ordered_bn
-                        and self.fuse_bn_bwd and blk["cd"].Ci % 64 == 0 and
+            join_lin = (lin and "cd" in blk and self.linbn_fwd and self.linbn_ds and self.linbn_join and self.fuse_bn_bwd
+                        and blk["cd"].Ci % 64 == 0 and
                         (blk["cd"].stride == 1 or (bi > 0 and blk["cd"].stride == 2 and
                                                    (Vt == 1 or (N * h * w) % 256 == 0))))
             if join_lin:
@@ -1417,7 +1244,7 @@ class SM3Engine:
                 idn, _, _ = self.conv_bn(blk["cd"], blk["bd"], cur, N, h, w, False, None, train, br)
             else:
                 idn = cur
-            if lin and "cd" not in blk and self.linbn_fwd and not self._ordered_bn:
+            if lin and "cd" not in blk and self.linbn_fwd:
                 # conv3 -> bn3 -> (+identity) -> ReLU in ONE launch: bn3's batch statistics come from the moments of y2
                 y3, h3, w3 = self.conv3_bn3_fused(blk["c3"], blk["b3"], br[1], y2, idn, N, h2, w2, br)
             else:
@@ -1565,17 +1392,13 @@ class SM3Engine:
         part = self._work("fz_partials", rs.V * prow * 2 * 64)
         ops.maxpool_bn_bwd(self.dtype, ctx["argmax"], dcur, rs.xo, rs.scale, rs.shift, rs.mean, rs.invstd, dz, part,
                            N, Ho, Wo, 64, views=rs.V)
-        if self.direct_stem:
-            # BatchNorm-backward apply inside the stem weight gradient's operand load: d(conv1 output) never reaches HBM
-            lsums, gsums, count = self._bn_backward_sums(rs, part, prow)
-            bn = rs.bu.name
-            wg = ops.stem_wgrad_bn16 if isinstance(rs.x_in, ops.StemImage) else ops.stem_wgrad_bn
-            wg(self.dtype, rs.x_in, dz, rs.xo, rs.mean, rs.invstd, self._p(bn + ".weight"), gsums, count,
-               lsums, self._g(bn + ".weight"), self._g(bn + ".bias"), self._g(rs.cu.name + ".weight"), views=rs.V,
-               slabs=self._work("stem_slabs", ops.STEM_WGRAD_SLABS * 64 * 147) if self.det_wgrad else None)
-        else:
-            dxo, _ = self.bn_backward(rs, dz, keep_dz=False, fused_rows=prow)
-            self.conv_backward(rs, dxo, need_dx=False)
+        # BatchNorm-backward apply inside the stem weight gradient's operand load: d(conv1 output) never reaches HBM
+        lsums, gsums, count = self._bn_backward_sums(rs, part, prow)
+        bn = rs.bu.name
+        wg = ops.stem_wgrad_bn16 if isinstance(rs.x_in, ops.StemImage) else ops.stem_wgrad_bn
+        wg(self.dtype, rs.x_in, dz, rs.xo, rs.mean, rs.invstd, self._p(bn + ".weight"), gsums, count,
+           lsums, self._g(bn + ".weight"), self._g(bn + ".bias"), self._g(rs.cu.name + ".weight"), views=rs.V,
+           slabs=self._work("stem_slabs", ops.STEM_WGRAD_SLABS * 64 * 147) if self.det_wgrad else None)
         if last_view:
             self._notify(plan.prefix + "conv1", plan.prefix + "layer1.")
 
@@ -1623,7 +1446,7 @@ class SM3Engine:
         # clinical ones, so each runs at the end of its modality's lane, hidden behind the other lane's encoder, instead of
         # on the main stream after the join (4 projector passes = ~50 small dependent launches in series).
         lane_cross = (self.cross is not None and streams is not None and set(self.branches) == {"derm", "clinic"}
-                      and not self.view_lanes and self.lane_cross)
+                      and self.lane_cross)
         pairs = self.cross_pairs(style) if self.cross is not None else []
         zc = [self._share(torch.empty(2 * B, self.module.proj_dim, dtype=torch.float32, device=dev), streams) for _ in pairs] \
             if lane_cross else []
@@ -1637,15 +1460,13 @@ class SM3Engine:
             f32 = self._share(torch.empty(2 * B, plan.out_dim, dtype=torch.float32, device=dev), streams)
             ft = self._share(torch.empty(2 * B, plan.out_dim, dtype=self.tdt, device=dev), streams)
             ctxs = [None, None] if want_grad else None
-            split = bool(streams) and self.view_lanes
-            self._ordered_bn = split and train
             # the two views go through the encoder separately: BN statistics per view (simclr.py:58-59)
-            pair = (self.pair_views and train and not split and len(imgs) == 2 and imgs[0].shape == imgs[1].shape
+            pair = (self.pair_views and train and len(imgs) == 2 and imgs[0].shape == imgs[1].shape
                     and self.pair_ok(B, imgs[0].shape[2], imgs[0].shape[3])
-                    # the kernels address a tensor with 32-bit buffer offsets below 3 GB; the largest one is the stem's
-                    # im2col matrix (SM3_DIRECT_STEM=0) or the stem / layer1 maps (direct stem)
+                    # the kernels address a tensor with 32-bit buffer offsets below 3 GB; the largest ones are the stem /
+                    # layer1 maps
                     and 2 * B * ((imgs[0].shape[2] - 1) // 2 + 1) * ((imgs[0].shape[3] - 1) // 2 + 1)
-                    * (64 if self.direct_stem else STEM_KPAD) * ops._sz(self.dtype) < 0xC0000000)
+                    * 64 * ops._sz(self.dtype) < 0xC0000000)
             if pair:  # both views as one batch of 2B images (BatchNorm statistics still per view)
                 with self.lane(key, streams):
                     tmp = [] if want_grad else None
@@ -1653,17 +1474,14 @@ class SM3Engine:
                     if want_grad:
                         ctxs = [tmp[0]]
             for v in (() if pair else (0, 1)):
-                with self.lane(key + "#1" if (split and v == 1) else key, streams):
+                with self.lane(key, streams):
                     tmp = [] if want_grad else None
                     self.encoder_forward(plan, imgs[v], train, f32[v * B:(v + 1) * B], ft[v * B:(v + 1) * B], tmp)
                     if want_grad:
                         ctxs[v] = tmp[0]
-            self._ordered_bn = False
             feats[key] = (f32, ft)
             precs = sv()
             with self.lane(key, streams):
-                if split:
-                    torch.cuda.current_stream().wait_stream(streams[key + "#1"])
                 if proj is not None:  # in-modal projector on cat([f1, f2])  (simclr.py:61)
                     z = torch.empty(2 * B, self.module.proj_dim, dtype=torch.float32, device=dev)
                     self.projector_forward(proj, ft, 2 * B, train, z, precs)
@@ -1720,7 +1538,6 @@ class SM3Engine:
 
     def _notify(self, plan_prefix_first, plan_prefix_last):
         if self.grad_ready is not None:
-            self._sync_side()
             self.grad_ready(plan_prefix_first, plan_prefix_last)
 
     def backward(self, saved, dz, dfeat=None):
@@ -1735,8 +1552,8 @@ class SM3Engine:
             self._share(t, streams)
         # mirror of forward(): each cross-modal projector's backward inside its modality's lane (no join, no main-stream pass)
         lane_cross = (self.cross is not None and streams is not None and set(self.branches) == {"derm", "clinic"}
-                      and not self.view_lanes and self.lane_cross and bool(saved.get("cross")) and all(f"cross{ci}" in dz
-                                                                                 for ci in range(len(saved["cross"]))))
+                      and self.lane_cross and bool(saved.get("cross")) and all(f"cross{ci}" in dz
+                                                                             for ci in range(len(saved["cross"]))))
         for key, (plan, proj) in self.branches.items():
             extra = dfeat.get(key) if dfeat is not None else None
             self._share(extra, streams)
@@ -1757,7 +1574,6 @@ class SM3Engine:
                     if proj is not None:
                         self._notify(proj.prefix, proj.prefix)
                     self._notify(self.cross[side].prefix, self.cross[side].prefix)
-                self._sync_side()
         if not lane_cross:
             self._join(streams)
             for ci, (a, b, pa, pb) in enumerate(saved["cross"]):
@@ -1774,32 +1590,16 @@ class SM3Engine:
             if "meta" in dz and saved.get("meta") is not None:
                 self.projector_backward(saved["meta"], dz["meta"])
             self._notify(self.meta.prefix, self.meta.prefix)
-        split = bool(streams) and self.view_lanes
         for key, (plan, proj) in self.branches.items():
             if len(saved[key]["enc"]) == 1:  # both views went through as one batch
                 with self.lane(key, streams):
                     self.encoder_backward(saved[key]["enc"][0], dfe[key], last_view=True)
                     saved[key]["enc"][0] = None
-                    self._sync_side()
                 continue
             for v in (1, 0):
-                with self.lane(key + "#1" if (split and v == 1) else key, streams):
-                    if split and v == 1:
-                        self._lane_grad_begin(plan)
-                    # with the views on two lanes a stage's gradients are final only when BOTH are done: the
-                    # per-stage notifications of the last view are replaced by one round after the join below
-                    self.encoder_backward(saved[key]["enc"][v], dfe[key][v * B:(v + 1) * B],
-                                          last_view=(v == 0 and not split))
-                    saved[key]["enc"][v] = None  # free the view's activations as soon as it is done
-                    self._sync_side()
-            if split:
                 with self.lane(key, streams):
-                    torch.cuda.current_stream().wait_stream(streams[key + "#1"])
-                    self._lane_grad_end(key + "#1")
-                    for li in (4, 3, 2):
-                        self._notify(f"{plan.prefix}layer{li}.", f"{plan.prefix}layer{li}.")
-                    self._notify(plan.prefix + "conv1", plan.prefix + "layer1.")
-        self._sync_side()
+                    self.encoder_backward(saved[key]["enc"][v], dfe[key][v * B:(v + 1) * B], last_view=(v == 0))
+                    saved[key]["enc"][v] = None  # free the view's activations as soon as it is done
         self._join(streams)
 
     def encoder_only(self, branch, x, train, want_grad):

@@ -805,35 +805,6 @@ def linbn_post(dtype, wbn, w_dgrad, hn, P, G, Tm, s, coef, dw, Cn, p, views=1):
                                          _ptr(coef), _ptr(dw), Cn, p, views, _stream()), "sm3_linbn_post")
 
 
-def conv3x3_bnin_ok(desc, views=1):
-    """True iff conv3x3_bnin can take this launch (the halo-resident kernel would run it: sm3_conv3x3_bnin_ok)."""
-    return bool(_lib.load().sm3_conv3x3_bnin_ok(C.byref(desc), int(views)))
-
-
-def conv3x3_bnin(desc, x_raw, in_scale, in_shift, act_out, mask_out, w, y, stat_partials, views=1):
-    """y = conv3x3(relu(x_raw * in_scale[v] + in_shift[v])) + BatchNorm partial sums of y; the activation and its ReLU bits
-    written on the side (sm3_conv3x3_bnin): bn_act + conv_gemm in one launch, bit for bit."""
-    tdt = TORCH_DTYPE[desc.dtype]
-    _chk(x_raw, tdt, "x_raw"); _chk(act_out, tdt, "act_out"); _chk(w, tdt, "w"); _chk(y, tdt, "y")
-    _chk(in_scale, torch.float32, "in_scale"); _chk(in_shift, torch.float32, "in_shift")
-    _chk(mask_out, torch.uint8, "mask_out"); _chk(stat_partials, torch.float32, "stat_partials")
-    M = desc.N * desc.Ho * desc.Wo
-    n_in = desc.N * desc.Hi * desc.Wi * desc.Ci
-    if x_raw.numel() != n_in or act_out.numel() != n_in or mask_out.numel() != n_in // 8 or y.numel() != M * desc.Co or \
-            in_scale.numel() < views * desc.Ci or in_shift.numel() < views * desc.Ci or w.numel() != desc.Co * desc.w_row_stride:
-        raise ValueError("conv3x3_bnin: operand size does not match descriptor")
-    if stat_partials is not None and stat_partials.numel() < conv_partial_rows(desc) * 2 * desc.Co:
-        raise ValueError("conv3x3_bnin: partials workspace too small")
-    sz = _sz(desc.dtype)
-    tag = _conv_tag(desc)
-    if _PROFILER is not None and getattr(_PROFILER, "detail", False):
-        tag += f"|M{M}_K{desc.ntaps}x{desc.Ci}_N{desc.Co}_s{desc.osy}_bnin"
-    with _prof(tag, 2.0 * M * desc.Co * desc.ntaps * desc.Ci, sz * (2 * n_in + M * desc.Co) + n_in // 8):
-        check(_lib.load().sm3_conv3x3_bnin(C.byref(desc), _ptr(x_raw), _ptr(in_scale), _ptr(in_shift), int(views),
-                                           _ptr(act_out), _ptr(mask_out), _ptr(w), _ptr(y), _ptr(stat_partials), _stream()),
-              "sm3_conv3x3_bnin")
-
-
 def linbn_banks_post(dtype, w_dgrad, coef, wa, col_const, hn, P, G, Tm, s, dw, Cn, p, views=1):
     """linbn_banks + linbn_post in one launch (sm3_linbn_banks_post): same wa / col_const / hn / dw, bit for bit."""
     tdt = TORCH_DTYPE[dtype]
@@ -938,39 +909,6 @@ def bn_finalize(sums, count, Cn, gamma, beta, eps, momentum, running_mean, runni
         check(_lib.load().sm3_bn_finalize(_ptr(sums), groups, views, float(count), Cn, _ptr(gamma), _ptr(beta), eps,
                                           momentum, _ptr(running_mean), _ptr(running_var), _ptr(nbt), _ptr(scale),
                                           _ptr(shift), _ptr(save_mean), _ptr(save_invstd), _stream()), "sm3_bn_finalize")
-
-
-_bn_tickets = {}
-
-
-def bn_stats_finalize(partials, rows, count, Cn, gamma, beta, eps, momentum, running_mean, running_var, nbt, scale, shift,
-                      save_mean, save_invstd, views=1):
-    """bn_stats_reduce (stage A) + bn_finalize as ONE launch (single rank): partials [views][rows][2][C] -> scale / shift /
-    save_mean / save_invstd [views][C], running statistics updated view by view.  Same bits as the two-launch form."""
-    _chk(partials, torch.float32, "partials")
-    for t, n in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
-        _chk(t, torch.float32, n)
-        if t is not None and t.numel() < Cn:
-            raise ValueError(f"{n} too small")
-    for t, n in ((scale, "scale"), (shift, "shift"), (save_mean, "save_mean"), (save_invstd, "save_invstd")):
-        _chk(t, torch.float32, n)
-        if t is not None and t.numel() < views * Cn:
-            raise ValueError(f"{n} too small")
-    _chk(nbt, torch.int64, "num_batches_tracked")
-    if partials.numel() < views * rows * 2 * Cn:
-        raise ValueError("bn_stats_finalize: partials too small")
-    ws = _bn_workspace(partials.device, Cn, views)
-    key = (partials.device, _stream_handle() if partials.device.type == "cuda" else 0)
-    tk = _bn_tickets.get(key)
-    if tk is None:  # zero once; every launch leaves them zero (stream-ordered reuse: one set per device AND stream)
-        tk = _bn_tickets[key] = torch.zeros(256, dtype=torch.int32, device=partials.device)
-    if (Cn + 31) // 32 > tk.numel():
-        raise ValueError("bn_stats_finalize: more than 8192 channels")
-    with _prof("bn_stats_finalize", 0.0, 4.0 * views * rows * 2 * Cn):
-        check(_lib.load().sm3_bn_stats_finalize(_ptr(partials), rows, Cn, views, _ptr(ws), _ptr(tk), float(count), _ptr(gamma),
-                                                _ptr(beta), eps, momentum, _ptr(running_mean), _ptr(running_var), _ptr(nbt),
-                                                _ptr(scale), _ptr(shift), _ptr(save_mean), _ptr(save_invstd), _stream()),
-              "sm3_bn_stats_finalize")
 
 
 def bn_eval_scale_shift(gamma, beta, running_mean, running_var, eps, Cn, scale, shift):
@@ -1183,18 +1121,6 @@ def bn_bwd_apply(dtype, dz, x, mean, invstd, gamma, gsums, count, lsums, dgamma,
 # ------------------------------------------------------------------------------------------
 # stem / pooling / weights
 # ------------------------------------------------------------------------------------------
-def stem_im2col(dtype, x_nchw, cols, Kpad):
-    _chk(x_nchw, torch.float32, "x"); _chk(cols, TORCH_DTYPE[dtype], "cols")
-    N, Cc, H, W = x_nchw.shape
-    if Cc != 3:
-        raise ValueError("stem expects 3 input channels")
-    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    if cols.numel() != N * Ho * Wo * Kpad:
-        raise ValueError("cols size mismatch")
-    with _prof("stem_im2col", 0.0, 4.0 * x_nchw.numel() + _sz(dtype) * cols.numel()):
-        check(_lib.load().sm3_stem_im2col(dtype, _ptr(x_nchw), _ptr(cols), N, H, W, Kpad, _stream()), "sm3_stem_im2col")
-
-
 STEM_KDIRECT = 176  # K of the direct stem's filter bank: (kh, c) groups x 8 (kw padded), 22nd group zero
 
 

@@ -5,8 +5,8 @@ Same public surface as the reference file (resnet.py:177-329, 680-751): `ResNet`
 attribute names (`conv1, bn1, relu, maxpool,
 layer1..4, avgpool, fc`) and therefore the same state_dict keys, Kaiming fan_out initialisation
 (resnet.py:227-232) and `zero_init_residual`.  The nn.Conv2d / nn.BatchNorm2d children are parameter
-containers only: `forward` runs the hand-written gfx950 kernels through sm3hip.engine (stem im2col +
-MFMA GEMM, gather-GEMM convolutions with BN-statistics epilogues, fused BN/residual/ReLU, pooling).
+containers only: `forward` runs the hand-written gfx950 kernels through sm3hip.engine (direct 7x7 stem
+on MFMA, gather-GEMM convolutions with BN-statistics epilogues, fused BN/residual/ReLU, pooling).
 No torchvision dependency.  Both block families run on the engine: BasicBlock (resnet18/34, the reference's
 default architecture) and Bottleneck (resnet50/101/152, and the ResNeXts, whose 3x3 convolution is grouped: `groups`,
 `width_per_group`, csrc/gconv.hip).  The wide ResNets are not implemented: their constructors raise NotImplementedError.

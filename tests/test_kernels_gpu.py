@@ -336,7 +336,9 @@ def test_bn_eval_and_f32_out():
 
 
 @pytest.mark.parametrize("dt", DTYPES, ids=["f32", "bf16"])
-def test_stem_im2col_matches_conv(dt):
+def test_padded_k_stem_gemm_and_wgrad_match_conv(dt):
+    """The 7x7 / stride-2 stem as a gather-GEMM over im2col columns whose K (147) is zero-padded to 192: the forward, and the
+    weight gradient dropping the columns at or beyond w_row_stride."""
     ops = _ops()
     code = ops.dtype_code(dt)
     g = torch.Generator().manual_seed(11)
@@ -346,8 +348,9 @@ def test_stem_im2col_matches_conv(dt):
     ref = F.conv2d(rnd(x, dt).double(), rnd(w, dt).double(), stride=2, padding=3)
     Ho, Wo = ref.shape[2:]
     Kpad = 192
-    cols = torch.empty(N * Ho * Wo, Kpad, dtype=dt, device=dev())
-    ops.stem_im2col(code, x.to(dev()), cols, Kpad)
+    # rows (n, oy, ox), columns (ky, kx, c): the order w.permute(0, 2, 3, 1) gives the weights; zeros from 147 to Kpad
+    patches = F.unfold(x, 7, padding=3, stride=2).reshape(N, 3, 7, 7, Ho * Wo).permute(0, 4, 2, 3, 1).reshape(-1, 147)
+    cols = F.pad(patches, (0, Kpad - 147)).to(dt).to(dev())
     wm = w.permute(0, 2, 3, 1).contiguous().reshape(64, 147).to(dev())
     wf = torch.empty(64, Kpad, dtype=dt, device=dev())
     ops.weight_prep(code, wm, 64, 1, 147, wf, Kpad, None)
