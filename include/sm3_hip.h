@@ -650,6 +650,20 @@ int sm3_p2p_free(void* ptr);
 int sm3_p2p_allreduce_f64(double* buf, int n, void* const* mailboxes, int rank, int world, uint64_t seq, int* err_flag,
                           double timeout_s, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Weighted k-nearest-neighbour vote (replaces KNNOnlineEvaluator.predict, src/models/evaluator.py:56-84, from the
+ * similarity matrix on: topk -> gather -> exp(s / T) -> one-hot weighted sum).
+ *   S [B, ld] f32, of which columns [0, N) are valid; targets [N, L] int32, one class per label; class_offsets: HOST array
+ *   [L + 1], 0 = off[0] < off[1] < ... < off[L] <= 256, label l owning classes [0, off[l+1] - off[l]).
+ *   scores [B, off[L]]: scores[b, off[l] + c] = sum of expf(s_j / T) over the k largest s_j of row b whose neighbour j has
+ *   class c for label l (a target outside its label's range casts no vote).  nbr_idx / nbr_sim [B, k] (nullable): the
+ *   neighbours' indices and similarities in rank order.
+ * Equal similarities rank by the lower index first.  Each label's votes are added in rank order by one thread, no atomics:
+ * the result is a function of the inputs alone.  1 <= k <= min(N, 1024), 1 <= L <= 16, T > 0, B, N, ld < 2^31.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_knn_vote(const float* S, int64_t B, int64_t N, int64_t ld, const int32_t* targets, int L, const int32_t* class_offsets,
+                 int k, float temperature, float* scores, int32_t* nbr_idx, float* nbr_sim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

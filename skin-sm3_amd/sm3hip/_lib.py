@@ -163,6 +163,7 @@ SIGNATURES = {
     "sm3_gconv_dgrad": [_I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sm3_gconv_wgrad_slabs": [_I, _I, _I, _I, _I],
     "sm3_gconv_wgrad_det": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "sm3_knn_vote": [_P, _L, _L, _L, _P, _I, _P, _I, _F, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -1560,3 +1560,43 @@ def token_heads(dtype, x, W, bias, token_of, l2_norm, out, B, S, D, T):
         raise ValueError("token_heads: at most 8 tokens")
     check(_lib.load().sm3_token_heads(dtype, _ptr(x), _ptr(W), _ptr(bias), _ptr(token_of), int(bool(l2_norm)), _ptr(out),
                                       B, S, D, T, _stream()), "sm3_token_heads")
+
+
+# ------------------------------------------------------------------------------------------
+# weighted k-nearest-neighbour vote (KNNOnlineEvaluator, sm3hip/knn.py)
+# ------------------------------------------------------------------------------------------
+KNN_MAX_K, KNN_MAX_LABELS, KNN_MAX_CLASSES = 1024, 16, 256
+
+
+def knn_vote(S, n_valid, targets, class_offsets, k, temperature, scores, nbr_idx=None, nbr_sim=None):
+    """scores[b, off[l] + c] = sum of exp(s / T) over the k largest S[b, :n_valid] whose neighbour has class c for label l
+    (sm3_knn_vote); nbr_idx / nbr_sim [B, k] (optional): the neighbours in rank order, equal similarities lower index
+    first.  targets [N, L] int32, class_offsets: L + 1 host ints."""
+    if S.dim() != 2 or targets.dim() != 2 or scores.dim() != 2:
+        raise ValueError("knn_vote: S [B, ld], targets [N, L] and scores [B, sum C] are 2-D")
+    B, ld = S.shape
+    N, L = targets.shape
+    offs = [int(o) for o in class_offsets]
+    if not 1 <= L <= KNN_MAX_LABELS:
+        raise ValueError(f"knn_vote: {L} labels, 1 to {KNN_MAX_LABELS} supported")
+    if len(offs) != L + 1 or offs[0] != 0 or any(b <= a for a, b in zip(offs, offs[1:])):
+        raise ValueError("knn_vote: class_offsets must be L + 1 increasing ints from 0")
+    if offs[-1] > KNN_MAX_CLASSES:
+        raise ValueError(f"knn_vote: {offs[-1]} classes over all labels, at most {KNN_MAX_CLASSES}")
+    if not 1 <= n_valid <= ld or N != n_valid or max(B, ld) > 0x7fffffff:
+        raise ValueError(f"knn_vote: {n_valid} valid columns of S [{B}, {ld}] against {N} targets")
+    if not 1 <= k <= min(n_valid, KNN_MAX_K):
+        raise ValueError(f"knn_vote: k = {k} outside [1, min(N = {n_valid}, {KNN_MAX_K})]")
+    if not temperature > 0 or temperature == float("inf"):
+        raise ValueError("knn_vote: temperature must be positive and finite")
+    if tuple(scores.shape) != (B, offs[-1]):
+        raise ValueError(f"knn_vote: scores must be [{B}, {offs[-1]}]")
+    for t, n in ((nbr_idx, "nbr_idx"), (nbr_sim, "nbr_sim")):
+        if t is not None and tuple(t.shape) != (B, k):
+            raise ValueError(f"knn_vote: {n} must be [{B}, {k}]")
+    _chk(S, torch.float32, "S"); _chk(targets, torch.int32, "targets"); _chk(scores, torch.float32, "scores")
+    _chk(nbr_idx, torch.int32, "nbr_idx"); _chk(nbr_sim, torch.float32, "nbr_sim")
+    off = (C.c_int32 * (L + 1))(*offs)
+    with _prof("knn_vote", 0.0, 4.0 * 4 * B * n_valid):  # bytes: the 4 select passes over S
+        check(_lib.load().sm3_knn_vote(_ptr(S), B, n_valid, ld, _ptr(targets), L, off, int(k), float(temperature),
+                                       _ptr(scores), _ptr(nbr_idx), _ptr(nbr_sim), _stream()), "sm3_knn_vote")
