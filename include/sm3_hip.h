@@ -553,7 +553,8 @@ int sm3_mlc_add_ln_fwd(const float* a, const float* b, const float* gamma, const
                        uint32_t seed, float* out, float* stats, int64_t rows, int D, void* stream);
 int sm3_mlc_add_ln_bwd(const float* dout, const float* a, const float* b, const float* stats, const float* gamma, float p,
                        uint32_t seed, float* da, float* db, float* dgamma, float* dbeta, int64_t rows, int D, void* stream);
-/* h = relu(y + bias) [rows, N], hd = dropout_p(h); backward dh = dhd * mask/(1-p) * (h > 0), dbias += column sums */
+/* h = relu(y + bias) [rows, N], hd = dropout_p(h); backward dh = dhd * mask/(1-p) * (h > 0), dbias += column sums (atomics;
+ * dbias nullable: dh only, the bias gradient then being sm3_mlc_colsum_det of dh) */
 int sm3_mlc_bias_relu_drop_fwd(const float* y, const float* bias, float p, uint32_t seed, float* h, float* hd, int64_t rows,
                                int N, void* stream);
 int sm3_mlc_relu_drop_bwd(const float* dhd, const float* h, float p, uint32_t seed, float* dh, float* dbias, int64_t rows,
@@ -578,6 +579,34 @@ int sm3_mlc_heads_bwd(const float* dlogits, const float* x, const float* W, cons
 int sm3_mlc_kmeans_assign(const float* emb, const float* centroids, int64_t* assign, float* sums, int* counts, int N, int D,
                           int K, void* stream);
 int sm3_mlc_kmeans_update(float* centroids, const float* sums, const int* counts, int K, int D, void* stream);
+
+/* ---- the same sums as functions of their inputs: no float atomics (what sm3hip/mlc.py runs unless SM3_WGRAD_DET=0) -----
+ * Every float sum over rows below has ONE order, which depends on the shapes alone: the rows are cut into slabs of
+ * SM3_MLC_SLAB_ROWS consecutive rows; within slab j four partial sums start at 0 and add the rows j*256 + t, + 4, + 8, ...
+ * (t = 0..3) in ascending order, the slab's value being (p0 + p1) + (p2 + p3); then out = out + (((q0 + q1) + q2) + ... + q_{m-1})
+ * over the m = ceil(rows / 256) slabs in index order.  With m > 1 the slab values are stored plainly into `slabs` (room for
+ * m * W floats, W the number of output elements named at each entry point) and a second launch adds them; with m = 1 slabs may
+ * be null.  Outputs are accumulated into (+=), as by the atomic forms.  Arguments are checked before anything is launched. */
+#define SM3_MLC_SLAB_ROWS 256
+/* db[g*N + c] += sum_{r < rows} dy[g*rows + r][c] for g < groups (W = groups * N): the bias gradient of a Linear, or of
+ * `groups` Linears over consecutive row blocks of one dy (the v4 label projectors) */
+int sm3_mlc_colsum_det(const float* dy, float* db, float* slabs, int64_t rows, int N, int groups, void* stream);
+/* sm3_mlc_add_ln_bwd with dgamma[d] += sum_r dout[r][d] * xhat[r][d] and dbeta[d] += sum_r dout[r][d] in the order above
+ * (W = 2 * D; slab j holds dgamma's D values, then dbeta's).  da / db are those of sm3_mlc_add_ln_bwd, bit for bit. */
+int sm3_mlc_add_ln_bwd_det(const float* dout, const float* a, const float* b, const float* stats, const float* gamma, float p,
+                           uint32_t seed, float* da, float* db, float* dgamma, float* dbeta, float* slabs, int64_t rows, int D,
+                           void* stream);
+/* sm3_mlc_heads_bwd with the sums over the batch in the order above, the rows being the B samples:
+ * dW[t][d] += dlogits[b][t] * x[b, tok t][d] * inv[b][tok t] (inv = 1 / |x[b, s]| when l2_norm, else the factor is absent)
+ * and dbias[t] += dlogits[b][t] (dbias nullable).  dx is that of sm3_mlc_heads_bwd, bit for bit.  work: room for
+ * B * S + m * W floats, W = Tn * D + (dbias ? Tn : 0) -- the per-token 1/|x| first, then the slabs (never null). */
+int sm3_mlc_heads_bwd_det(const float* dlogits, const float* x, const float* W, const int* token_of, int l2_norm, float* dx,
+                          float* dW, float* dbias, float* work, int B, int S, int D, int Tn, int label_major, void* stream);
+/* sm3_mlc_kmeans_assign with the M-step sums in the order above over the N embeddings: sums[k][d] += emb[n][d] for the n with
+ * assign[n] = k, ascending n within each lane of a slab (W = K * D); assign (first maximum) and the integer counts as there.
+ * sums and counts required; sm3_mlc_kmeans_update then runs on them unchanged. */
+int sm3_mlc_kmeans_assign_det(const float* emb, const float* centroids, int64_t* assign, float* sums, int* counts, float* slabs,
+                              int N, int D, int K, void* stream);
 
 /* ---- grouped 1x1 GEMM: the per-label layers of the BN-MLP label projectors (reference src/models/projector.py:5-62, built by
  * tools/mlc_train.py:352-361 and tools/mlc_eval.py:344-353 for --mlc-proj v1 / v2 / v3), exact f32 (SM3_F32 only) ------------

@@ -173,7 +173,8 @@ __global__ __launch_bounds__(256) void mlc_add_ln_fwd_kernel(const float* __rest
     }
 }
 
-// ds = gradient w.r.t. (a + dropout(b)); da = ds; db = mask/(1-p) * ds; dgamma/dbeta += (atomics)
+// ds = gradient w.r.t. (a + dropout(b)); da = ds; db = mask/(1-p) * ds; dgamma/dbeta += (atomics; both null: the fixed-order
+// form sm3_mlc_add_ln_bwd_det sums them after this kernel)
 template <int NV>
 __global__ __launch_bounds__(256) void mlc_add_ln_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ a,
                                                              const float* __restrict__ b, const float* __restrict__ stats,
@@ -194,8 +195,10 @@ __global__ __launch_bounds__(256) void mlc_add_ln_bwd_kernel(const float* __rest
         const float x = a[o] + (k ? b[o] * scale : 0.f);
         xh[n] = (x - mean) * rstd;
         const float go = dout[o];
-        atomicAdd(&dgamma[d], go * xh[n]);
-        atomicAdd(&dbeta[d], go);
+        if (dgamma) {
+            atomicAdd(&dgamma[d], go * xh[n]);
+            atomicAdd(&dbeta[d], go);
+        }
         g[n] = go * gamma[d];
         s1 += g[n];
         s2 += g[n] * xh[n];
@@ -222,7 +225,7 @@ __global__ __launch_bounds__(256) void mlc_bias_relu_drop_fwd_kernel(const float
         hd[i] = (p <= 0.f || keep(seed, (uint32_t)i, p)) ? v * scale : 0.f;
     }
 }
-// dh = dhd * mask/(1-p) * (h > 0); dbias += column sums
+// dh = dhd * mask/(1-p) * (h > 0); dbias += column sums (atomics; dbias null: dh only)
 __global__ __launch_bounds__(256) void mlc_relu_drop_bwd_kernel(const float* __restrict__ dhd, const float* __restrict__ h,
                                                                 float p, uint32_t seed, float* __restrict__ dh,
                                                                 float* __restrict__ dbias, int64_t n, int N) {
@@ -230,7 +233,7 @@ __global__ __launch_bounds__(256) void mlc_relu_drop_bwd_kernel(const float* __r
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float v = (h[i] > 0.f && (p <= 0.f || keep(seed, (uint32_t)i, p))) ? dhd[i] * scale : 0.f;
         dh[i] = v;
-        if (v != 0.f) atomicAdd(&dbias[i % N], v);
+        if (dbias && v != 0.f) atomicAdd(&dbias[i % N], v);
     }
 }
 // db[c] += sum_r dy[r][c]   (bias gradient of a Linear): one block per 64 columns x row chunk
@@ -278,7 +281,8 @@ __global__ __launch_bounds__(256) void mlc_ce_kernel(const float* __restrict__ l
 }
 
 // ---- prototype heads backward: out[b][t] = <xn[b][tok(t)], W[t]> (+bias), xn = x or x/|x| ------------------------------
-// grid = B; dx [B][S][D] (written), dW [Tn][D] += , dbias [Tn] += (nullable)
+// grid = B; dx [B][S][D] (written), dW [Tn][D] += , dbias [Tn] += (nullable).  dW null: no atomics, and inv_out (when
+// l2_norm) receives the per-token 1/|x| [B][S] for the fixed-order sums of sm3_mlc_heads_bwd_det
 #define XR(ptr, s_) ROWP(ptr, s_, D)
 // forward: out[b][t] = <xn[b][tok(t)], W[t]> + bias[t]  (sm3_token_heads with row strides, fp32)
 __global__ __launch_bounds__(256) void mlc_heads_fwd_kernel(const float* __restrict__ x, const float* __restrict__ W,
@@ -317,8 +321,8 @@ __global__ __launch_bounds__(256) void mlc_heads_fwd_kernel(const float* __restr
 __global__ __launch_bounds__(256) void mlc_heads_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ x,
                                                             const float* __restrict__ W, const int* __restrict__ token_of,
                                                             int l2_norm, float* __restrict__ dx, float* __restrict__ dW,
-                                                            float* __restrict__ dbias, int S, int D, int Tn, int64_t ss,
-                                                            int64_t ts) {
+                                                            float* __restrict__ dbias, float* __restrict__ inv_out, int S,
+                                                            int D, int Tn, int64_t ss, int64_t ts) {
     __shared__ float inv_norm[kMaxS], dots[kMaxS];
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* gl = dlogits + (int64_t)b * Tn;
@@ -335,6 +339,7 @@ __global__ __launch_bounds__(256) void mlc_heads_bwd_kernel(const float* __restr
         for (int o = 1; o < 32; o <<= 1) q += __shfl_xor(q, o, 64);
         if (s < S && part == 0) inv_norm[s] = 1.f / fmaxf(sqrtf(q), 1e-12f);
         __syncthreads();
+        if (inv_out && tid < S) inv_out[(int64_t)b * S + tid] = inv_norm[tid];
     }
     // v[s][d] = sum_{t: tok(t) = s} dlogits[t] W[t][d]  -> gradient w.r.t. the (normalised) token
     for (int o = tid; o < S * D; o += 256) {
@@ -344,12 +349,14 @@ __global__ __launch_bounds__(256) void mlc_heads_bwd_kernel(const float* __restr
             if (token_of[t] == s) v += gl[t] * W[(int64_t)t * D + d];
         XR(dx, s)[d] = v;
     }
-    for (int o = tid; o < Tn * D; o += 256) {  // dW[t][d] += dlogits[t] * xn[tok(t)][d]
-        const int t = o / D, d = o - t * D, s = token_of[t];
-        const float g = gl[t];
-        if (g != 0.f) atomicAdd(&dW[o], g * XR(x, s)[d] * inv_norm[s]);
+    if (dW) {
+        for (int o = tid; o < Tn * D; o += 256) {  // dW[t][d] += dlogits[t] * xn[tok(t)][d]
+            const int t = o / D, d = o - t * D, s = token_of[t];
+            const float g = gl[t];
+            if (g != 0.f) atomicAdd(&dW[o], g * XR(x, s)[d] * inv_norm[s]);
+        }
+        if (dbias && tid < Tn) atomicAdd(&dbias[tid], gl[tid]);
     }
-    if (dbias && tid < Tn) atomicAdd(&dbias[tid], gl[tid]);
     if (l2_norm) {  // dx = inv * (v - xn (xn . v))
         __syncthreads();
         const int s = tid >> 5, part = tid & 31;
@@ -409,6 +416,129 @@ __global__ __launch_bounds__(64) void mlc_kmeans_update_kernel(float* __restrict
     const float inv = 1.f / fmaxf(sqrtf(q), 1e-12f);
     for (int d = lane; d < D; d += 64) cent[(int64_t)k * D + d] *= inv;
 }
+
+// ---- fixed-order column sums: the float sums over rows of the head step and of k-means, without atomics --------------
+// out[e] += sum over the rows r of v(r, e), for the columns e < W of a virtual matrix whose entries each form computes:
+//   kColsum  e = (g, c), v = dy[g*rows + r][c]                              (Linear bias gradients, `groups` blocks of rows)
+//   kLnGrad  e <  D: v = dout[r][e] * xhat[r][e];  e >= D: v = dout[r][e - D] (LayerNorm dgamma | dbeta)
+//   kHeads   e <  Tn*D: (t, d), v = dlogits[r][t] * x[row(r, tok t)][d] * inv[r][tok t];  e >= Tn*D: v = dlogits[r][e - Tn*D]
+//   kKmeans  e = (k, d), v = emb[r][d] for the rows with assign[r] == k (the other rows add nothing)
+// Order, a function of (rows, e) alone: the rows are cut into slabs of kSlabRows; in slab j four partial sums start at 0 and
+// add the rows j*kSlabRows + t, + 4, + 8, ... (t = 0..3) in ascending order, the slab's value is (p0 + p1) + (p2 + p3); then
+// out[e] = out[e] + (((q0 + q1) + q2) + ... + q_{m-1}) over the m slabs in index order.  A single slab is added by
+// mlc_colslab_kernel itself, more are stored plainly into slabs[j][e] and mlc_slab_finish_kernel adds them.
+constexpr int kSlabRows = SM3_MLC_SLAB_ROWS;
+enum { kColsum = 0, kLnGrad = 1, kHeads = 2, kKmeans = 3 };
+
+struct ColArgs {
+    const float* v0;         // dy | dout | dlogits | emb
+    const float* v1;         // -  | a    | x       | -
+    const float* v2;         // -  | b    | inv (nullable: l2_norm off) | -
+    const float* stats;      // LayerNorm (mean, rstd) per row
+    const int* tok;          // heads: token of each prototype
+    const int64_t* assign;   // k-means
+    int64_t rows, W;
+    int N, S, Tn;            // N: columns per group (colsum), D otherwise
+    int64_t ss, ts;          // heads: token row strides
+    float p;
+    uint32_t seed;
+};
+
+template <int MODE>
+__device__ __forceinline__ float col_partial(const ColArgs& A, int64_t e, int64_t r, int64_t r1) {
+    float s = 0.f;
+    if constexpr (MODE == kColsum) {
+        const int64_t g = e / A.N, c = e - g * A.N;
+        const float* src = A.v0 + g * A.rows * A.N + c;
+        for (; r < r1; r += 4) s += src[r * A.N];
+    } else if constexpr (MODE == kLnGrad) {
+        const int D = A.N;
+        const bool gam = e < D;
+        const int d = gam ? (int)e : (int)(e - D);
+        const float scale = A.p > 0.f ? 1.f / (1.f - A.p) : 1.f;
+        for (; r < r1; r += 4) {
+            const int64_t o = r * D + d;
+            const float go = A.v0[o];
+            if (gam) {  // xhat as mlc_add_ln_bwd_kernel recomputes it
+                const bool k = A.p <= 0.f || keep(A.seed, (uint32_t)o, A.p);
+                const float x = A.v1[o] + (k ? A.v2[o] * scale : 0.f);
+                s += go * ((x - A.stats[2 * r]) * A.stats[2 * r + 1]);
+            } else {
+                s += go;
+            }
+        }
+    } else if constexpr (MODE == kHeads) {
+        const int D = A.N;
+        const int64_t nw = (int64_t)A.Tn * D;
+        if (e < nw) {
+            const int t = (int)(e / D), d = (int)(e - (int64_t)t * D), tk = A.tok[t];
+            for (; r < r1; r += 4) {
+                const float iv = A.v2 ? A.v2[r * A.S + tk] : 1.f;
+                s += A.v0[r * A.Tn + t] * A.v1[(r * A.ss + (int64_t)tk * A.ts) * D + d] * iv;
+            }
+        } else {
+            const int t = (int)(e - nw);
+            for (; r < r1; r += 4) s += A.v0[r * A.Tn + t];
+        }
+    } else {
+        const int D = A.N;
+        const int64_t k = e / D, d = e - k * D;
+        for (; r < r1; r += 4)
+            if (A.assign[r] == k) s += A.v0[r * D + d];
+    }
+    return s;
+}
+
+// grid (ceil(W / 64), slabs); 64 columns x 4 row lanes
+template <int MODE>
+__global__ __launch_bounds__(256) void mlc_colslab_kernel(const ColArgs A, float* __restrict__ slabs, float* __restrict__ out0,
+                                                          float* __restrict__ out1, int64_t split) {
+    __shared__ float red[4][64];
+    const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+    const int64_t e = (int64_t)blockIdx.x * 64 + lane;
+    const int64_t r0 = (int64_t)blockIdx.y * kSlabRows, r1 = r0 + kSlabRows < A.rows ? r0 + kSlabRows : A.rows;
+    red[t][lane] = e < A.W ? col_partial<MODE>(A, e, r0 + t, r1) : 0.f;
+    __syncthreads();
+    if (t == 0 && e < A.W) {
+        const float v = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+        if (gridDim.y == 1) {
+            float* o = e < split ? out0 + e : out1 + (e - split);
+            *o = *o + v;
+        } else {
+            slabs[(int64_t)blockIdx.y * A.W + e] = v;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void mlc_slab_finish_kernel(const float* __restrict__ slabs, int nslab, int64_t W,
+                                                              float* __restrict__ out0, float* __restrict__ out1, int64_t split) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= W) return;
+    float v = slabs[e];
+    for (int j = 1; j < nslab; ++j) v += slabs[(int64_t)j * W + e];
+    float* o = e < split ? out0 + e : out1 + (e - split);
+    *o = *o + v;
+}
+
+inline int64_t colslab_count(int64_t rows) { return (rows + kSlabRows - 1) / kSlabRows; }
+
+// the launches of one fixed-order column sum (arguments checked by the caller)
+template <int MODE>
+int colslab_run(const ColArgs& A, float* slabs, float* out0, float* out1, int64_t split, hipStream_t st) {
+    const int64_t m = colslab_count(A.rows);
+    hipLaunchKernelGGL(mlc_colslab_kernel<MODE>, dim3((unsigned)((A.W + 63) / 64), (unsigned)m), dim3(256), 0, st, A, slabs, out0,
+                       out1, split);
+    SM3_CHECK_LAUNCH();
+    if (m > 1) {
+        hipLaunchKernelGGL(mlc_slab_finish_kernel, dim3((unsigned)((A.W + 255) / 256)), dim3(256), 0, st, slabs, (int)m, A.W, out0,
+                           out1, split);
+        SM3_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// slab count and columns within what one launch can address
+inline bool colslab_fits(int64_t rows, int64_t W) { return rows > 0 && W > 0 && colslab_count(rows) <= 65535 && (W + 63) / 64 <= 0x7fffffff; }
 
 inline unsigned ew_grid(int64_t n) {
     int64_t g = (n + 255) / 256;
@@ -472,7 +602,7 @@ extern "C" int sm3_mlc_bias_relu_drop_fwd(const float* y, const float* bias, flo
 }
 extern "C" int sm3_mlc_relu_drop_bwd(const float* dhd, const float* h, float p, uint32_t seed, float* dh, float* dbias,
                                      int64_t rows, int N, void* stream) {
-    if (!dhd || !h || !dh || !dbias || rows <= 0 || N <= 0 || p < 0.f || p >= 1.f) return SM3_EINVAL;
+    if (!dhd || !h || !dh || rows <= 0 || N <= 0 || p < 0.f || p >= 1.f) return SM3_EINVAL;
     hipLaunchKernelGGL(mlc_relu_drop_bwd_kernel, dim3(ew_grid(rows * N)), dim3(256), 0, (hipStream_t)stream, dhd, h, p, seed, dh,
                        dbias, rows * N, N);
     SM3_CHECK_LAUNCH();
@@ -510,7 +640,7 @@ extern "C" int sm3_mlc_heads_bwd(const float* dlogits, const float* x, const flo
         return SM3_EINVAL;
     MLC_STRIDES();
     hipLaunchKernelGGL(mlc_heads_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, dlogits, x, W, token_of, l2_norm, dx,
-                       dW, dbias, S, D, Tn, ss, ts);
+                       dW, dbias, nullptr, S, D, Tn, ss, ts);
     SM3_CHECK_LAUNCH();
     return 0;
 }
@@ -527,4 +657,56 @@ extern "C" int sm3_mlc_kmeans_update(float* centroids, const float* sums, const 
     hipLaunchKernelGGL(mlc_kmeans_update_kernel, dim3(K), dim3(64), 0, (hipStream_t)stream, centroids, sums, counts, D);
     SM3_CHECK_LAUNCH();
     return 0;
+}
+
+
+// ---- fixed-order forms (no float atomics; orders in include/sm3_hip.h) -------------------------------------------------
+extern "C" int sm3_mlc_colsum_det(const float* dy, float* db, float* slabs, int64_t rows, int N, int groups, void* stream) {
+    if (!dy || !db || N <= 0 || groups <= 0 || !colslab_fits(rows, (int64_t)groups * N)) return SM3_EINVAL;
+    if (colslab_count(rows) > 1 && !slabs) return SM3_EINVAL;
+    ColArgs A = {};
+    A.v0 = dy; A.rows = rows; A.N = N; A.W = (int64_t)groups * N;
+    return colslab_run<kColsum>(A, slabs, db, db, A.W, (hipStream_t)stream);
+}
+extern "C" int sm3_mlc_add_ln_bwd_det(const float* dout, const float* a, const float* b, const float* stats, const float* gamma,
+                                      float p, uint32_t seed, float* da, float* db, float* dgamma, float* dbeta, float* slabs,
+                                      int64_t rows, int D, void* stream) {
+    if (!dout || !a || !b || !stats || !gamma || !da || !db || !dgamma || !dbeta || D <= 0 || D > 4096 || p < 0.f || p >= 1.f ||
+        !colslab_fits(rows, 2 * (int64_t)D) || (rows + 3) / 4 > 0x7fffffff)
+        return SM3_EINVAL;
+    if (colslab_count(rows) > 1 && !slabs) return SM3_EINVAL;
+    hipLaunchKernelGGL(D <= 1024 ? mlc_add_ln_bwd_kernel<16> : mlc_add_ln_bwd_kernel<64>, dim3((unsigned)((rows + 3) / 4)), dim3(256),
+                       0, (hipStream_t)stream, dout, a, b, stats, gamma, p, seed, da, db, nullptr, nullptr, rows, D);
+    SM3_CHECK_LAUNCH();
+    ColArgs A = {};
+    A.v0 = dout; A.v1 = a; A.v2 = b; A.stats = stats; A.rows = rows; A.N = D; A.W = 2 * (int64_t)D; A.p = p; A.seed = seed;
+    return colslab_run<kLnGrad>(A, slabs, dgamma, dbeta, D, (hipStream_t)stream);
+}
+extern "C" int sm3_mlc_heads_bwd_det(const float* dlogits, const float* x, const float* W, const int* token_of, int l2_norm,
+                                     float* dx, float* dW, float* dbias, float* work, int B, int S, int D, int Tn, int label_major,
+                                     void* stream) {
+    if (!dlogits || !x || !W || !token_of || !dx || !dW || !work || B <= 0 || S <= 0 || S > kMaxS || D <= 0 || Tn <= 0 ||
+        Tn > 256 || !colslab_fits(B, (int64_t)Tn * D + Tn))
+        return SM3_EINVAL;
+    MLC_STRIDES();
+    float* inv = l2_norm ? work : nullptr;
+    hipLaunchKernelGGL(mlc_heads_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, dlogits, x, W, token_of, l2_norm, dx,
+                       nullptr, nullptr, inv, S, D, Tn, ss, ts);
+    SM3_CHECK_LAUNCH();
+    ColArgs A = {};
+    A.v0 = dlogits; A.v1 = x; A.v2 = inv; A.tok = token_of; A.rows = B; A.N = D; A.S = S; A.Tn = Tn; A.ss = ss; A.ts = ts;
+    A.W = (int64_t)Tn * D + (dbias ? Tn : 0);
+    return colslab_run<kHeads>(A, work + (int64_t)B * S, dW, dbias, (int64_t)Tn * D, (hipStream_t)stream);
+}
+extern "C" int sm3_mlc_kmeans_assign_det(const float* emb, const float* centroids, int64_t* assign, float* sums, int* counts,
+                                         float* slabs, int N, int D, int K, void* stream) {
+    if (!emb || !centroids || !assign || !sums || !counts || D <= 0 || K <= 0 || !colslab_fits(N, (int64_t)K * D))
+        return SM3_EINVAL;
+    if (colslab_count(N) > 1 && !slabs) return SM3_EINVAL;
+    hipLaunchKernelGGL(mlc_kmeans_assign_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, emb, centroids, assign,
+                       nullptr, counts, N, D, K);
+    SM3_CHECK_LAUNCH();
+    ColArgs A = {};
+    A.v0 = emb; A.assign = assign; A.rows = N; A.N = D; A.W = (int64_t)K * D;
+    return colslab_run<kKmeans>(A, slabs, sums, sums, A.W, (hipStream_t)stream);
 }

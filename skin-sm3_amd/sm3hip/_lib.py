@@ -156,6 +156,10 @@ SIGNATURES = {
     "sm3_mlc_heads_bwd": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "sm3_mlc_kmeans_assign": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "sm3_mlc_kmeans_update": [_P, _P, _P, _I, _I, _P],
+    "sm3_mlc_colsum_det": [_P, _P, _P, _L, _I, _I, _P],
+    "sm3_mlc_add_ln_bwd_det": [_P, _P, _P, _P, _P, _F, _U, _P, _P, _P, _P, _P, _L, _I, _P],
+    "sm3_mlc_heads_bwd_det": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sm3_mlc_kmeans_assign_det": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "sm3_grouped_gemm": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "sm3_grouped_wgrad_det": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "sm3_gconv_weight_prep": [_I, _P, _P, _P, _I, _I, _P, _P],

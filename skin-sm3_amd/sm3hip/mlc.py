@@ -24,7 +24,13 @@ attention over the 8 tokens, the two residual LayerNorms with their dropouts, bi
 and the pseudo-label cross-entropy are csrc/heads_train.hip.  fp32 throughout, as the reference runs this part
 (mlc_train.py:294-295).  One torch.autograd.Function spans the heads, so the frozen-extractor default
 (mlc_train.py:347-348) and --finetune-backbone (gradient into the HIP encoders through sm3hip.bridge) both work, and the
-caller keeps the reference's literal loop (CrossEntropyLoss on the predictions, torch.optim.AdamW)."""
+caller keeps the reference's literal loop (CrossEntropyLoss on the predictions, torch.optim.AdamW).
+
+A step is a function of its inputs: every float sum over rows (weight gradients: sm3_conv_wgrad_det; bias, LayerNorm and
+prototype gradients and the k-means cluster sums: the sm3_mlc_*_det forms) has a fixed order, so two runs give the same bits.
+SM3_WGRAD_DET=0 (read when the heads are built, or per clustering) runs the float-atomic forms instead, for A/B measurement."""
+import os
+
 import torch
 
 from . import _lib, ops
@@ -35,6 +41,32 @@ _P = ops._ptr
 
 def _st():
     return ops._stream()
+
+
+SLAB_ROWS = 256  # SM3_MLC_SLAB_ROWS: rows per slab of the fixed-order column sums
+
+
+def _det_default():
+    return os.environ.get("SM3_WGRAD_DET", "1") != "0"
+
+
+def _nslab(rows):
+    return (rows + SLAB_ROWS - 1) // SLAB_ROWS
+
+
+def colsum_det(dy, db, groups=1, slabs=None):
+    """db[g, :] += column sums of the g-th of `groups` row blocks of dy [groups * rows, N], fixed order (sm3_mlc_colsum_det)."""
+    rows, N = dy.shape[0] // groups, dy.shape[1]
+    if rows * groups != dy.shape[0] or db.numel() != groups * N:
+        raise ValueError("colsum_det: dy [groups * rows, N], db [groups * N]")
+    if slabs is None and _nslab(rows) > 1:
+        slabs = torch.empty(_nslab(rows) * groups * N, dtype=torch.float32, device=dy.device)
+    check(_lib.load().sm3_mlc_colsum_det(_P(dy), _P(db), _P(slabs), rows, N, groups, _st()), "sm3_mlc_colsum_det")
+
+
+def heads_bwd_work(B, S, D, T, bias):
+    """Floats of workspace sm3_mlc_heads_bwd_det needs."""
+    return B * S + _nslab(B) * (T * D + (T if bias else 0))
 
 
 def _projector_kind(projectors):
@@ -84,6 +116,8 @@ class MLCHeads:
             raise NotImplementedError("one dropout rate for the whole layer, as nn.TransformerEncoderLayer builds it")
         self.sizes = [l.weight.shape[0] for l in model.prototypes]
         self.has_pbias = model.prototypes[0].bias is not None
+        self.det = _det_default()  # fixed-order sums (SM3_WGRAD_DET=0: the float-atomic kernels)
+        self._ws = None            # the slab workspace of the backward, grown on demand and reused by every site of a step
 
     def proj_params(self):
         m = self.model
@@ -122,19 +156,44 @@ class MLCHeads:
         ops.conv_gemm(ops.fwd_desc(SM3_F32, rows, 1, 1, K, N, 1, 1, 0), x, w, out, addend, None)
         return out
 
-    @staticmethod
-    def _wgrad(x, dy, dw):
+    def _work(self, n, dev):
+        """fp32 workspace of at least n floats, shared by the sequential launches of a backward on one stream."""
+        if self._ws is None or self._ws.numel() < n or self._ws.device != dev:
+            self._ws = torch.empty(max(n, 4), dtype=torch.float32, device=dev)
+        return self._ws
+
+    def _wgrad(self, x, dy, dw):
         """dw[N, K] += dy[rows, N]^T @ x[rows, K]."""
         rows, K = x.shape
-        ops.conv_wgrad(ops.fwd_desc(SM3_F32, rows, 1, 1, K, dy.shape[1], 1, 1, 0), x, dy, dw)
+        desc = ops.fwd_desc(SM3_F32, rows, 1, 1, K, dy.shape[1], 1, 1, 0)
+        if not self.det:
+            ops.conv_wgrad(desc, x, dy, dw)
+            return
+        n = dy.shape[1] * K
+        cap = ops.grouped_wgrad_slab_cap(rows, n)
+        # (capacity 1: one slice adds its tiles to dw itself and the slab buffer is never written)
+        ops.conv_wgrad_det(desc, x, dy, dw, dw if cap == 1 else self._work(cap * n, x.device), cap)
 
     def _bias(self, y, bias, ones):
         rows, N = y.shape
         ops.bn_act(SM3_F32, y, ones[:N], bias, None, False, y, rows, N)
 
-    @staticmethod
-    def _colsum(dy, db):
-        check(_lib.load().sm3_mlc_colsum(_P(dy), _P(db), dy.shape[0], dy.shape[1], _st()), "sm3_mlc_colsum")
+    def _colsum(self, dy, db, groups=1):
+        if not self.det:
+            check(_lib.load().sm3_mlc_colsum(_P(dy), _P(db), dy.shape[0], dy.shape[1], _st()), "sm3_mlc_colsum")
+            return
+        rows, N = dy.shape[0] // groups, dy.shape[1]
+        colsum_det(dy, db, groups, self._work(_nslab(rows) * groups * N, dy.device) if _nslab(rows) > 1 else None)
+
+    def _add_ln_bwd(self, dout, a, b, stats, gamma, p, seed, da, db, dgamma, dbeta):
+        R, D = dout.shape
+        if not self.det:
+            check(_lib.load().sm3_mlc_add_ln_bwd(_P(dout), _P(a), _P(b), _P(stats), _P(gamma), p, seed, _P(da), _P(db), _P(dgamma),
+                                                 _P(dbeta), R, D, _st()), "sm3_mlc_add_ln_bwd")
+            return
+        ws = self._work(_nslab(R) * 2 * D, dout.device)
+        check(_lib.load().sm3_mlc_add_ln_bwd_det(_P(dout), _P(a), _P(b), _P(stats), _P(gamma), p, seed, _P(da), _P(db), _P(dgamma),
+                                                 _P(dbeta), _P(ws), R, D, _st()), "sm3_mlc_add_ln_bwd_det")
 
     # ---- BN-MLP label projectors (v1 / v2 / v3) --------------------------------------------------------------------
     def _mlp_banks(self):
@@ -327,15 +386,27 @@ class MLCHeads:
         dev = dlogits.device
         z = lambda t: torch.zeros_like(t, dtype=torch.float32)
         skip = {id(q) for q in self.proj_params()} if self.kind == "mlp" else set()  # (filled by _mlp_backward, or None)
+        pbias = None
+        if self.kind == "v4" and self.det:  # the S label biases: one grouped column sum into a bank, handed out as views
+            pbias = torch.zeros(S, D, dtype=torch.float32, device=dev)
+            skip |= {id(l[0].bias) for l in m.projectors.projectors}
         g = {id(q): (None if id(q) in skip else z(q)) for q in self.params()}
+        if pbias is not None:
+            for s, l in enumerate(m.projectors.projectors):
+                g[id(l[0].bias)] = pbias[s]
         G = lambda q: g[id(q)]
         dlogits = dlogits.contiguous().float()
         T = sv["wp"].shape[0]
         dx2 = torch.empty(R, D, dtype=torch.float32, device=dev)
         dwp = torch.zeros(T, D, dtype=torch.float32, device=dev)
         dbp = torch.zeros(T, dtype=torch.float32, device=dev) if self.has_pbias else None
-        check(lib.sm3_mlc_heads_bwd(_P(dlogits), _P(sv["x2"]), _P(sv["wp"]), _P(sv["tok"]), int(bool(m.l2_norm)), _P(dx2),
-                                    _P(dwp), _P(dbp), B, S, D, T, 1, _st()), "sm3_mlc_heads_bwd")
+        if self.det:
+            ws = self._work(heads_bwd_work(B, S, D, T, self.has_pbias), dev)
+            check(lib.sm3_mlc_heads_bwd_det(_P(dlogits), _P(sv["x2"]), _P(sv["wp"]), _P(sv["tok"]), int(bool(m.l2_norm)), _P(dx2),
+                                            _P(dwp), _P(dbp), _P(ws), B, S, D, T, 1, _st()), "sm3_mlc_heads_bwd_det")
+        else:
+            check(lib.sm3_mlc_heads_bwd(_P(dlogits), _P(sv["x2"]), _P(sv["wp"]), _P(sv["tok"]), int(bool(m.l2_norm)), _P(dx2),
+                                        _P(dwp), _P(dbp), B, S, D, T, 1, _st()), "sm3_mlc_heads_bwd")
         off = 0
         for l, n in zip(m.prototypes, self.sizes):
             G(l.weight).copy_(dwp[off:off + n])
@@ -344,23 +415,23 @@ class MLCHeads:
             off += n
         # LayerNorm 2 (+ dropout2): d(x1 + drop(fo))
         dx1, dfo = torch.empty_like(dx2), torch.empty_like(dx2)
-        check(lib.sm3_mlc_add_ln_bwd(_P(dx2), _P(sv["x1"]), _P(sv["fo"]), _P(sv["st2"]), _P(sa.norm2.weight.detach()), p,
-                                     seed + 4, _P(dx1), _P(dfo), _P(G(sa.norm2.weight)), _P(G(sa.norm2.bias)), R, D, _st()),
-              "sm3_mlc_add_ln_bwd")
+        self._add_ln_bwd(dx2, sv["x1"], sv["fo"], sv["st2"], sa.norm2.weight.detach(), p, seed + 4, dx1, dfo, G(sa.norm2.weight),
+                         G(sa.norm2.bias))
         # feed-forward
         self._colsum(dfo, G(sa.linear2.bias))
         self._wgrad(sv["hd"], dfo, G(sa.linear2.weight))
         dhd = self._gemm(dfo, sa.linear2.weight.detach().t().contiguous())
         dh = torch.empty_like(dhd)
-        check(lib.sm3_mlc_relu_drop_bwd(_P(dhd), _P(sv["h"]), p, seed + 3, _P(dh), _P(G(sa.linear1.bias)), R, dh.shape[1],
-                                        _st()), "sm3_mlc_relu_drop_bwd")
+        check(lib.sm3_mlc_relu_drop_bwd(_P(dhd), _P(sv["h"]), p, seed + 3, _P(dh), _P(None if self.det else G(sa.linear1.bias)), R,
+                                        dh.shape[1], _st()), "sm3_mlc_relu_drop_bwd")
+        if self.det:
+            self._colsum(dh, G(sa.linear1.bias))
         self._wgrad(sv["x1"], dh, G(sa.linear1.weight))
         self._gemm(dh, sa.linear1.weight.detach().t().contiguous(), out=dx1, addend=dx1)
         # LayerNorm 1 (+ dropout1): d(x0 + drop(o))
         dx0, do = torch.empty_like(dx2), torch.empty_like(dx2)
-        check(lib.sm3_mlc_add_ln_bwd(_P(dx1), _P(sv["x0"]), _P(sv["o"]), _P(sv["st1"]), _P(sa.norm1.weight.detach()), p,
-                                     seed + 2, _P(dx0), _P(do), _P(G(sa.norm1.weight)), _P(G(sa.norm1.bias)), R, D, _st()),
-              "sm3_mlc_add_ln_bwd")
+        self._add_ln_bwd(dx1, sv["x0"], sv["o"], sv["st1"], sa.norm1.weight.detach(), p, seed + 2, dx0, do, G(sa.norm1.weight),
+                         G(sa.norm1.bias))
         # attention
         self._colsum(do, G(att.out_proj.bias))
         self._wgrad(sv["a"], do, G(att.out_proj.weight))
@@ -384,9 +455,12 @@ class MLCHeads:
                 for q, t in zip(self.proj_params(), pg):
                     g[id(q)] = t
             return [g[id(q)] for q in self.params()], dfeats
+        if pbias is not None:
+            self._colsum(dx0, pbias, groups=S)
         for s, l in enumerate(m.projectors.projectors):
             blk = dx0[s * B:(s + 1) * B]
-            self._colsum(blk, G(l[0].bias))
+            if pbias is None:
+                self._colsum(blk, G(l[0].bias))
             self._wgrad(sv["feats"], blk, G(l[0].weight))
             if need_dfeats:
                 wt = l[0].weight.detach().t().contiguous()
@@ -431,10 +505,11 @@ def heads_forward(model, feats, seed=None):
 
 # ---- pseudo-labels: spherical k-means over the memory bank (mlc_train.py:116-189) -----------------------------------
 @torch.no_grad()
-def spherical_kmeans(embeddings, K, iters=10, generator=None):
+def spherical_kmeans(embeddings, K, iters=10, generator=None, det=None):
     """embeddings [N, D] fp32 CUDA (one label's memory bank) -> (centroids [K, D], assignments [N] int64): random
     samples as the initial centroids, `iters` rounds of (assign by largest dot product; centroid = L2-normalised mean of
-    its members), then the final assignment."""
+    its members), then the final assignment.  det (default: SM3_WGRAD_DET != 0): the cluster sums in a fixed order
+    (sm3_mlc_kmeans_assign_det), so the centroids and assignments are a function of the bank and the generator."""
     if not embeddings.is_cuda or embeddings.dtype != torch.float32:
         raise ValueError("spherical_kmeans: fp32 CUDA embeddings")
     emb = embeddings.contiguous()
@@ -447,12 +522,18 @@ def spherical_kmeans(embeddings, K, iters=10, generator=None):
     sums = torch.empty(K, D, dtype=torch.float32, device=emb.device)
     counts = torch.empty(K, dtype=torch.int32, device=emb.device)
     lib = _lib.load()
+    det = _det_default() if det is None else bool(det)
+    slabs = torch.empty(_nslab(N) * K * D, dtype=torch.float32, device=emb.device) if det and _nslab(N) > 1 else None
     with ops.stream_scope():
         for _ in range(iters):
             sums.zero_()
             counts.zero_()
-            check(lib.sm3_mlc_kmeans_assign(_P(emb), _P(cent), _P(assign), _P(sums), _P(counts), N, D, K, _st()),
-                  "sm3_mlc_kmeans_assign")
+            if det:
+                check(lib.sm3_mlc_kmeans_assign_det(_P(emb), _P(cent), _P(assign), _P(sums), _P(counts), _P(slabs), N, D, K, _st()),
+                      "sm3_mlc_kmeans_assign_det")
+            else:
+                check(lib.sm3_mlc_kmeans_assign(_P(emb), _P(cent), _P(assign), _P(sums), _P(counts), N, D, K, _st()),
+                      "sm3_mlc_kmeans_assign")
             check(lib.sm3_mlc_kmeans_update(_P(cent), _P(sums), _P(counts), K, D, _st()), "sm3_mlc_kmeans_update")
         check(lib.sm3_mlc_kmeans_assign(_P(emb), _P(cent), _P(assign), None, None, N, D, K, _st()), "sm3_mlc_kmeans_assign")
     return cent, assign
