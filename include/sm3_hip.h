@@ -367,6 +367,18 @@ int sm3_stem_wgrad_bn16(int dtype, const void* ximg, const void* dz, const void*
                         const float* gamma, const double* global_sums, double count, const double* local_sums,
                         float* dgamma, float* dbeta, float* dw, float* dw_slabs, int N, int H, int W, int views,
                         void* stream);
+/* Stem data gradient (ABI 9, additive): the gradient of the fp32 NCHW image batch,
+ *   dx[n, c, iy, ix] = sum over the taps of (iy, ix) of dxo[n, oy, ox, co] * w[co][kh][kw][c],   dx: [N][3][H][W] fp32,
+ * with dxo the stem BatchNorm's input gradient computed on the fly from dz, xo, mean, invstd, gamma, global_sums and count
+ * exactly as sm3_stem_wgrad_bn computes it (all-zero global_sums: frozen statistics, dxo = gamma*invstd*dz); dxo is not
+ * written to HBM.  w_master: the fp32 [64][7][7][3] weight (rounded to dtype in LDS as sm3_stem_weight_prep rounds it);
+ * dz, xo: [N*Ho*Wo, 64] dtype, 16-byte aligned.  Gather form: every element of dx is written once, in a fixed summation
+ * order (no atomics: the result is a function of the inputs).  Any geometry sm3_stem_conv_fwd accepts; views as
+ * sm3_stem_wgrad_bn.  The same kernel serves both image paths: the image gradient passes straight through the 16-bit
+ * rounding of sm3_stem_image_prep. */
+int sm3_stem_dgrad_bn(int dtype, const void* dz, const void* xo, const float* mean, const float* invstd, const float* gamma,
+                      const double* global_sums, double count, const float* w_master, float* dx, int N, int H, int W,
+                      int views, void* stream);
 /* argmax (nullable): [N,Ho,Wo,C] bytes, window position kh*3+kw of the first maximum in scan order (ATen's tie rule) */
 int sm3_maxpool3x3s2_fwd(int dtype, const void* x, void* y, uint8_t* argmax, int N, int H, int W, int C, void* stream);
 /* dx[n,iy,ix,c] = sum of dy over the windows whose recorded argmax is (iy,ix); gather form, no atomics */

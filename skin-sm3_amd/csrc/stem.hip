@@ -901,6 +901,202 @@ __global__ void stem_weight_prep_f32_kernel(const float* __restrict__ w, float* 
     out[i] = v;
 }
 
+// ---- data gradient (input images), gather form ---------------------------------------------------------------------
+//   dx[n, c, iy, ix] = sum_{kh, kw, co} dxo[n, oy, ox, co] w[co][kh][kw][c],   iy = 2 oy - 3 + kh,  ix = 2 ox - 3 + kw
+// Write iy = 2 i + r, ix = 2 j + q (i < Ho, j < Wo, r, q in {0, 1}).  Then the taps of pixel (i, j, r, q) are the dxo
+// pixels oy = i + 2 - t, ox = j + 2 - s for t, s in 0..3, with kh = 2 t + r - 1, kw = 2 s + q - 1 (a negative kh / kw is
+// no tap: 4 x 4, 4 x 3, 3 x 4 or 3 x 3 of them by parity).  As a GEMM per 2 x 2 pixel group (i, j):
+//   M = the groups of a row pair (j), N = 16 >= 12 = (r, q, c), K = (t, s, co) = 1024,
+//   A[j][(t, s, co)] = dxo[i + 2 - t][j + 2 - s][co],  B[(t, s, co)][(r, q, c)] = w[co][2t + r - 1][2s + q - 1][c].
+// A is a sliding window over four dxo rows: a tile (one image, DG_J column pairs, DG_RC row pairs) keeps a ring of four
+// staged dxo rows in LDS and stages ONE new row per row pair, with the BatchNorm-backward apply of the weight-gradient
+// kernels (dxo = A dz - B xo + C per channel) on the way in; dxo never reaches HBM.  B, the filter bank in this order, is
+// built in LDS from the fp32 master weight by every (persistent) workgroup, rounded as sm3_stem_weight_prep rounds it.
+// Each output element is written once, by the workgroup that owns its 2 x 2 group, from a K loop in a fixed order: dx is a
+// function of the inputs (no atomics; the same bits for any batch position or grid).
+constexpr int DG_J = 64;             // column pairs per tile: 4 waves x 16 MFMA rows
+constexpr int DG_COLS = DG_J + 3;    // staged dxo columns: ox = j0 - 1 .. j0 + DG_J + 1
+constexpr int DG_RC = 16;            // row pairs per tile
+constexpr int DG_OUT = 2 * 3 * 2 * DG_J;  // floats of the staged output tile [r][c][2 DG_J]
+
+template <typename T>
+struct DgradCfg {
+    static constexpr int ES = sizeof(T) == 2 ? 2 : 4;
+    static constexpr int VEC = 16 / ES;             // co per 16-byte chunk
+    static constexpr int RP = 64 + VEC;             // LDS pitch (elements) of a staged pixel / a bank column: bank spread
+    static constexpr int CPR = 64 / VEC;            // chunks per staged pixel
+    static constexpr int NCH = DG_COLS * CPR;       // chunks per staged row
+    static constexpr int SLOTS = (NCH + 255) / 256; // chunks per thread
+    static constexpr int RING = DG_COLS * RP * ES;  // bytes per ring row
+    static constexpr int BANK = 16 * 16 * RP * ES;  // bytes of the bank [(t, s)][n][RP]
+    static constexpr int LDS = 4 * RING + BANK + DG_OUT * 4 + 3 * 64 * 4;
+};
+
+struct StemDgradParams {
+    const char* dz;
+    const char* xo;
+    const float *mean, *invstd, *gamma;  // [views][64], [views][64], [64] (nullable)
+    const double* gsums;                 // [views][128]
+    const float* w;                      // fp32 master [64][7][7][3]
+    float* dx;                           // [N][3][H][W]
+    double inv_count;
+    int H, W, Ho, Wo, xblocks, rchunks, n_per_view;
+    long tiles;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const StemDgradParams p) {
+    using C = DgradCfg<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem_dg[];
+    char* sRing = smem_dg;                                           // [4][DG_COLS][RP] T
+    char* sBank = smem_dg + 4 * C::RING;                             // [16 (t, s)][16 n][RP] T
+    float* sOut = reinterpret_cast<float*>(sBank + C::BANK);         // [2 r][3 c][2 DG_J]
+    float(*sCoef)[64] = reinterpret_cast<float(*)[64]>(sOut + DG_OUT);  // [A | B | C][64]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+    for (int e = tid; e < 16 * 16 * 64; e += 256) {  // the bank, in the B order of the header comment
+        const int co = e & 63, n = (e >> 6) & 15, ts = e >> 10, t = ts >> 2, s = ts & 3;
+        float v = 0.f;
+        if (n < 12) {
+            const int r = n / 6, q = (n / 3) & 1, c = n % 3;
+            const int kh = 2 * t + r - 1, kw = 2 * s + q - 1;
+            if (kh >= 0 && kw >= 0) v = p.w[co * 147 + (kh * 7 + kw) * 3 + c];
+        }
+        char* dst = sBank + ((ts * 16 + n) * C::RP + co) * C::ES;
+        if constexpr (C::ES == 4) *reinterpret_cast<float*>(dst) = v;
+        else *reinterpret_cast<uint16_t*>(dst) = (uint16_t)pack2<T>(v, 0.f);
+    }
+
+    // 16-bit modes: this lane's 32 B fragments (the same for every row pair) in registers, so that the MFMA loop reads only
+    // the A fragments from LDS -- with both, LDS bandwidth bounded the loop (32 bytes per lane and MFMA)
+    constexpr int NBR = C::ES == 2 ? 32 : 1;
+    uint4 breg[NBR];
+    __syncthreads();
+    if constexpr (C::ES == 2) {
+        const int m = lane & 15, kg = lane >> 4;
+#pragma unroll
+        for (int ts = 0; ts < 16; ++ts)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+                breg[ts * 2 + cb] = *reinterpret_cast<const uint4*>(sBank + ((ts * 16 + m) * C::RP + 32 * cb + 8 * kg) * 2);
+    }
+
+    uint4 gz[C::SLOTS], gx[C::SLOTS];
+    int cur_view = -1;
+    for (long tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
+        const int xb = (int)(tile % p.xblocks);
+        const long rr = tile / p.xblocks;
+        const int rc = (int)(rr % p.rchunks), n = (int)(rr / p.rchunks);
+        const int j0 = xb * DG_J, i0 = rc * DG_RC, i1 = min(p.Ho, i0 + DG_RC);
+        const int view = n / p.n_per_view;
+        if (view != cur_view) {  // block-uniform
+            cur_view = view;
+            __syncthreads();  // nobody still stages with the previous coefficients
+            if (tid < 64) {   // the arithmetic of stem_wgrad_kernel
+                const int c = tid;
+                const float is = p.invstd[view * 64 + c];
+                const float g = p.gamma ? p.gamma[c] : 1.f;
+                const float k0c = g * is;
+                const float k1c = (float)(p.gsums[view * 128 + c] * p.inv_count);
+                const float qc = k0c * is * (float)(p.gsums[view * 128 + 64 + c] * p.inv_count);
+                sCoef[0][c] = k0c;
+                sCoef[1][c] = qc;
+                sCoef[2][c] = qc * p.mean[view * 64 + c] - k0c * k1c;
+            }
+            __syncthreads();
+        }
+        // dxo row oy -> registers (zeros outside the map) ...
+        auto load_row = [&](int oy) {
+#pragma unroll
+            for (int k = 0; k < C::SLOTS; ++k) {
+                const int ch = tid + 256 * k, cidx = ch / C::CPR, cc = ch - cidx * C::CPR;
+                const int ox = j0 - 1 + cidx;
+                const bool ok = ch < C::NCH && (unsigned)oy < (unsigned)p.Ho && (unsigned)ox < (unsigned)p.Wo;
+                const long off = ((((long)n * p.Ho + oy) * p.Wo + ox) * 64 + cc * C::VEC) * C::ES;
+                gz[k] = ok ? ldg16<true>(p.dz + off) : make_uint4(0, 0, 0, 0);
+                gx[k] = ok ? ldg16<true>(p.xo + off) : make_uint4(0, 0, 0, 0);
+            }
+        };
+        // ... -> BatchNorm-backward apply -> ring slot (oy + 1) & 3
+        auto store_row = [&](int oy) {
+            char* row = sRing + ((oy + 1) & 3) * C::RING;
+#pragma unroll
+            for (int k = 0; k < C::SLOTS; ++k) {
+                const int ch = tid + 256 * k, cidx = ch / C::CPR, cc = ch - cidx * C::CPR;
+                if (ch >= C::NCH) continue;
+                const int ox = j0 - 1 + cidx;
+                uint4 out = make_uint4(0, 0, 0, 0);
+                if ((unsigned)oy < (unsigned)p.Ho && (unsigned)ox < (unsigned)p.Wo) {
+                    float g[C::VEC], xv[C::VEC];
+                    unpack16<T>(gz[k], g);
+                    unpack16<T>(gx[k], xv);
+#pragma unroll
+                    for (int e = 0; e < C::VEC; ++e) {
+                        const int c = cc * C::VEC + e;
+                        g[e] = sCoef[0][c] * g[e] - sCoef[1][c] * xv[e] + sCoef[2][c];
+                    }
+                    out = pack16<T>(g);
+                }
+                *reinterpret_cast<uint4*>(row + (cidx * C::RP + cc * C::VEC) * C::ES) = out;
+            }
+        };
+        for (int oy = i0 - 1; oy <= i0 + 1; ++oy) {
+            load_row(oy);
+            store_row(oy);
+        }
+        load_row(i0 + 2);
+        for (int i = i0; i < i1; ++i) {
+            store_row(i + 2);
+            __syncthreads();  // rows i - 1 .. i + 2 staged; the previous row pair's output tile has been written out
+            if (i + 1 < i1) load_row(i + 3);  // lands during this row pair's MFMA loop
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            const int m = lane & 15, kg = lane >> 4;
+            const int cbase = 16 * wave + m + 3;  // staged column of ox = j + 2 - s is cbase - s
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const char* arow = sRing + ((i + 3 - t) & 3) * C::RING;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const char* a0 = arow + (cbase - s) * C::RP * C::ES;
+                    const char* b0 = sBank + ((t * 4 + s) * 16 + m) * C::RP * C::ES;
+                    if constexpr (C::ES == 2) {
+#pragma unroll
+                        for (int cb = 0; cb < 2; ++cb) {  // K = 32 co per MFMA: lane group kg supplies co 32 cb + 8 kg ..
+                            const int co = 32 * cb + 8 * kg;
+                            sm3conv::mma_frag16<T>(*reinterpret_cast<const uint4*>(a0 + co * 2), breg[(t * 4 + s) * 2 + cb],
+                                                   acc);
+                        }
+                    } else {
+#pragma unroll
+                        for (int cb = 0; cb < 4; ++cb) {  // 16 co per four MFMAs: lane group kg supplies co 16 cb + 4 kg ..
+                            const int co = 16 * cb + 4 * kg;
+                            const float4 a = *reinterpret_cast<const float4*>(a0 + co * 4);
+                            const float4 b = *reinterpret_cast<const float4*>(b0 + co * 4);
+                            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+                            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+                            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+                            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+                        }
+                    }
+                }
+            }
+            // D[row 4 kg + v][col m]: column pair 16 wave + 4 kg + v, output column m = (r, q, c)
+            if (m < 12) {
+                const int r = m / 6, q = (m / 3) & 1, c = m % 3;
+#pragma unroll
+                for (int v = 0; v < 4; ++v) sOut[(r * 3 + c) * (2 * DG_J) + 2 * (16 * wave + 4 * kg + v) + q] = acc[v];
+            }
+            __syncthreads();  // output tile complete; everyone is done reading ring row i - 1
+            for (int e = tid; e < DG_OUT; e += 256) {
+                const int rcix = e / (2 * DG_J), x = e - rcix * (2 * DG_J);
+                const int r = rcix / 3, c = rcix - 3 * r;
+                const int iy = 2 * i + r, ix = 2 * j0 + x;
+                if (iy < p.H && ix < p.W) p.dx[(((long)n * 3 + c) * p.H + iy) * p.W + ix] = sOut[e];
+            }
+        }
+    }
+}
+
 int stem_geometry(int N, int H, int W, int& Ho, int& Wo, int& xblocks, long& tiles) {
     if (N <= 0 || H <= 0 || W <= 0) return SM3_EINVAL;
     Ho = (H - 1) / 2 + 1;
@@ -1086,4 +1282,46 @@ extern "C" int sm3_stem_wgrad_bn16(int dtype, const void* ximg, const void* dz, 
         hipLaunchKernelGGL(stem_wgrad16_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, pp);
     SM3_CHECK_LAUNCH();
     return dw_slabs ? sm3_slab_reduce(dw_slabs, (int)grid, 64 * 147, dw, 1, stream) : 0;
+}
+
+template <typename T>
+static int stem_dgrad_launch(const StemDgradParams& p, hipStream_t stream) {
+    static std::atomic<int> done[32];  // dynamic LDS above 64 KB needs the function attribute: once per device
+    const int bytes = DgradCfg<T>::LDS;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 31) dev = 0;
+    if (!done[dev].load(std::memory_order_acquire)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_dgrad_kernel<T>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return (int)e;
+        done[dev].store(1, std::memory_order_release);
+    }
+    // persistent: 2 workgroups per CU in the 16-bit modes (79 KB of LDS each), 1 in the exact-f32 mode (146 KB)
+    const long cap = sizeof(T) == 2 ? 512 : 256;
+    const unsigned grid = (unsigned)(p.tiles < cap ? p.tiles : cap);
+    hipLaunchKernelGGL(stem_dgrad_kernel<T>, dim3(grid), dim3(256), bytes, stream, p);
+    SM3_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sm3_stem_dgrad_bn(int dtype, const void* dz, const void* xo, const float* mean, const float* invstd,
+                                 const float* gamma, const double* global_sums, double count, const float* w_master,
+                                 float* dx, int N, int H, int W, int views, void* stream) {
+    if (!dz || !xo || !mean || !invstd || !global_sums || !w_master || !dx || !(count > 0) || views < 1 || N % views)
+        return SM3_EINVAL;
+    if (dtype != SM3_BF16 && dtype != SM3_F16 && dtype != SM3_F32) return SM3_EDTYPE;
+    if ((((uintptr_t)dz) | ((uintptr_t)xo)) & 15) return SM3_EALIGN;
+    StemDgradParams p;
+    long tiles;
+    if (int rc = stem_geometry(N, H, W, p.Ho, p.Wo, p.xblocks, tiles)) return rc;
+    p.xblocks = (p.Wo + DG_J - 1) / DG_J;
+    p.rchunks = (p.Ho + DG_RC - 1) / DG_RC;
+    p.tiles = (long)N * p.rchunks * p.xblocks;
+    p.dz = (const char*)dz; p.xo = (const char*)xo;
+    p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.gsums = global_sums; p.w = w_master; p.dx = dx;
+    p.inv_count = 1.0 / count;
+    p.H = H; p.W = W; p.n_per_view = N / views;
+    if (dtype == SM3_BF16) return stem_dgrad_launch<bf16_t>(p, (hipStream_t)stream);
+    if (dtype == SM3_F16) return stem_dgrad_launch<f16_t>(p, (hipStream_t)stream);
+    return stem_dgrad_launch<float>(p, (hipStream_t)stream);
 }

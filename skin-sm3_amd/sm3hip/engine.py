@@ -1033,7 +1033,10 @@ class SM3Engine:
         return dz2, nrows // V, ds
 
     def _wgrad(self, cu, r, dxo):
-        """Weight gradient of a unit, accumulated into the flat gradient buffer on the lane's stream."""
+        """Weight gradient of a unit, accumulated into the flat gradient buffer on the lane's stream (nothing in a
+        data-only backward)."""
+        if self.__dict__.get("_data_only"):
+            return
         gw = self._g(cu.name + ".weight")
         if cu.groups > 1:
             n = gw.numel()
@@ -1259,12 +1262,17 @@ class SM3Engine:
         ops.avgpool_fwd(self.dtype, cur, feat_f32, feat_t, N, h * w, plan.out_dim)
         if save is not None:
             save.append({"plan": plan, "stem": recs[0], "stem_hw": (Ho, Wo), "pool_hw": (Hp, Wp), "argmax": amax,
-                         "blocks": block_recs, "N": N, "last_hw": (h, w), "V": self._V})
+                         "blocks": block_recs, "N": N, "last_hw": (h, w), "V": self._V, "img_hw": (H, W)})
 
-    def encoder_backward(self, ctx, dfeat, last_view=True, taps=None):
+    def encoder_backward(self, ctx, dfeat, last_view=True, taps=None, dx_out=None, params=True):
         """dfeat: [N,2048] `dtype` gradient of the pooled features.  On the last view of a step each stage's
         parameter gradients are final once its blocks are done: grad_ready fires per stage so the caller can
         start that bucket's all-reduce while earlier stages are still computing.
+        dx_out: an fp32 [N, 3, H, W] tensor that receives the gradient of the input images (sm3_stem_dgrad_bn, after the
+        stem BatchNorm-backward sums); None: no image gradient, the launches are those of the parameter backward alone.
+        params=False: a data-only backward -- no weight-gradient launch, no slab reduction, no grad_ready notification; the
+        data gradients are bit-identical to those of the full backward.  BatchNorm parameter gradients that come out of a
+        data-gradient launch (the apply passes) are still accumulated into the flat gradient buffer.
         taps (tests): a dict that receives taps["g"][i], a clone of the gradient arriving at the boundary of
         encoder_forward's taps["x"][i] (complete: every addend is in), and taps["g_pre_relu"][i]: whether that
         gradient is already masked by the ReLU of the block that produced taps["x"][i], i.e. taken with respect to
@@ -1272,6 +1280,14 @@ class SM3Engine:
         gradient (False); an inner boundary whose gradient came out of a data-gradient launch with the previous
         block's BatchNorm-backward phase 1 in its epilogue is masked (True), one that was summed without it is not;
         the max-pool output has no ReLU after it (False).  None: nothing is recorded."""
+        prev = self.__dict__.get("_data_only", False)
+        self._data_only = prev or not params
+        try:
+            self._encoder_backward(ctx, dfeat, last_view, taps, dx_out)
+        finally:
+            self._data_only = prev
+
+    def _encoder_backward(self, ctx, dfeat, last_view, taps, dx_out):
         plan, N = ctx["plan"], ctx["N"]
         h, w = ctx["last_hw"]
         dcur = torch.empty(N * h * w, plan.out_dim, dtype=self.tdt, device=dfeat.device)
@@ -1383,7 +1399,7 @@ class SM3Engine:
                 self._notify(stage + ".", stage + ".")
         if taps is not None:
             taps["g"][0] = dcur.clone()  # the gradient of the max-pool output (not masked: maxpool_bn_bwd applies the mask)
-        # maxpool -> stem BN/ReLU -> stem weight gradient (no data gradient: the image needs none)
+        # maxpool -> stem BN/ReLU -> stem weight gradient (and, when asked for, the image gradient)
         Ho, Wo = ctx["stem_hw"]
         rs = ctx["stem"]
         # maxpool gradient gather + recomputed ReLU mask + BatchNorm-backward phase 1 in one pass
@@ -1395,10 +1411,16 @@ class SM3Engine:
         # BatchNorm-backward apply inside the stem weight gradient's operand load: d(conv1 output) never reaches HBM
         lsums, gsums, count = self._bn_backward_sums(rs, part, prow)
         bn = rs.bu.name
-        wg = ops.stem_wgrad_bn16 if isinstance(rs.x_in, ops.StemImage) else ops.stem_wgrad_bn
-        wg(self.dtype, rs.x_in, dz, rs.xo, rs.mean, rs.invstd, self._p(bn + ".weight"), gsums, count,
-           lsums, self._g(bn + ".weight"), self._g(bn + ".bias"), self._g(rs.cu.name + ".weight"), views=rs.V,
-           slabs=self._work("stem_slabs", ops.STEM_WGRAD_SLABS * 64 * 147) if self.det_wgrad else None)
+        if not self._data_only:
+            wg = ops.stem_wgrad_bn16 if isinstance(rs.x_in, ops.StemImage) else ops.stem_wgrad_bn
+            wg(self.dtype, rs.x_in, dz, rs.xo, rs.mean, rs.invstd, self._p(bn + ".weight"), gsums, count,
+               lsums, self._g(bn + ".weight"), self._g(bn + ".bias"), self._g(rs.cu.name + ".weight"), views=rs.V,
+               slabs=self._work("stem_slabs", ops.STEM_WGRAD_SLABS * 64 * 147) if self.det_wgrad else None)
+        if dx_out is not None:
+            # the same BatchNorm-backward apply, on the fly, then the transposed 7x7 / stride-2 convolution in gather form;
+            # the gradient passes straight through the 16-bit rounding of the images (StemImage), as a cast does
+            ops.stem_dgrad_bn(self.dtype, dz, rs.xo, rs.mean, rs.invstd, self._p(bn + ".weight"), gsums, count,
+                              self._p(rs.cu.name + ".weight"), dx_out, views=rs.V)
         if last_view:
             self._notify(plan.prefix + "conv1", plan.prefix + "layer1.")
 
@@ -1537,13 +1559,24 @@ class SM3Engine:
         return zs, feats, saved
 
     def _notify(self, plan_prefix_first, plan_prefix_last):
-        if self.grad_ready is not None:
+        if self.grad_ready is not None and not self.__dict__.get("_data_only"):
             self.grad_ready(plan_prefix_first, plan_prefix_last)
 
-    def backward(self, saved, dz, dfeat=None):
+    def backward(self, saved, dz, dfeat=None, want_dx=None, params=True):
         """dz: dict name -> [2B,proj] `dtype` gradient of the projector outputs; dfeat: optional dict branch ->
         [2B,2048] `dtype` gradient arriving at the pooled features directly.  Accumulates parameter gradients
-        into the flat gradient buffer (self.store.flat_g)."""
+        into the flat gradient buffer (self.store.flat_g).
+        want_dx: optional dict branch -> (view 0?, view 1?): the image gradients to compute; returns dict branch ->
+        [dx_view0, dx_view1] (fp32 NCHW, None where not asked for).  A pair batch (both views in one encoder pass) gives
+        one [2B, 3, H, W] gradient, split into its views.  params=False: data-only (see encoder_backward)."""
+        prev = self.__dict__.get("_data_only", False)
+        self._data_only = prev or not params
+        try:
+            return self._backward(saved, dz, dfeat, want_dx)
+        finally:
+            self._data_only = prev
+
+    def _backward(self, saved, dz, dfeat, want_dx):
         B = saved["B"]
         dfe = {}
         dev = self.store.flat_p.device
@@ -1590,17 +1623,34 @@ class SM3Engine:
             if "meta" in dz and saved.get("meta") is not None:
                 self.projector_backward(saved["meta"], dz["meta"])
             self._notify(self.meta.prefix, self.meta.prefix)
+        dxs = {}
         for key, (plan, proj) in self.branches.items():
+            want = tuple(want_dx.get(key, (False, False))) if want_dx is not None else (False, False)
+            dxs[key] = [None, None]
             if len(saved[key]["enc"]) == 1:  # both views went through as one batch
                 with self.lane(key, streams):
-                    self.encoder_backward(saved[key]["enc"][0], dfe[key], last_view=True)
+                    ec = saved[key]["enc"][0]
+                    dxo = None
+                    if any(want):
+                        H, W = ec["img_hw"]
+                        dxo = self._share(torch.empty(ec["N"], 3, H, W, dtype=torch.float32, device=dev), streams)
+                    self.encoder_backward(ec, dfe[key], last_view=True, dx_out=dxo)
                     saved[key]["enc"][0] = None
+                if dxo is not None:  # split the pair batch back into its views
+                    dxs[key] = [dxo[:B] if want[0] else None, dxo[B:] if want[1] else None]
                 continue
             for v in (1, 0):
                 with self.lane(key, streams):
-                    self.encoder_backward(saved[key]["enc"][v], dfe[key][v * B:(v + 1) * B], last_view=(v == 0))
+                    ec = saved[key]["enc"][v]
+                    dxo = None
+                    if want[v]:
+                        H, W = ec["img_hw"]
+                        dxo = self._share(torch.empty(ec["N"], 3, H, W, dtype=torch.float32, device=dev), streams)
+                        dxs[key][v] = dxo
+                    self.encoder_backward(ec, dfe[key][v * B:(v + 1) * B], last_view=(v == 0), dx_out=dxo)
                     saved[key]["enc"][v] = None  # free the view's activations as soon as it is done
         self._join(streams)
+        return dxs
 
     def encoder_only(self, branch, x, train, want_grad):
         """One encoder call (SimCLRSkinV3.extract / a bare ResNet forward): fp32 features [N,2048] and the

@@ -1228,6 +1228,32 @@ def stem_wgrad_bn16(dtype, img, dz, xo, mean, invstd, gamma, gsums, count, lsums
                                               _ptr(slabs), N, H, W, views, _stream()), "sm3_stem_wgrad_bn16")
 
 
+def stem_dgrad_bn(dtype, dz, xo, mean, invstd, gamma, gsums, count, w_master, dx, views=1):
+    """Image gradient of the stem (sm3_stem_dgrad_bn): dx [N, 3, H, W] fp32 (written, not accumulated) from the stem
+    BatchNorm's output gradient dz and its saved input xo ([N*Ho*Wo, 64] `dtype`), the BatchNorm-backward apply computed on
+    the fly as in stem_wgrad_bn (gsums all zero: frozen statistics); w_master: the fp32 [64, 3, 7, 7]-sized master weight in
+    [64][kh][kw][c] order."""
+    tdt = TORCH_DTYPE[dtype]
+    _chk(dz, tdt, "dz"); _chk(xo, tdt, "xo"); _chk(dx, torch.float32, "dx"); _chk(w_master, torch.float32, "w")
+    for t in (mean, invstd, gamma):
+        _chk(t, torch.float32)
+    _chk(gsums, torch.float64)
+    if dx.dim() != 4 or dx.shape[1] != 3:
+        raise ValueError("stem_dgrad_bn: dx must be [N, 3, H, W]")
+    N, _, H, W = dx.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if dz.numel() != N * Ho * Wo * 64 or xo.numel() != dz.numel() or w_master.numel() != 64 * 147 or views < 1 or N % views:
+        raise ValueError("stem_dgrad_bn: size mismatch")
+    if mean.numel() < views * 64 or invstd.numel() < views * 64 or gsums.numel() < views * 128 or \
+            (gamma is not None and gamma.numel() < 64):
+        raise ValueError("stem_dgrad_bn: per-channel vector too small")
+    M = N * Ho * Wo
+    with _prof("stem_dgrad_bn", 2.0 * M * 64 * 147, 2.0 * _sz(dtype) * dz.numel() + 4.0 * dx.numel()):
+        check(_lib.load().sm3_stem_dgrad_bn(dtype, _ptr(dz), _ptr(xo), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(gsums),
+                                            float(count), _ptr(w_master), _ptr(dx), N, H, W, views, _stream()),
+              "sm3_stem_dgrad_bn")
+
+
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):
     """Stem weight gradient with bn1's backward apply fused into the operand load (sm3_stem_wgrad_bn; bf16 / fp16 / exact f32).
     slabs: fp32 workspace of STEM_WGRAD_SLABS * 64 * 147 floats -> fixed-order sum instead of float atomics."""
