@@ -705,6 +705,21 @@ int sm3_p2p_allreduce_f64(double* buf, int n, void* const* mailboxes, int rank, 
 int sm3_knn_vote(const float* S, int64_t B, int64_t N, int64_t ld, const int32_t* targets, int L, const int32_t* class_offsets,
                  int k, float temperature, float* scores, int32_t* nbr_idx, float* nbr_sim, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Grad-CAM of an encoder stage (csrc/cam.hip; ABI 9, additive).  A: the stage output [N][h][w][C] (NHWC, `dtype`, post-ReLU);
+ * G: the gradients of T target logits with respect to A, [T][N][h*w][C] `dtype`.
+ * sm3_cam_alpha: alpha [T][N][C] f32 = the mean of G over the h*w positions, added in ascending position order, then divided
+ *   by h*w (HW = h*w).
+ * sm3_cam_maps: low [N][T][h][w] f32 = ReLU(sum_c alpha[t][n][c] * A[n][p][c]) in a fixed channel order; maps [N][T][H][W] f32 =
+ *   low upsampled as F.interpolate(mode="bilinear", align_corners=False) does, then (cam - min) / (1e-7 + max(cam - min)) per
+ *   map.  C a multiple of 8 and A 16-byte aligned (SM3_EALIGN otherwise).
+ * Sizes and dtypes are checked on the host (SM3_EINVAL / SM3_EALIGN / SM3_EDTYPE) before anything is launched.  No atomics:
+ * equal inputs give equal bits whatever the grid and the batch position.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_cam_alpha(int dtype, const void* g, float* alpha, int T, int N, int HW, int C, void* stream);
+int sm3_cam_maps(int dtype, const void* a, const float* alpha, float* low, float* maps, int N, int T, int h, int w, int C, int H,
+                 int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

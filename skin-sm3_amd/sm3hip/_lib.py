@@ -169,6 +169,8 @@ SIGNATURES = {
     "sm3_gconv_wgrad_slabs": [_I, _I, _I, _I, _I],
     "sm3_gconv_wgrad_det": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "sm3_knn_vote": [_P, _L, _L, _L, _P, _I, _P, _I, _F, _P, _P, _P, _P],
+    "sm3_cam_alpha": [_I, _P, _P, _I, _I, _I, _I, _P],
+    "sm3_cam_maps": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 
 _lib = None

@@ -1120,12 +1120,14 @@ class SM3Engine:
                 return False
         return True
 
-    def encoder_forward(self, plan, x, train, feat_f32, feat_t, save=None, views=1, taps=None):
+    def encoder_forward(self, plan, x, train, feat_f32, feat_t, save=None, views=1, taps=None, keep=None):
         """x: NCHW fp32 [N,3,H,W] (as the loader delivers it, tools/backbone_train.py:89-92).
         Writes the pooled features into feat_f32 [N,2048] (fp32) and feat_t (dtype copy, optional).
         views=2: x holds two views back to back (N = 2B), BatchNorm statistics per view.
         taps (tests): a dict that receives taps["x"] = [max-pool output, output of block 0, block 1, ...], clones of the
-        [N*H*W, C] `dtype` maps at every block boundary (views back to back).  None: nothing is recorded."""
+        [N*H*W, C] `dtype` maps at every block boundary (views back to back).  None: nothing is recorded.
+        keep: a dict {"stage": "layer1" ... "layer4"} that receives keep["out"] = (A, h, w), the output of that stage's last
+        block (post-ReLU, [N*h*w, C] `dtype`; the tensor the next block reads, not a copy), with or without `save`."""
         xs = list(x) if isinstance(x, (list, tuple)) else [x]  # the views of the batch, back to back
         if any(t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3 or t.shape != xs[0].shape for t in xs):
             raise ValueError("encoder input must be NCHW float32 with 3 channels")
@@ -1135,11 +1137,16 @@ class SM3Engine:
             x = xs[0]
         self._V = views if train else 1
         try:
-            self._encoder_forward(plan, x, train, feat_f32, feat_t, save, taps)
+            self._encoder_forward(plan, x, train, feat_f32, feat_t, save, taps, keep)
         finally:
             self._V = 1
 
-    def _encoder_forward(self, plan, x, train, feat_f32, feat_t, save, taps=None):
+    @staticmethod
+    def stage_of(blk):
+        """"layer1" ... "layer4": the stage a block of an EncoderPlan belongs to."""
+        return blk["c1"].name.rsplit(".", 3)[-3]
+
+    def _encoder_forward(self, plan, x, train, feat_f32, feat_t, save, taps=None, keep_out=None):
         if self.stem16:
             # 16-bit modes: the images are rounded ONCE (the rounding the stem kernels used to apply per staged tile, forward
             # and again in the weight gradient) into a row-padded 16-bit copy that both kernels stage by LDS-DMA; the views
@@ -1173,6 +1180,11 @@ class SM3Engine:
         if taps is not None:
             taps["x"] = [p.clone()]
         block_recs = []
+        kept = keep = None
+        if keep_out is not None:
+            keep = keep_out["stage"]
+            if keep not in {self.stage_of(b) for b in plan.blocks}:
+                raise ValueError(f"keep: no stage {keep!r} in this encoder")
         # BatchNorm by linearity for conv3 -> bn3 (csrc/linbn.hip) needs two moments of conv3's input y2 per view: sum(y2),
         # which bn2's apply pass adds up on the side (per-block partial rows), and the Gram matrix y2^T y2, one launch of the
         # weight-gradient kernel on y2 alone (plain-store split-K slabs); sm3_linbn_moments adds both up in a fixed order,
@@ -1203,6 +1215,8 @@ class SM3Engine:
                 del y1, idn
                 block_recs.append(br)
                 cur, h, w = y2, h2, w2
+                if keep is not None and self.stage_of(blk) == keep:
+                    kept = (cur, h, w)
                 if taps is not None:
                     taps["x"].append(cur.clone())
                 continue
@@ -1233,6 +1247,8 @@ class SM3Engine:
                 y3, h3, w3 = self.join_fused(blk, br[1], y2, cur, N, h, w, h2, w2, br)
                 block_recs.append(br)
                 cur, h, w = y3, h3, w3
+                if keep is not None and self.stage_of(blk) == keep:
+                    kept = (cur, h, w)
                 if taps is not None:
                     taps["x"].append(cur.clone())
                 continue
@@ -1257,14 +1273,18 @@ class SM3Engine:
                     br[-1].linbn = True  # backward of conv3 -> bn3 by linearity; needs br[1].colsum / .gram (moments of y2)
             block_recs.append(br)
             cur, h, w = y3, h3, w3
+            if keep is not None and self.stage_of(blk) == keep:
+                kept = (cur, h, w)
             if taps is not None:
                 taps["x"].append(cur.clone())
         ops.avgpool_fwd(self.dtype, cur, feat_f32, feat_t, N, h * w, plan.out_dim)
+        if keep_out is not None:
+            keep_out["out"] = kept
         if save is not None:
             save.append({"plan": plan, "stem": recs[0], "stem_hw": (Ho, Wo), "pool_hw": (Hp, Wp), "argmax": amax,
                          "blocks": block_recs, "N": N, "last_hw": (h, w), "V": self._V, "img_hw": (H, W)})
 
-    def encoder_backward(self, ctx, dfeat, last_view=True, taps=None, dx_out=None, params=True):
+    def encoder_backward(self, ctx, dfeat, last_view=True, taps=None, dx_out=None, params=True, stop_at=None):
         """dfeat: [N,2048] `dtype` gradient of the pooled features.  On the last view of a step each stage's
         parameter gradients are final once its blocks are done: grad_ready fires per stage so the caller can
         start that bucket's all-reduce while earlier stages are still computing.
@@ -1279,16 +1299,32 @@ class SM3Engine:
         its pre-ReLU sum (out + identity) rather than its output.  The last block receives the un-masked pooled
         gradient (False); an inner boundary whose gradient came out of a data-gradient launch with the previous
         block's BatchNorm-backward phase 1 in its epilogue is masked (True), one that was summed without it is not;
-        the max-pool output has no ReLU after it (False).  None: nothing is recorded."""
+        the max-pool output has no ReLU after it (False).  None: nothing is recorded.
+        stop_at: a stage name ("layer1" ... "layer3") of an eval-mode context (frozen statistics): the backward stops once the
+        gradient of that stage's output is complete and returns it ([N*h*w, C] `dtype`) -- the stages below and the stem are
+        skipped.  The gradient is taken with respect to the post-ReLU output itself (not masked by its ReLU): the first block
+        of the next stage computes its data gradient without the previous block's BatchNorm-backward phase 1 in the epilogue
+        (the unfused form of that boundary).  Use with params=False."""
         prev = self.__dict__.get("_data_only", False)
         self._data_only = prev or not params
         try:
-            self._encoder_backward(ctx, dfeat, last_view, taps, dx_out)
+            return self._encoder_backward(ctx, dfeat, last_view, taps, dx_out, stop_at)
         finally:
             self._data_only = prev
 
-    def _encoder_backward(self, ctx, dfeat, last_view, taps, dx_out):
+    def _stop_block(self, ctx, stop_at):
+        """Index of the first block after stage `stop_at` (whose input gradient is that stage's output gradient)."""
+        blocks = ctx["plan"].blocks
+        names = [self.stage_of(b) for b in blocks]
+        if stop_at not in names or names[-1] == stop_at:
+            raise ValueError(f"stop_at: {stop_at!r} is not a stage below the last one of this encoder")
+        if not ctx["stem"].frozen_stats:
+            raise NotImplementedError("stop_at: eval-mode (frozen-statistics) contexts only")
+        return max(i for i, n in enumerate(names) if n == stop_at) + 1
+
+    def _encoder_backward(self, ctx, dfeat, last_view, taps, dx_out, stop_at=None):
         plan, N = ctx["plan"], ctx["N"]
+        stop_bi = self._stop_block(ctx, stop_at) if stop_at is not None else -1
         h, w = ctx["last_hw"]
         dcur = torch.empty(N * h * w, plan.out_dim, dtype=self.tdt, device=dfeat.device)
         ops.avgpool_bwd(self.dtype, dfeat, dcur, N, h * w, plan.out_dim)
@@ -1298,6 +1334,7 @@ class SM3Engine:
             taps["g_pre_relu"] = [False] * (len(plan.blocks) + 1)
         for bi in range(len(plan.blocks) - 1, -1, -1):
             blk, br = plan.blocks[bi], ctx["blocks"][bi]
+            unfused_in = bi == stop_bi  # the gradient of this block's input is returned: no previous-block epilogue
             if taps is not None:  # before this block's first kernel, which masks dcur in place when fr is None
                 taps["g"][bi + 1], taps["g_pre_relu"][bi + 1] = dcur.clone(), fr is not None
             if plan.basic:
@@ -1328,7 +1365,7 @@ class SM3Engine:
                                           mask=r3.mask, views=V3)
                     else:
                         prow, bpart = fr, self._ws[(self._lane, "fz_partials")]
-                    prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 else None
+                    prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 and not unfused_in else None
                     lin_d = rd is not None and (rd.linbn or (
                         self.linbn_ds and rd.cu.Ci % 64 == 0 and not rd.frozen_stats and
                         (rd.cu.stride == 1 or (prev_r3 is not None and self.fuse_bn_bwd and rd.cu.stride == 2 and
@@ -1350,7 +1387,7 @@ class SM3Engine:
             if rd is not None and isinstance(dxd, dict):
                 # the downsample unit went by linearity: its data gradient is the two-segment product of dz (= dcur) and the
                 # compact block input, joined with conv1's data gradient as the two-pass form's is
-                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 else None
+                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 and not unfused_in else None
                 cd = rd.cu
                 Vd = r3.V
                 Cd, Cin = cd.Co, cd.Ci
@@ -1366,7 +1403,7 @@ class SM3Engine:
                                       w_view_stride=Cin * Cd, w1_view_stride=Cin * Cin)
                     fr = None
             elif rd is not None:
-                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 else None
+                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 and not unfused_in else None
                 cd = rd.cu
                 V = prev_r3.V if prev_r3 is not None else 1
                 if (prev_r3 is not None and self.fuse_bn_bwd and cd.stride == 2
@@ -1391,9 +1428,11 @@ class SM3Engine:
                     fr = None
             else:
                 # din is the gradient of the previous block's output = of its bn3 (+residual, ReLU) unit
-                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 else None
+                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 and not unfused_in else None
                 din, fr = self.conv_backward(r1, dx1, addend=dz, fuse=prev_r3)
             dcur = din
+            if unfused_in:
+                return dcur
             if last_view and "cd" in blk and bi > 0:  # first block of a stage: the stage is complete
                 stage = blk["c1"].name.rsplit(".", 2)[0]  # e.g. derm_backbone.encoder.layer4
                 self._notify(stage + ".", stage + ".")
@@ -1652,9 +1691,9 @@ class SM3Engine:
         self._join(streams)
         return dxs
 
-    def encoder_only(self, branch, x, train, want_grad):
+    def encoder_only(self, branch, x, train, want_grad, keep=None):
         """One encoder call (SimCLRSkinV3.extract / a bare ResNet forward): fp32 features [N,2048] and the
-        context for encoder_backward when want_grad."""
+        context for encoder_backward when want_grad (keep: see encoder_forward)."""
         dev = x.device
         self.prepare(dev)
         self.refresh_weights()
@@ -1662,5 +1701,5 @@ class SM3Engine:
         N = x.shape[0]
         f32 = torch.empty(N, plan.out_dim, dtype=torch.float32, device=dev)
         ctxs = [] if want_grad else None
-        self.encoder_forward(plan, x, train, f32, None, ctxs)
+        self.encoder_forward(plan, x, train, f32, None, ctxs, keep=keep)
         return f32, (ctxs[0] if want_grad else None)

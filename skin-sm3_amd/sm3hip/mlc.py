@@ -261,7 +261,8 @@ class MLCHeads:
                 ops.bn_eval_scale_shift(bk["gamma"], bk["beta"], rm, rv, bns[0].eps, SC, scale, shift)
             out = torch.empty_like(y)
             ops.bn_act(SM3_F32, y, scale, shift, None, relu, out, B, SC)
-            recs.append(dict(x=h, y=y, out=out, mean=mean, invstd=invstd, train=train))
+            recs.append(dict(x=h, y=y, out=out, mean=mean, invstd=invstd, train=train,
+                             frozen=None if train else (rm, rv, bns[0].eps)))
             h = out
         return h, recs
 
@@ -275,19 +276,23 @@ class MLCHeads:
             bk, r = banks[j], recs[j]
             C, Cin = bk["C"], bk["Cin"]
             SC = S * C
-            if not r["train"]:
-                raise NotImplementedError("backward through a label projector whose BatchNorm1d is in eval mode "
-                                          "(the reference freezes such projectors: mlc_eval.py --finetune fc)")
+            mean, invstd = r["mean"], r["invstd"]
+            if not r["train"]:  # eval mode: the running statistics are constants (the encoders' frozen_stats form)
+                rm, rv, eps = r["frozen"]
+                mean, invstd = rm, torch.rsqrt(rv + eps)
             prow = ops.bn_bwd_partial_rows(B, SC)
             bpart = torch.empty(prow, 2, SC, dtype=torch.float32, device=dev)
             dz = torch.empty_like(dh)
-            ops.bn_bwd_reduce(SM3_F32, dh, r["out"] if bk["relu"] else None, r["y"], r["mean"], r["invstd"], dz, B, SC, bpart)
+            ops.bn_bwd_reduce(SM3_F32, dh, r["out"] if bk["relu"] else None, r["y"], mean, invstd, dz, B, SC, bpart)
             lsums = torch.empty(2 * SC, dtype=torch.float64, device=dev)
             ops.bn_stats_reduce(bpart, prow, SC, lsums)
             dgam = torch.zeros(SC, dtype=torch.float32, device=dev) if bk["gamma"] is not None else None
             dbet = torch.zeros(SC, dtype=torch.float32, device=dev) if bk["gamma"] is not None else None
             dy = torch.empty_like(dz)
-            ops.bn_bwd_apply(SM3_F32, dz, r["y"], r["mean"], r["invstd"], bk["gamma"], lsums, B, lsums, dgam, dbet, dy, B, SC)
+            # eval mode: all-zero batch sums drop the mean(dz) / mean(dz * xhat) terms, so dy = gamma * invstd * dz, and
+            # d(gamma), d(beta) are the plain sums
+            gsums = lsums if r["train"] else torch.zeros_like(lsums)
+            ops.bn_bwd_apply(SM3_F32, dz, r["y"], mean, invstd, bk["gamma"], gsums, B, lsums, dgam, dbet, dy, B, SC)
             grads_g[j], grads_b[j] = dgam, dbet
             if j == 0:
                 if need_params:

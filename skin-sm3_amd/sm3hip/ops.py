@@ -1254,6 +1254,35 @@ def stem_dgrad_bn(dtype, dz, xo, mean, invstd, gamma, gsums, count, w_master, dx
               "sm3_stem_dgrad_bn")
 
 
+def cam_alpha(dtype, g, alpha, N, HW, C):
+    """Grad-CAM channel weights (sm3_cam_alpha): alpha [T, N, C] fp32 = the mean over the HW positions of g [T, N, HW, C]
+    (`dtype`), positions added in ascending order."""
+    _chk(g, TORCH_DTYPE[dtype], "g"); _chk(alpha, torch.float32, "alpha")
+    T = alpha.numel() // (N * C) if N * C > 0 else 0
+    if T < 1 or alpha.numel() != T * N * C or g.numel() != T * N * HW * C:
+        raise ValueError("cam_alpha: g [T, N, HW, C] and alpha [T, N, C] do not match")
+    with _prof("cam_alpha", float(g.numel()), _sz(dtype) * g.numel() + 4.0 * alpha.numel()):
+        check(_lib.load().sm3_cam_alpha(dtype, _ptr(g), _ptr(alpha), T, N, HW, C, _stream()), "sm3_cam_alpha")
+
+
+def cam_maps(dtype, a, alpha, low, maps, N, h, w, C):
+    """Grad-CAM maps (sm3_cam_maps) of the stage output a [N, h*w, C] (`dtype`, NHWC) weighted by alpha [T, N, C] fp32: low
+    [N, T, h, w] = ReLU(sum_c alpha * a) and maps [N, T, H, W] = low upsampled (bilinear, align_corners=False) and
+    normalised to [0, 1] per map, both fp32."""
+    _chk(a, TORCH_DTYPE[dtype], "a")
+    for t, n in ((alpha, "alpha"), (low, "low"), (maps, "maps")):
+        _chk(t, torch.float32, n)
+    T = alpha.numel() // (N * C) if N * C > 0 else 0
+    if maps.dim() != 4 or tuple(maps.shape[:2]) != (N, T) or tuple(low.shape) != (N, T, h, w):
+        raise ValueError("cam_maps: low must be [N, T, h, w] and maps [N, T, H, W]")
+    if T < 1 or alpha.numel() != T * N * C or a.numel() != N * h * w * C:
+        raise ValueError("cam_maps: a [N, h*w, C] and alpha [T, N, C] do not match")
+    H, W = maps.shape[2], maps.shape[3]
+    with _prof("cam_maps", 2.0 * N * h * w * C * T, _sz(dtype) * a.numel() + 4.0 * (low.numel() + maps.numel())):
+        check(_lib.load().sm3_cam_maps(dtype, _ptr(a), _ptr(alpha), _ptr(low), _ptr(maps), N, T, h, w, C, H, W, _stream()),
+              "sm3_cam_maps")
+
+
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):
     """Stem weight gradient with bn1's backward apply fused into the operand load (sm3_stem_wgrad_bn; bf16 / fp16 / exact f32).
     slabs: fp32 workspace of STEM_WGRAD_SLABS * 64 * 147 floats -> fixed-order sum instead of float atomics."""
