@@ -250,10 +250,11 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const T* __restrict__ x, co
             for (int e = 0; e < E; ++e) v[e] += q[e] * rs[e];
         }
         if (relu) {
-            if (mask) {  // one bit per element (y > 0), one byte per 16-byte vector: what backward needs of y
+            if (mask) {  // one bit per element (stored y > 0), one byte per 16-byte vector: what backward needs of y
+                constexpr float thr = OUT_F32 ? 0.f : ElemTraits<T>::kReluBit;
                 unsigned m = 0;
 #pragma unroll
-                for (int e = 0; e < E; ++e) m |= (v[e] > 0.f ? 1u : 0u) << e;
+                for (int e = 0; e < E; ++e) m |= (v[e] > thr ? 1u : 0u) << e;
                 mask[r * (C / E) + cv] = (uint8_t)m;
             }
 #pragma unroll

@@ -61,15 +61,20 @@ __device__ __forceinline__ float keep_if_bit(float v, unsigned m, int e) {
 
 template <typename T>
 struct ElemTraits;
+// kReluBit: a ReLU output's bit is `v > kReluBit`, v the fp32 value before it is stored as T -- exactly `stored y > 0`
+// under round-to-nearest-even.  f16: 0 < v <= 2^-25 (half the smallest subnormal) stores +0, so its bit must be 0.  bf16
+// keeps 0: only fp32 subnormals at or below 2^-134 would store +0 there.
 template <>
 struct ElemTraits<float> {
     static constexpr int kPer16B = 4;
+    static constexpr float kReluBit = 0.f;
     __device__ static __forceinline__ float load(const float* p) { return *p; }
     __device__ static __forceinline__ float round(float v) { return v; }
 };
 template <>
 struct ElemTraits<bf16_t> {
     static constexpr int kPer16B = 8;
+    static constexpr float kReluBit = 0.f;
     __device__ static __forceinline__ float load(const bf16_t* p) { return bf16_to_f32(p->v); }
     __device__ static __forceinline__ float round(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 };
@@ -77,6 +82,7 @@ struct ElemTraits<bf16_t> {
 template <>
 struct ElemTraits<f16_t> {
     static constexpr int kPer16B = 8;
+    static constexpr float kReluBit = 0x1p-25f;
     __device__ static __forceinline__ float load(const f16_t* p) { return f16_to_f32(p->v); }
     __device__ static __forceinline__ float round(float v) { return f16_to_f32(f32_to_f16(v)); }
 };

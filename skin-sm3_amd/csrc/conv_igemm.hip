@@ -953,7 +953,7 @@ __global__ __launch_bounds__(WM* WN * 64, (EPI >= 1 && STAGES == 1) ? 4 : 2) voi
                 if (p.ep_mask) {  // what the backward pass needs of the output: one bit per element
                     unsigned m = 0;
 #pragma unroll
-                    for (int e = 0; e < EPC; ++e) m |= (v[e] > 0.f ? 1u : 0u) << e;
+                    for (int e = 0; e < EPC; ++e) m |= (v[e] > ElemTraits<T>::kReluBit ? 1u : 0u) << e;
                     p.ep_mask[e_off[k] / EPC] = (uint8_t)m;
                 }
 #pragma unroll

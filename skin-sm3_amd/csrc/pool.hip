@@ -192,8 +192,8 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const T* __res
 
 // Backward of that chain up to BatchNorm-backward phase 1, in one pass over the stem-sized tensors: gathers the
 // pooled gradient through the argmax bytes (as maxpool_bwd_kernel), masks it with the ReLU recomputed from the
-// pre-BN tensor (x*scale + shift > 0), stores dz and emits the per-block partial sums of (dz, dz * xhat) in the
-// layout of sm3_bn_bwd_reduce.  Replaces maxpool_bwd + bn_bwd_reduce: one write and one read of the gradient of
+// pre-BN tensor (x*scale + shift > kReluBit: the stored forward value > 0), stores dz and emits the per-block partial
+// sums of (dz, dz * xhat) in the layout of sm3_bn_bwd_reduce.  Replaces maxpool_bwd + bn_bwd_reduce: one write and one read of the gradient of
 // the largest activation fewer, and no ReLU mask was ever stored.
 // grid (vectors per pixel / tbx, row groups, views); rows = pixels of ONE view.
 template <typename T>
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void maxpool_bn_bwd_kernel(const uint8_t* __re
                 float xv[E];
                 unpack16<T>(xu[u], xv);
 #pragma unroll
-                for (int e = 0; e < E; ++e) g[e] = (xv[e] * sc[e] + sh[e] > 0.f) ? g[e] : 0.f;
+                for (int e = 0; e < E; ++e) g[e] = (xv[e] * sc[e] + sh[e] > ElemTraits<T>::kReluBit) ? g[e] : 0.f;
                 const uint4 packed = pack16<T>(g);
                 stg16<true>(dz + pixs[u] * C + (int64_t)cv * E, packed);
                 float gr[E];

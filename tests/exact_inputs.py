@@ -1,0 +1,110 @@
+"""Test helper: exact-input generation and the checks of the bit-exact kernel suites (test_exact_gemm_gpu.py,
+test_exact_bn_gpu.py).
+
+Every operand is a small integer times a power of two.  A product of such operands is exact in fp32, and so is every
+partial sum whose magnitude stays below 2^24 quanta, whatever the summation order.  need_exact / need_repr assert those
+preconditions in fp64 on the CPU; Guarded, same and env are what the GPU tests compare and launch with."""
+import contextlib
+import os
+
+import torch
+
+Q24 = float(1 << 24)
+SENTINEL = 0xA5
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# exact-input generator and its preconditions (CPU only)
+# ------------------------------------------------------------------------------------------------------------------------
+def draw(gen, shape, amp, density, exp=0):
+    """Integers in [-amp, amp], nonzero with probability `density`, times 2^exp (fp64)."""
+    mag = torch.randint(1, amp + 1, shape, generator=gen)
+    sign = torch.randint(0, 2, shape, generator=gen) * 2 - 1
+    keep = torch.rand(shape, generator=gen) < density
+    return (mag * sign * keep).double() * 2.0 ** exp
+
+
+def quantum(*ts):
+    """Largest power of two that divides every element (1 for all-zero input)."""
+    q = None
+    for t in ts:
+        nz = t[t != 0].abs().double()
+        if nz.numel() == 0:
+            continue
+        m, e = torch.frexp(nz)
+        mi = (m * 2.0 ** 53).long()
+        low = (mi & -mi).double() * torch.pow(2.0, (e - 53).double())
+        v = float(low.min())
+        q = v if q is None else min(q, v)
+    return 1.0 if q is None else q
+
+
+def need_exact(abs_sum, q, what):
+    """abs_sum: sum of |terms| of an fp32 accumulation (any order), every term a multiple of q."""
+    worst = float(abs_sum.max()) / q if abs_sum.numel() else 0.0
+    assert worst < Q24, f"{what}: worst-case partial sum is {worst:.0f} quanta (>= 2^24): not exact in fp32"
+
+
+def need_repr(t, dt, what):
+    assert torch.equal(t.to(dt).double(), t), f"{what}: not representable in {dt}"
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# GPU helpers
+# ------------------------------------------------------------------------------------------------------------------------
+def _dev():
+    return torch.device("cuda:0")
+
+
+class Guarded:
+    """A contiguous slice of a sentinel-filled buffer; guards() is True when the bytes around it are unchanged."""
+    PAD = 512  # bytes either side (keeps the slice 16-byte aligned)
+
+    def __init__(self, n, dtype, fill=None):
+        self.es = torch.empty(0, dtype=dtype).element_size()
+        self.g = self.PAD // self.es
+        self.buf = torch.empty(n + 2 * self.g, dtype=dtype, device=_dev())
+        self.buf.view(torch.uint8).fill_(SENTINEL)
+        self.t = self.buf[self.g:self.g + n]
+        if fill is not None:
+            self.t.copy_(fill.reshape(-1))
+
+    def guards(self):
+        b = self.buf.view(torch.uint8)
+        return bool((b[:self.PAD] == SENTINEL).all()) and bool((b[-self.PAD:] == SENTINEL).all())
+
+    def untouched(self):
+        return bool((self.buf.view(torch.uint8) == SENTINEL).all())
+
+
+@contextlib.contextmanager
+def env(settings):
+    old = {k: os.environ.get(k) for k in settings}
+    try:
+        for k, v in settings.items():
+            os.environ[k] = str(v)
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def same(got, ref, what):
+    """Value equality in fp64 (+0 == -0), both on the GPU."""
+    a = got.reshape(-1).double()
+    b = ref.reshape(-1).to(_dev()).double()
+    eq = (a == b) | (torch.isnan(a) & torch.isnan(b))
+    if not bool(eq.all()):
+        bad = (~eq).nonzero()[:, 0]
+        i = int(bad[0])
+        raise AssertionError(f"{what}: {bad.numel()} of {a.numel()} differ; first at {i}: got {float(a[i])!r}, "
+                             f"want {float(b[i])!r}")
+
+
+def mask_bytes(bits, epc):
+    """ReLU bits [.., C] -> one byte per `epc` consecutive elements, element e in bit e."""
+    b = bits.reshape(-1, epc).to(torch.int64)
+    return (b << torch.arange(epc)).sum(1).to(torch.uint8)

@@ -12,64 +12,28 @@ for the whole table without a GPU).  Two regimes:
 The epilogues with an affine step or an addend round the GEMM result to 16 bits BEFORE the addend on the lean path
 (csrc/conv_igemm.hip, EPI 2 / 3): those cases stay in the representable regime, where one and two roundings agree.
 
-Contracts pinned here besides the values: the ReLU bits are `y > 0` (strict, as threshold_backward); the BatchNorm partial
+Contracts pinned here besides the values: the ReLU bits are `stored y > 0` (strict, as threshold_backward); the BatchNorm partial
 rows of a forward launch are the sums of the rounded GEMM result (before an addend); a fused BN-backward launch without x
 writes 0 into the sum(dz * xhat) slot; outputs are compared with +0 and -0 identified.  Every output is a slice of a larger
 buffer filled with a sentinel, and the bytes around it must come back unchanged.
 """
-import contextlib
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
 
+from exact_inputs import SENTINEL, Guarded, _dev, draw, env, mask_bytes, need_exact, need_repr, quantum, same
+
 F32, BF16, F16 = torch.float32, torch.bfloat16, torch.float16
 DTYPES = [F32, BF16, F16]
 IDS = ["f32", "bf16", "f16"]
-Q24 = float(1 << 24)
 KCH = {F32: 32, BF16: 64, F16: 64}  # elements per 128-byte K chunk
 EPC = {F32: 4, BF16: 8, F16: 8}     # elements per ReLU-mask byte (one 16-byte vector)
-SENTINEL = 0xA5
 LAUNCHES = [0]
 
 
 # ------------------------------------------------------------------------------------------------------------------------
 # exact-input generator and its preconditions (CPU only)
 # ------------------------------------------------------------------------------------------------------------------------
-def draw(gen, shape, amp, density, exp=0):
-    """Integers in [-amp, amp], nonzero with probability `density`, times 2^exp (fp64)."""
-    mag = torch.randint(1, amp + 1, shape, generator=gen)
-    sign = torch.randint(0, 2, shape, generator=gen) * 2 - 1
-    keep = torch.rand(shape, generator=gen) < density
-    return (mag * sign * keep).double() * 2.0 ** exp
-
-
-def quantum(*ts):
-    """Largest power of two that divides every element (1 for all-zero input)."""
-    q = None
-    for t in ts:
-        nz = t[t != 0].abs().double()
-        if nz.numel() == 0:
-            continue
-        m, e = torch.frexp(nz)
-        mi = (m * 2.0 ** 53).long()
-        low = (mi & -mi).double() * torch.pow(2.0, (e - 53).double())
-        v = float(low.min())
-        q = v if q is None else min(q, v)
-    return 1.0 if q is None else q
-
-
-def need_exact(abs_sum, q, what):
-    """abs_sum: sum of |terms| of an fp32 accumulation (any order), every term a multiple of q."""
-    worst = float(abs_sum.max()) / q if abs_sum.numel() else 0.0
-    assert worst < Q24, f"{what}: worst-case partial sum is {worst:.0f} quanta (>= 2^24): not exact in fp32"
-
-
-def need_repr(t, dt, what):
-    assert torch.equal(t.to(dt).double(), t), f"{what}: not representable in {dt}"
-
-
 def tile_sums(rows, tiles=None):
     """[M, C] -> per-128-row sums [tiles, C] (fp64)."""
     M, C = rows.shape
@@ -508,65 +472,8 @@ def test_case_table_preconditions():
 # ------------------------------------------------------------------------------------------------------------------------
 # GPU helpers
 # ------------------------------------------------------------------------------------------------------------------------
-def _dev():
-    return torch.device("cuda:0")
-
-
-class Guarded:
-    """A contiguous slice of a sentinel-filled buffer; guards() is True when the bytes around it are unchanged."""
-    PAD = 512  # bytes either side (keeps the slice 16-byte aligned)
-
-    def __init__(self, n, dtype, fill=None):
-        self.es = torch.empty(0, dtype=dtype).element_size()
-        self.g = self.PAD // self.es
-        self.buf = torch.empty(n + 2 * self.g, dtype=dtype, device=_dev())
-        self.buf.view(torch.uint8).fill_(SENTINEL)
-        self.t = self.buf[self.g:self.g + n]
-        if fill is not None:
-            self.t.copy_(fill.reshape(-1))
-
-    def guards(self):
-        b = self.buf.view(torch.uint8)
-        return bool((b[:self.PAD] == SENTINEL).all()) and bool((b[-self.PAD:] == SENTINEL).all())
-
-    def untouched(self):
-        return bool((self.buf.view(torch.uint8) == SENTINEL).all())
-
-
-@contextlib.contextmanager
-def env(settings):
-    old = {k: os.environ.get(k) for k in settings}
-    try:
-        for k, v in settings.items():
-            os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def _g(t, dt):
     return t.to(dt).to(_dev()).contiguous()
-
-
-def same(got, ref, what):
-    """Value equality in fp64 (+0 == -0), both on the GPU."""
-    a = got.reshape(-1).double()
-    b = ref.reshape(-1).to(_dev()).double()
-    eq = (a == b) | (torch.isnan(a) & torch.isnan(b))
-    if not bool(eq.all()):
-        bad = (~eq).nonzero()[:, 0]
-        i = int(bad[0])
-        raise AssertionError(f"{what}: {bad.numel()} of {a.numel()} differ; first at {i}: got {float(a[i])!r}, "
-                             f"want {float(b[i])!r}")
-
-
-def mask_bytes(bits, epc):
-    b = bits.reshape(-1, epc).to(torch.int64)
-    return (b << torch.arange(epc)).sum(1).to(torch.uint8)
 
 
 def launch(fn, *a, **k):
@@ -1046,6 +953,33 @@ def test_f16_data_gradient_overflow_stores_inf():
             same(dz.t, want, f"f16 overflow dgrad {e}")
             same(y.t, want, f"f16 overflow forward {e}")
             assert dz.guards() and y.guards()
+
+
+@pytest.mark.gpu
+def test_f16_relu_bits_at_the_underflow_threshold():
+    """Affine outputs 2^-26, 2^-25, 3 2^-26 and -2^-26 store as +0, +0 (the tie goes to the even 0), 2^-24 and 0: their
+    ReLU bits are 0, 0, 1, 0 -- the stored y > 0 -- on every epilogue path of the fused forward launch."""
+    o = ops()
+    code = o.dtype_code(F16)
+    M, K, C = 128, 64, 8
+    x = torch.zeros(M, K, dtype=torch.float64)
+    w = torch.zeros(C, K, dtype=torch.float64)
+    x[:, 0] = torch.tensor([1.0, 2.0, 3.0, -1.0, 4.0, 0.0, 1.0, 3.0]).repeat(M // 8)
+    w[:, 0] = 1.0
+    sc = torch.full((C,), 2.0 ** -26, dtype=torch.float64)
+    pre = (x[:, :1] * sc).expand(M, C)
+    want = pre.clamp_min(0).to(F16).double()
+    assert int(((pre > 0) & (want == 0)).sum()) == M // 8 * 3 * C
+    d = o.make_desc(code, M, 1, 1, K, 1, 1, C, 1, 1, [(0, 0, 0)], K)
+    for e in CONV_ENVS:
+        with env(e):
+            y = Guarded(M * C, F16)
+            mk = Guarded(M * C // 8, torch.uint8)
+            o.conv_bn_act_fused(d, _g(x, F16), _g(w, F16), _g(sc, F32), _g(torch.zeros(C), F32), None, True, y.t, mk.t)
+            torch.cuda.synchronize()
+            same(y.t, want, f"f16 underflow y {e}")
+            assert torch.equal(mk.t.cpu(), mask_bytes(want > 0, 8)), f"f16 underflow: ReLU bits != (stored y > 0) {e}"
+            assert y.guards() and mk.guards()
 
 
 # ------------------------------------------------------------------------------------------------------------------------
