@@ -720,6 +720,34 @@ int sm3_cam_alpha(int dtype, const void* g, float* alpha, int T, int N, int HW, 
 int sm3_cam_maps(int dtype, const void* a, const float* alpha, float* low, float* maps, int N, int T, int h, int w, int C, int H,
                  int W, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Pixel-level attributions: Integrated Gradients and SmoothGrad (csrc/attr.hip; ABI 9, additive).  x: one modality's images
+ * [N][E] f32, E = 3 * H * W, a multiple of 4; every pointer 16-byte aligned (SM3_EALIGN otherwise).  Every product and sum
+ * below is a separately rounded f32 operation (no FMA) unless float64 is named.
+ * sm3_attr_path: out [c][N][E] = base + alpha_k * (x - base), k = k0 .. k0 + c - 1, alpha_k = (float)(2k + 1) / (float)(2 *
+ *   steps) (midpoint rule); base [base_n][E], base_n = 1 (shared) or N.  k0 + c <= steps <= 2^23.
+ * sm3_attr_noise: out [c][N][E] = x + sigma[n] * z(seed, sample, n, e), sample = k0 + j * stride for j < c; z: Philox4x32-10,
+ *   key = (seed low word, seed high word), counter = (e / 4, n, sample, 0), Box-Muller in float64 on the word pairs (w0, w1)
+ *   and (w2, w3) with u = (w + 0.5) * 2^-32: r = sqrt(-2 log(u_a)), (r cos(2 pi u_b), r sin(2 pi u_b)), rounded to f32;
+ *   element e takes lane e % 4.  The value depends on (seed, sample, n, e) alone, never on c, k0, stride or the grid.
+ * sm3_attr_accumulate: acc [N][E] = (((acc + w * f(g[0])) + w * f(g[1])) + ...) over g [c][N][E], ascending, f = identity
+ *   (squared = 0) or the square (squared = 1): cutting the c steps into several calls gives the same bits.
+ * sm3_attr_finish: acc, attr [T][N][C][HW]; mode 0 (IG): attr = (x - base) * acc with x [N][C][HW] and base [base_n][C][HW];
+ *   mode 1 (SmoothGrad): attr = acc (x, base unused).  maps [T][N][HW] = the sum over c (ascending) of |attr|.  sums [T][N]
+ *   float64 = the sum of attr over (c, p) by a fixed tree: per-workgroup partials (partials: float64 workspace of T * N *
+ *   sm3_attr_finish_blocks(HW) values, stored plainly), then one launch adding a row's partials in index order.  HW a multiple
+ *   of 4, T * N <= 65535.
+ * Sizes are checked on the host (SM3_EINVAL / SM3_EALIGN) before anything is launched.  No atomics.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_attr_path(const float* x, const float* base, int base_n, float* out, int N, int64_t E, int k0, int c, int steps,
+                  void* stream);
+int sm3_attr_noise(const float* x, const float* sigma, float* out, int N, int64_t E, int k0, int c, int stride, uint64_t seed,
+                   void* stream);
+int sm3_attr_accumulate(const float* g, float* acc, int c, int N, int64_t E, float weight, int squared, void* stream);
+int sm3_attr_finish_blocks(int HW);
+int sm3_attr_finish(const float* acc, const float* x, const float* base, int base_n, float* attr, float* maps, double* sums,
+                    double* partials, int T, int N, int C, int HW, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

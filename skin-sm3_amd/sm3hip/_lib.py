@@ -171,6 +171,11 @@ SIGNATURES = {
     "sm3_knn_vote": [_P, _L, _L, _L, _P, _I, _P, _I, _F, _P, _P, _P, _P],
     "sm3_cam_alpha": [_I, _P, _P, _I, _I, _I, _I, _P],
     "sm3_cam_maps": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "sm3_attr_path": [_P, _P, _I, _P, _I, _L, _I, _I, _I, _P],
+    "sm3_attr_noise": [_P, _P, _P, _I, _L, _I, _I, _I, C.c_uint64, _P],
+    "sm3_attr_accumulate": [_P, _P, _I, _I, _L, _F, _I, _P],
+    "sm3_attr_finish_blocks": [_I],
+    "sm3_attr_finish": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
 _lib = None

@@ -33,42 +33,42 @@ STAGES = ("layer1", "layer2", "layer3", "layer4")
 TARGETS = ("pred", "cls")
 
 
-def _parts(model):
+def _parts(model, who="grad_cam"):
     """(kind, derm encoder, clinic encoder) of a Baseline ("baseline") or an inference.py Model ("mlc")."""
     if hasattr(model, "classifier") and hasattr(model, "derm_backbone"):
         return "baseline", model.derm_backbone, model.clinic_backbone
     if hasattr(model, "extractor") and hasattr(model, "prototypes") and hasattr(model, "mlc_sa"):
         return "mlc", model.extractor.derm_backbone, model.extractor.clinic_backbone
-    raise TypeError("grad_cam: model must be a Baseline (src/models/baseline.py) or an inference.py Model")
+    raise TypeError(f"{who}: model must be a Baseline (src/models/baseline.py) or an inference.py Model")
 
 
-def _check(model, derm, clinic, layer, target):
-    kind = _parts(model)[0]
+def _check(model, derm, clinic, layer, target, who="grad_cam"):
+    kind = _parts(model, who)[0]
     if layer not in STAGES:
-        raise ValueError(f"grad_cam: layer must be one of {', '.join(STAGES)}, got {layer!r}")
+        raise ValueError(f"{who}: layer must be one of {', '.join(STAGES)}, got {layer!r}")
     train = [n for n, m in model.named_modules() if m.training]
     if train:
-        raise ValueError(f"grad_cam: the model must be in eval mode (model.eval()); in train mode: {train[0] or 'model'}")
+        raise ValueError(f"{who}: the model must be in eval mode (model.eval()); in train mode: {train[0] or 'model'}")
     for name, x in (("derm", derm), ("clinic", clinic)):
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise ValueError(f"grad_cam: {name} must be a CUDA tensor (the SM3 HIP path has no CPU fallback)")
+            raise ValueError(f"{who}: {name} must be a CUDA tensor (the SM3 HIP path has no CPU fallback)")
         if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"grad_cam: {name} must be float32 [N, 3, H, W]")
+            raise ValueError(f"{who}: {name} must be float32 [N, 3, H, W]")
     if derm.shape != clinic.shape:
-        raise ValueError("grad_cam: derm and clinic must have the same shape")
+        raise ValueError(f"{who}: derm and clinic must have the same shape")
     if any(not p.is_cuda for p in model.parameters()):
-        raise ValueError("grad_cam: the model's parameters must be on the GPU")
+        raise ValueError(f"{who}: the model's parameters must be on the GPU")
     N = derm.shape[0]
     if isinstance(target, str):
         if target not in TARGETS:
-            raise ValueError(f"grad_cam: target must be 'pred', 'cls' or a LongTensor [N, 8], got {target!r}")
+            raise ValueError(f"{who}: target must be 'pred', 'cls' or a LongTensor [N, 8], got {target!r}")
     else:
         if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (N, len(NUM_CLASSES)):
-            raise ValueError("grad_cam: a target tensor must be int64 [N, 8]")
+            raise ValueError(f"{who}: a target tensor must be int64 [N, 8]")
         t = target.cpu()
         for i, n in enumerate(NUM_CLASSES):
             if bool(((t[:, i] < 0) | (t[:, i] >= n)).any()):
-                raise ValueError(f"grad_cam: target class out of range for label {i} ({n} classes)")
+                raise ValueError(f"{who}: target class out of range for label {i} ({n} classes)")
     return kind
 
 

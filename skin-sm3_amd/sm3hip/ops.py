@@ -1283,6 +1283,86 @@ def cam_maps(dtype, a, alpha, low, maps, N, h, w, C):
               "sm3_cam_maps")
 
 
+def _attr_rows(x, name):
+    """(N, E) of one modality's images [N, 3, H, W] (or [N, E]) fp32."""
+    _chk(x, torch.float32, name)
+    if x.dim() < 2 or x.shape[0] < 1:
+        raise ValueError(f"{name} must be [N, ...]")
+    return x.shape[0], x.numel() // x.shape[0]
+
+
+def attr_path(x, base, out, k0, steps):
+    """Integrated-Gradients path points (sm3_attr_path): out [c, N, ...] fp32 = base + alpha_k (x - base), k = k0 .. k0 + c - 1,
+    alpha_k = (2k + 1) / (2 steps); base: [1, ...] (shared by the batch) or [N, ...]."""
+    N, E = _attr_rows(x, "x")
+    _chk(base, torch.float32, "base"); _chk(out, torch.float32, "out")
+    c = out.shape[0] if out.dim() > 1 else 0
+    if c < 1 or out.numel() != c * N * E or base.numel() not in (E, N * E):
+        raise ValueError("attr_path: x [N, E], base [1 | N, E] and out [c, N, E] do not match")
+    with _prof("attr_path", 3.0 * out.numel(), 4.0 * (x.numel() + base.numel() + out.numel())):
+        check(_lib.load().sm3_attr_path(_ptr(x), _ptr(base), base.numel() // E, _ptr(out), N, E, k0, c, steps, _stream()),
+              "sm3_attr_path")
+
+
+def attr_noise(x, sigma, out, k0, seed, stride=1):
+    """SmoothGrad samples (sm3_attr_noise): out [c, N, ...] fp32 = x + sigma[n] * z(seed, k0 + j * stride, n, e), z standard
+    normal (Philox4x32-10 + Box-Muller), a function of (seed, sample, n, e) alone."""
+    N, E = _attr_rows(x, "x")
+    _chk(sigma, torch.float32, "sigma"); _chk(out, torch.float32, "out")
+    c = out.shape[0] if out.dim() > 1 else 0
+    if c < 1 or out.numel() != c * N * E or sigma.numel() != N:
+        raise ValueError("attr_noise: x [N, E], sigma [N] and out [c, N, E] do not match")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("attr_noise: seed must fit 64 bits")
+    with _prof("attr_noise", 2.0 * out.numel(), 4.0 * (x.numel() + out.numel())):
+        check(_lib.load().sm3_attr_noise(_ptr(x), _ptr(sigma), _ptr(out), N, E, k0, c, stride, seed, _stream()),
+              "sm3_attr_noise")
+
+
+def attr_accumulate(g, acc, weight, squared=False):
+    """acc [N, ...] fp32 = (((acc + w * f(g[0])) + w * f(g[1])) + ...) over g [c, N, ...] fp32 (or [c * N, ...]) in ascending
+    order (sm3_attr_accumulate), f the identity or the square."""
+    N, E = _attr_rows(acc, "acc")
+    _chk(g, torch.float32, "g")
+    c = g.numel() // (N * E)
+    if c < 1 or g.numel() != c * N * E:
+        raise ValueError("attr_accumulate: g [c, N, E] and acc [N, E] do not match")
+    with _prof("attr_accumulate", 2.0 * g.numel(), 4.0 * (g.numel() + 2 * acc.numel())):
+        check(_lib.load().sm3_attr_accumulate(_ptr(g), _ptr(acc), c, N, E, float(weight), int(bool(squared)), _stream()),
+              "sm3_attr_accumulate")
+
+
+def attr_finish(acc, x, base, attr, maps, sums, mode):
+    """The attributions of one modality (sm3_attr_finish).  acc, attr [T, N, C, H, W] fp32; mode 0 (IG): attr = (x - base) *
+    acc, x [N, C, H, W], base [1 | N, C, H, W]; mode 1 (SmoothGrad): attr = acc.  maps [T, N, H, W] = sum_c |attr|; sums
+    [T, N] fp64 = the sum of attr per (t, n) by a fixed tree."""
+    if acc.dim() != 5 or attr.shape != acc.shape:
+        raise ValueError("attr_finish: acc and attr must be [T, N, C, H, W]")
+    T, N, Cc, H, W = acc.shape
+    for t, n in ((acc, "acc"), (attr, "attr"), (maps, "maps")):
+        _chk(t, torch.float32, n)
+    _chk(sums, torch.float64, "sums")
+    if tuple(maps.shape) != (T, N, H, W) or tuple(sums.shape) != (T, N) or mode not in (0, 1):
+        raise ValueError("attr_finish: maps must be [T, N, H, W], sums [T, N], mode 0 or 1")
+    base_n = 1
+    if mode == 0:
+        _chk(x, torch.float32, "x"); _chk(base, torch.float32, "base")
+        E = Cc * H * W
+        if x.numel() != N * E or base.numel() not in (E, N * E):
+            raise ValueError("attr_finish: x [N, C, H, W] and base [1 | N, C, H, W] do not match acc")
+        base_n = base.numel() // E
+    else:
+        x = base = None
+    lib = _lib.load()
+    blocks = lib.sm3_attr_finish_blocks(H * W)
+    if blocks < 1:
+        raise ValueError("attr_finish: empty images")
+    partials = torch.empty(T * N * blocks, dtype=torch.float64, device=acc.device)
+    with _prof("attr_finish", 4.0 * acc.numel(), 4.0 * (2 * acc.numel() + maps.numel())):
+        check(lib.sm3_attr_finish(_ptr(acc), _ptr(x), _ptr(base), base_n, _ptr(attr), _ptr(maps), _ptr(sums), _ptr(partials),
+                                  T, N, Cc, H * W, mode, _stream()), "sm3_attr_finish")
+
+
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):
     """Stem weight gradient with bn1's backward apply fused into the operand load (sm3_stem_wgrad_bn; bf16 / fp16 / exact f32).
     slabs: fp32 workspace of STEM_WGRAD_SLABS * 64 * 147 floats -> fixed-order sum instead of float atomics."""
