@@ -748,6 +748,28 @@ int sm3_attr_finish_blocks(int HW);
 int sm3_attr_finish(const float* acc, const float* x, const float* base, int base_n, float* attr, float* maps, double* sums,
                     double* partials, int T, int N, int C, int HW, int mode, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Deletion / insertion faithfulness curves of attribution maps (csrc/faith.hip; ABI 9, additive).  Integers and bit copies
+ * only: no float arithmetic, no float atomics.
+ * sm3_faith_rank: ranks [rows][HW] int32 of maps [rows][HW] f32 (finite), per row with IEEE comparisons (-0 == +0):
+ *   ranks[p] = #{q : map[q] > map[p]} + #{q < p : map[q] == map[p]} -- descending by value, ties by ascending index, a
+ *   permutation of 0 .. HW - 1 and a function of the map alone.  A stable least-significant-digit radix sort (4 passes of 8
+ *   bits over order-preserving keys), one workgroup per row; workspace: sm3_faith_rank_workspace(rows, HW) bytes (8-byte
+ *   aligned; the size query returns SM3_EINVAL when the byte count does not fit an int).  1 <= HW <= 2^24.
+ * sm3_faith_compose: one modality's perturbed inputs of curve steps k0 .. k0 + c - 1 for every label:
+ *   out [c][T][N][3][HW] = (ranks[n][t][p] < c_k) != invert ? base[n or 0][ch][p] : x[n][ch][p],  k = k0 + j,
+ *   c_k = (k * HW) / steps in 64-bit integers (c_0 = 0, c_steps = HW); invert = 0: deletion, 1: insertion.  x [N][3][HW], base
+ *   [base_n][3][HW] with base_n = 1 (shared) or N; ranks[n][t][p] is read at ranks[n * rank_stride_n + t * rank_stride_t + p]
+ *   (strides in elements, multiples of 4).  0 <= k0, k0 + c <= steps + 1, 1 <= steps <= HW, HW a multiple of 4, N * T <=
+ *   65535, every pointer 16-byte aligned (SM3_EALIGN otherwise).
+ * Sizes are checked on the host (SM3_EINVAL / SM3_EALIGN) before anything is launched.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_faith_rank_workspace(int rows, int HW);
+int sm3_faith_rank(const float* maps, int* ranks, int rows, int HW, void* workspace, int64_t workspace_bytes, void* stream);
+int sm3_faith_compose(const float* x, const float* base, int base_n, const int* ranks, int64_t rank_stride_n,
+                      int64_t rank_stride_t, float* out, int N, int T, int HW, int k0, int c, int steps, int invert,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

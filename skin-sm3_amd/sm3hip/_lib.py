@@ -176,6 +176,9 @@ SIGNATURES = {
     "sm3_attr_accumulate": [_P, _P, _I, _I, _L, _F, _I, _P],
     "sm3_attr_finish_blocks": [_I],
     "sm3_attr_finish": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sm3_faith_rank_workspace": [_I, _I],
+    "sm3_faith_rank": [_P, _P, _I, _I, _P, _L, _P],
+    "sm3_faith_compose": [_P, _P, _I, _P, _L, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 
 _lib = None

@@ -1363,6 +1363,51 @@ def attr_finish(acc, x, base, attr, maps, sums, mode):
                                   T, N, Cc, H * W, mode, _stream()), "sm3_attr_finish")
 
 
+FAITH_RANK_WORKSPACE = 256 << 20  # bytes of sort workspace per sm3_faith_rank launch, at most (one map's pairs at the least)
+
+
+def faith_rank(maps, ranks):
+    """ranks [..., HW] int32 of maps [..., HW] fp32 (finite): per row, descending by value, ties by ascending index
+    (sm3_faith_rank).  The rows are ranked in groups whose sort workspace stays within FAITH_RANK_WORKSPACE."""
+    _chk(maps, torch.float32, "maps"); _chk(ranks, torch.int32, "ranks")
+    if maps.dim() < 1 or maps.shape != ranks.shape or maps.numel() < 1:
+        raise ValueError("faith_rank: maps [..., HW] fp32 and ranks [..., HW] int32 must have the same, non-empty shape")
+    HW = maps.shape[-1]
+    rows = maps.numel() // HW
+    lib = _lib.load()
+    one = lib.sm3_faith_rank_workspace(1, HW)
+    if one < 1:
+        raise ValueError(f"faith_rank: HW = {HW} is out of range")
+    group = max(1, min(rows, FAITH_RANK_WORKSPACE // one))
+    ws = torch.empty(group * one, dtype=torch.uint8, device=maps.device)
+    m2, r2 = maps.view(rows, HW), ranks.view(rows, HW)
+    with _prof("faith_rank", 0.0, 4.0 * 2 * maps.numel() + 8.0 * 8 * maps.numel()):
+        for r0 in range(0, rows, group):
+            g = min(group, rows - r0)
+            check(lib.sm3_faith_rank(_ptr(m2[r0:]), _ptr(r2[r0:]), g, HW, _ptr(ws), ws.numel(), _stream()), "sm3_faith_rank")
+
+
+def faith_compose(x, base, ranks, out, k0, steps, invert):
+    """One modality's deletion (invert False) or insertion (True) inputs of curve steps k0 .. k0 + c - 1 (sm3_faith_compose):
+    out [c, T, N, 3, H, W] fp32 = base where (ranks[n, t] < (k * HW) // steps) != invert, else x.  x [N, 3, H, W], base [1 | N,
+    3, H, W]; ranks [N, T, H, W] int32, a view whose pixels are contiguous (one modality of the [N, T, 2, H, W] tensor)."""
+    N, E = _attr_rows(x, "x")
+    _chk(base, torch.float32, "base"); _chk(out, torch.float32, "out")
+    if x.dim() != 4 or x.shape[1] != 3 or out.dim() != 6 or ranks.dim() != 4:
+        raise ValueError("faith_compose: x [N, 3, H, W], ranks [N, T, H, W], out [c, T, N, 3, H, W]")
+    H, W = x.shape[2:]
+    c, T = out.shape[:2]
+    if not ranks.is_cuda or ranks.dtype != torch.int32 or tuple(ranks.shape) != (N, T, H, W) or ranks.stride(3) != 1 or \
+            ranks.stride(2) != W:
+        raise ValueError("faith_compose: ranks must be int32 [N, T, H, W] on the GPU with contiguous pixels")
+    if c < 1 or tuple(out.shape) != (c, T, N, 3, H, W) or base.numel() not in (E, N * E):
+        raise ValueError("faith_compose: x [N, 3, H, W], base [1 | N, 3, H, W] and out [c, T, N, 3, H, W] do not match")
+    with _prof("faith_compose", 0.0, 4.0 * (T * x.numel() + T * base.numel() + ranks.numel() + out.numel())):
+        check(_lib.load().sm3_faith_compose(_ptr(x), _ptr(base), base.numel() // E, _ptr(ranks), ranks.stride(0), ranks.stride(1),
+                                            _ptr(out), N, T, H * W, k0, c, steps, int(bool(invert)), _stream()),
+              "sm3_faith_compose")
+
+
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):
     """Stem weight gradient with bn1's backward apply fused into the operand load (sm3_stem_wgrad_bn; bf16 / fp16 / exact f32).
     slabs: fp32 workspace of STEM_WGRAD_SLABS * 64 * 147 floats -> fixed-order sum instead of float atomics."""

@@ -32,19 +32,19 @@ from sm3hip.cam import TARGETS  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES  # noqa: E402
 
 
-def add_attr_args(p):
+def add_attr_args(p, method_help="ig (Integrated Gradients) or smoothgrad",
+                  chunk_help="path points / samples per encoder forward (default: from the free device memory); any value gives "
+                             "the same bits"):
     """The flags the two attribution tools share (the place --cam-layer takes in the Grad-CAM tools)."""
     p.add_argument("--target", default="pred", choices=TARGETS,
                    help="logit per label: pred = the argmax class, cls = the class AUC_AVG scores (CLS_WEIGHTS)")
-    p.add_argument("--method", default="ig", help="ig (Integrated Gradients) or smoothgrad")
+    p.add_argument("--method", default="ig", help=method_help)
     p.add_argument("--steps", default=32, type=int, help="ig: points of the midpoint rule on the path from the baseline")
     p.add_argument("--samples", default=16, type=int, help="smoothgrad: noisy copies per image")
     p.add_argument("--sigma", default=0.15, type=float, help="smoothgrad: noise level relative to each image's max - min")
     p.add_argument("--squared", action="store_true", help="smoothgrad: average the squared gradients")
     p.add_argument("--attr-seed", default=0, type=int, help="smoothgrad: seed of the noise")
-    p.add_argument("--chunk", default=None, type=int,
-                   help="path points / samples per encoder forward (default: from the free device memory); any value gives "
-                        "the same bits")
+    p.add_argument("--chunk", default=None, type=int, help=chunk_help)
     p.add_argument("--split", default="test", choices=("test", "valid"))
     p.add_argument("--max-cases", default=64, type=int, help="cases of the split (or synthetic images) to attribute")
     return p
