@@ -8,8 +8,8 @@ al., 2017), one attribution per derm7pt label, image modality and pixel.
 The path (IG) is joint over the two images of a pair: both move from their baselines to the images with the same alpha, and
 the heads see the features of the same path point.  The targets are chosen once, at x.  Per chunk of c path points (noise
 samples) and modality: sm3_attr_path / sm3_attr_noise build the [c * N, 3, H, W] inputs, ONE encoder forward keeps the records
-of all of them, the heads give the 8 per-label seeds d logit_t / d feats (cam._head_grads), and 8 data-only backward passes
-(engine.encoder_backward(dx_out=, params=False)) from the shared forward each end in sm3_attr_accumulate, which adds the c
+of all of them, the heads give the 8 per-label seeds d logit_t / d feats (explain.Subject.head_grads), and 8 data-only backward
+passes (engine.encoder_backward(dx_out=, params=False)) from the shared forward each end in sm3_attr_accumulate, which adds the c
 gradients of every image into acc[t, modality] in ascending step order -- so the bits do not depend on the chunk.
 sm3_attr_finish multiplies by (x - b) (IG), sums |.| over the channels for the maps and adds the attributions of every
 (label, image) in float64 by a fixed tree: with the logits that gives IG's completeness gap
@@ -20,7 +20,8 @@ as they were.  Accumulators and outputs are fp32 in every arithmetic mode of the
 import torch
 
 from . import ops
-from .cam import _check, _head_grads, _parts
+from .bridge import scratch_grads
+from .explain import Subject, baseline_images, expand_baseline, forward_measured
 from .metrics import NUM_CLASSES
 
 METHODS = ("ig", "smoothgrad")
@@ -49,53 +50,31 @@ def _resolve_chunk(chunk, steps, N, saved_bytes, E, dev):
     return chunk
 
 
-def _baseline_images(baseline, x, who):
-    if isinstance(baseline, str):
-        if baseline != "zero":
-            raise ValueError(f"{who}: baseline must be 'zero' or a pair of tensors, got {baseline!r}")
-        return None
-    if not isinstance(baseline, (tuple, list)) or len(baseline) != 2:
-        raise ValueError(f"{who}: baseline must be 'zero' or a pair (derm, clinic) of tensors")
-    return baseline
-
-
-def _expand_baseline(b, x):
-    if b is None:
-        return torch.zeros((1,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
-    b = torch.as_tensor(b, dtype=torch.float32, device=x.device)
-    rows = x.shape[0] if b.dim() == 4 and b.shape[0] != 1 else 1
-    return torch.broadcast_to(b, (rows,) + tuple(x.shape[1:])).contiguous()
-
-
 class _Run:
     """The state shared by the two methods: engines, targets, accumulators, and the chunk loop."""
 
     def __init__(self, model, derm, clinic, target, who):
-        self.kind = _check(model, derm, clinic, "layer4", target, who)
+        self.sub = Subject(model, who).check(derm, clinic, target)
         if (derm.shape[2] * derm.shape[3]) % 4:
             raise ValueError(f"{who}: H * W must be a multiple of 4")
-        from .bridge import encoder_engine_for
-        _, enc_d, enc_c = _parts(model)
-        self.model, self.target = model, target
+        self.target, self.engs = target, self.sub.engs
         self.x = [derm.contiguous(), clinic.contiguous()]
-        self.engs = [encoder_engine_for(enc_d), encoder_engine_for(enc_c)]
         self.N, self.dev, self.T = derm.shape[0], derm.device, len(NUM_CLASSES)
 
     def forward_at(self, xs, measure=False):
         """(logits, target_class, saved bytes per image or 0) at the images xs (the targets: self.target)."""
         feats, saved = [], 0
         for eng, x in zip(self.engs, xs):
-            if measure:  # what one image's records hold, for the chunk planner
+            if measure:  # what one image's records hold, for the chunk planner: bound and laid out first, so only they count
                 eng.prepare(x.device)
                 eng.refresh_weights()
-                before = torch.cuda.memory_allocated(x.device)
-            f, ctx = eng.encoder_only("main", x, False, measure)
-            if measure:
-                saved = max(saved, (torch.cuda.memory_allocated(x.device) - before) // x.shape[0])
-            del ctx
+                f, bytes_ = forward_measured(eng, x)
+                saved = max(saved, bytes_)
+            else:
+                f, _ = eng.encoder_only("main", x, False, False)
             feats.append(f)
-        logits, tc, _ = _head_grads(self.kind, self.model, torch.cat(feats, dim=1), self.target)
-        return [o.float() for o in logits], tc, saved
+        logits, tc, _ = self.sub.head_grads(torch.cat(feats, dim=1), self.target)
+        return logits, tc, saved
 
     def accumulate(self, make_inputs, steps, chunk, weight, squared):
         """acc [2, T, N, 3, H, W] fp32: for every chunk [k0, k0 + c) make_inputs(m, k0, out [c, N, 3, H, W]) fills modality
@@ -103,35 +82,29 @@ class _Run:
         N, T, dev = self.N, self.T, self.dev
         shape = tuple(self.x[0].shape[1:])
         acc = torch.zeros((2, T, N) + shape, dtype=torch.float32, device=dev)
-        saved_g = [eng.store.flat_g for eng in self.engs]
-        try:
-            for k0 in range(0, steps, chunk):
-                c = min(chunk, steps - k0)
-                ctxs, feats = [], []
-                for m, eng in enumerate(self.engs):
-                    xin = torch.empty((c, N) + shape, dtype=torch.float32, device=dev)
-                    make_inputs(m, k0, xin)
-                    f, ctx = eng.encoder_only("main", xin.view((c * N,) + shape), False, True)
-                    ctxs.append(ctx), feats.append(f)
-                    del xin
-                _, _, dfeats = _head_grads(self.kind, self.model, torch.cat(feats, dim=1), self.tc.repeat(c, 1))
-                dx = torch.empty((c, N) + shape, dtype=torch.float32, device=dev)
-                off = 0
-                for m, (eng, ctx, f) in enumerate(zip(self.engs, ctxs, feats)):
-                    F_ = f.shape[1]
-                    # BatchNorm parameter gradients that the data-gradient launches accumulate go to a scratch buffer
-                    eng.store.flat_g = torch.zeros_like(saved_g[m])
+        for k0 in range(0, steps, chunk):
+            c = min(chunk, steps - k0)
+            ctxs, feats = [], []
+            for m, eng in enumerate(self.engs):
+                xin = torch.empty((c, N) + shape, dtype=torch.float32, device=dev)
+                make_inputs(m, k0, xin)
+                f, ctx = eng.encoder_only("main", xin.view((c * N,) + shape), False, True)
+                ctxs.append(ctx), feats.append(f)
+                del xin
+            _, _, dfeats = self.sub.head_grads(torch.cat(feats, dim=1), self.tc.repeat(c, 1))
+            dx = torch.empty((c, N) + shape, dtype=torch.float32, device=dev)
+            off = 0
+            for m, (eng, ctx, f) in enumerate(zip(self.engs, ctxs, feats)):
+                F_ = f.shape[1]
+                # BatchNorm parameter gradients that the data-gradient launches accumulate go to a scratch buffer
+                with scratch_grads(eng):
                     d = torch.empty(c * N, F_, dtype=eng.tdt, device=dev)
                     for t in range(T):
                         ops.cast_from_f32(eng.dtype, dfeats[t, :, off:off + F_].contiguous(), d)
                         eng.encoder_backward(ctx, d, last_view=True, dx_out=dx.view((c * N,) + shape), params=False)
                         ops.attr_accumulate(dx, acc[m, t], weight, squared)
-                    eng.store.flat_g = saved_g[m]
-                    off += F_
-                del ctxs, feats, dfeats, dx
-        finally:
-            for eng, g in zip(self.engs, saved_g):
-                eng.store.flat_g = g
+                off += F_
+            del ctxs, feats, dfeats, dx
         return acc
 
     def finish(self, acc, bases, mode):
@@ -158,10 +131,10 @@ def integrated_gradients(model, derm, clinic, target="pred", steps=32, baseline=
     who = "integrated_gradients"
     if not isinstance(steps, int) or steps < 1:
         raise ValueError(f"{who}: steps must be a positive integer")
-    pair = _baseline_images(baseline, derm, who)
+    pair = baseline_images(baseline, who)
     run = _Run(model, derm, clinic, target, who)
     with torch.no_grad(), ops.stream_scope():
-        bases = [_expand_baseline(None if pair is None else pair[m], run.x[m]) for m in range(2)]
+        bases = [expand_baseline(None if pair is None else pair[m], run.x[m]) for m in range(2)]
         logits, run.tc, saved = run.forward_at(run.x, measure=True)
         run.target = run.tc  # fixed at x
         N = run.N

@@ -3,6 +3,8 @@ bridge used by the drop-in `model(derm_imgs, clinic_imgs, style)` call contract,
 data-parallel detection.  Autograd is plumbing here: one Function spans the whole hot path; its backward
 runs our kernels and hands PyTorch finished parameter gradients (so DDP hooks, torch optimizers and
 GradScaler keep working unchanged)."""
+from contextlib import contextmanager
+
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -52,18 +54,25 @@ def _params(module):
     return [p for _, p in module.named_parameters()]
 
 
-def _scratch_backward(eng, fn, want_params=True):
-    """Run fn() with the engine's flat gradient buffer swapped for a zeroed scratch buffer; return (per-parameter
-    gradient views of the scratch (what autograd accumulates into .grad), fn's result).  want_params=False (a data-only
-    backward): the views are None -- what the backward still accumulates (BatchNorm parameter gradients that come out of
-    the data-gradient launches) stays in the scratch buffer and is dropped."""
+@contextmanager
+def scratch_grads(eng):
+    """Swap the engine's flat gradient buffer for a zeroed scratch buffer (yielded) while the body runs its backward passes:
+    what they accumulate -- in a data-only backward the BatchNorm parameter gradients that come out of the data-gradient
+    launches -- goes to the scratch and the engine's own buffer is left as it was."""
     scratch = torch.zeros_like(eng.store.flat_g)
     old = eng.store.flat_g
     eng.store.flat_g = scratch
     try:
-        out = fn()
+        yield scratch
     finally:
         eng.store.flat_g = old
+
+
+def _scratch_backward(eng, fn, want_params=True):
+    """Run fn() under scratch_grads; return (per-parameter gradient views of the scratch (what autograd accumulates into
+    .grad), fn's result).  want_params=False (a data-only backward): the views are None and the scratch is dropped."""
+    with scratch_grads(eng) as scratch:
+        out = fn()
     if not want_params:
         return [None] * len(eng.store.names), out
     return eng.store.grad_views(scratch), out

@@ -27,13 +27,11 @@ both curves: they are computed once ("logits", "baseline_logits") and the curves
 
 Everything runs under torch.no_grad: parameters, .grad fields, BatchNorm buffers and the engines' flat gradient buffers are left
 as they were.  The curves do not depend on the chunk (eval-mode rows are independent of batch position and batch size)."""
-from itertools import accumulate
-
 import torch
 
 from . import ops
-from .attr import _baseline_images, _expand_baseline, plan_chunk
-from .cam import _check, _mlc_heads, _parts, _target_class
+from .attr import plan_chunk
+from .explain import Subject, baseline_images, expand_baseline, forward_measured, target_class
 from .metrics import NUM_CLASSES
 
 MODES = ("both", "deletion", "insertion")
@@ -50,7 +48,7 @@ def counts(HW, steps):
 
 def _step_bytes(saved_bytes, E, T, perturbed):
     """Device bytes per curve step of one image pair: T masked fp32 inputs per perturbed modality and, as an upper bound of what
-    one image's eval forward holds at once, the size of the records a forward would save for it (measured as attr._Run does)."""
+    one image's eval forward holds at once, the size of the records a forward would save for it (explain.forward_measured)."""
     return T * perturbed * (4 * E + saved_bytes)
 
 
@@ -60,10 +58,7 @@ def _saved_bytes(eng, x):
     known = eng.__dict__.setdefault("_faith_saved_bytes", {})
     key = (eng.dtype, tuple(x.shape[1:]))
     if key not in known:
-        before = torch.cuda.memory_allocated(x.device)
-        _, ctx = eng.encoder_only("main", x, False, True)
-        known[key] = (torch.cuda.memory_allocated(x.device) - before) // x.shape[0]
-        del ctx
+        known[key] = forward_measured(eng, x)[1]
     return known[key]
 
 
@@ -83,30 +78,11 @@ def _check_maps(maps, derm, steps, who):
         raise ValueError(f"{who}: steps must be at most H * W = {HW}")
 
 
-def _logits(kind, model, feats):
-    """8 x [rows, n_i] fp32 at feature rows [rows, F]."""
-    if kind == "baseline":
-        return [clf(feats).float() for clf in model.classifier]  # stock PyTorch heads, as Baseline.forward runs them
-    heads = _mlc_heads(model)
-    _, out, _ = heads.forward(feats.contiguous(), 0, train=False)
-    return [o.float() for o in out.split(heads.sizes, dim=1)]
-
-
-def _target_probs(kind, model, feats, tc):
+def _target_probs(sub, feats, tc):
     """p [c, T, N] fp64 = softmax(logits_t.double())[tc[n, t]] at feats [c, T, N, F]: label t's logits of label t's rows only."""
-    c, T, N, F_ = feats.shape
+    c, T, N, _ = feats.shape
     p = torch.empty(c, T, N, dtype=torch.float64, device=feats.device)
-    if kind == "baseline":
-        for t, clf in enumerate(model.classifier):
-            lg = clf(feats[:, t].reshape(c * N, F_)).float()
-            p[:, t] = torch.softmax(lg.double(), dim=1).gather(1, tc[:, t].repeat(c)[:, None]).view(c, N)
-        return p
-    heads = _mlc_heads(model)
-    _, out, _ = heads.forward(feats.reshape(c * T * N, F_), 0, train=False)
-    out = out.view(c, T, N, -1)
-    off = [0] + list(accumulate(heads.sizes))
-    for t in range(T):
-        lg = out[:, t, :, off[t]:off[t + 1]].reshape(c * N, -1).float()
+    for t, lg in enumerate(sub.label_logits(feats)):
         p[:, t] = torch.softmax(lg.double(), dim=1).gather(1, tc[:, t].repeat(c)[:, None]).view(c, N)
     return p
 
@@ -151,28 +127,25 @@ def deletion_insertion(model, derm, clinic, maps, target="pred", steps=32, basel
         raise ValueError(f"{who}: modality must be one of {', '.join(MODALITIES)}, got {modality!r}")
     if chunk is not None and (not isinstance(chunk, int) or isinstance(chunk, bool) or not 1 <= chunk <= steps):
         raise ValueError(f"{who}: chunk must be None or an integer in [1, {steps}], got {chunk!r}")
-    pair = _baseline_images(baseline, derm, who)
+    pair = baseline_images(baseline, who)
     _check_maps(maps, derm, steps, who)
-    kind = _check(model, derm, clinic, "layer4", target, who)
+    sub = Subject(model, who).check(derm, clinic, target)
     if not maps.is_cuda:
         raise ValueError(f"{who}: maps must be a CUDA tensor (the SM3 HIP path has no CPU fallback)")
     N, _, H, W = derm.shape
     HW, T = H * W, len(NUM_CLASSES)
-    from .bridge import encoder_engine_for
-    _, enc_d, enc_c = _parts(model)
-    engs = [encoder_engine_for(enc_d), encoder_engine_for(enc_c)]
-    dev = derm.device
+    engs, dev = sub.engs, derm.device
     perturbed = [m for m, name in enumerate(MODALITIES[1:]) if modality in ("joint", name)]
     with torch.no_grad(), ops.stream_scope():
         x = [derm.contiguous(), clinic.contiguous()]
-        bases = [_expand_baseline(None if pair is None else pair[m], x[m]) for m in range(2)]
+        bases = [expand_baseline(None if pair is None else pair[m], x[m]) for m in range(2)]
         # steps 0 and S: the pair itself and the fully perturbed pair
         feats_x = [eng.encoder_only("main", xm, False, False)[0] for eng, xm in zip(engs, x)]
-        logits = _logits(kind, model, torch.cat(feats_x, dim=1))
-        tc = _target_class(logits, target, N, dev)
+        logits = sub.logits(torch.cat(feats_x, dim=1))
+        tc = target_class(logits, target, N, dev)
         feats_b = [engs[m].encoder_only("main", bases[m].expand_as(x[m]).contiguous(), False, False)[0] if m in perturbed
                    else feats_x[m] for m in range(2)]
-        base_logits = _logits(kind, model, torch.cat(feats_b, dim=1))
+        base_logits = sub.logits(torch.cat(feats_b, dim=1))
         ends = (_picked_probs(logits, tc), _picked_probs(base_logits, tc))  # [N, T] at k = 0 and k = S of the deletion curve
 
         ranks = torch.empty((N, T, 2, H, W), dtype=torch.int32, device=dev)
@@ -202,7 +175,7 @@ def deletion_insertion(model, derm, clinic, maps, target="pred", steps=32, basel
                         del xin
                     else:
                         feats.append(feats_x[m].repeat(n * T, 1))
-                p = _target_probs(kind, model, torch.cat(feats, dim=1).view(n, T, N, -1), tc)
+                p = _target_probs(sub, torch.cat(feats, dim=1).view(n, T, N, -1), tc)
                 curve[:, :, k0:k0 + n] = p.permute(2, 1, 0)
             out[name], out[name + "_auc"] = curve, auc(curve)
         out.update(ranks=ranks, logits=logits, baseline_logits=base_logits, target_class=tc, steps=steps, chunk=c,

@@ -15,7 +15,6 @@ synthetic, in the generated stream), layer.
 """
 import os
 import sys
-import time
 
 SCRIPT_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_PATH = os.path.split(SCRIPT_DIR)[0]
@@ -25,102 +24,38 @@ for _p in (ROOT_PATH, SCRIPT_DIR):
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in device memory: see sm3hip/__init__.py
 
-import torch  # noqa: E402
+import explain_cli as cli  # noqa: E402
+from sm3hip import cam  # noqa: E402
+from sm3hip.cam import STAGES  # noqa: E402
+from sm3hip.metrics import NUM_CLASSES  # noqa: E402
 
-import backbone_eval  # noqa: E402
-from backbone_saliency import load_linear  # noqa: E402
-from sm3hip.cam import STAGES, TARGETS  # noqa: E402
-from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES  # noqa: E402
+
+def add_cam_args(p):
+    cli.add_target_arg(p)
+    p.add_argument("--cam-layer", default="layer4", choices=STAGES, help="encoder stage whose output the maps weight")
+    return cli.add_cases_args(p)
 
 
 def get_parser():
-    p = backbone_eval.get_parser()
-    p.description = "SM3 Grad-CAM maps of a linear probe (MI355X)"
-    p.add_argument("--linear-path", type=str, default=None,
-                   help="backbone_eval's best_linear.pth (a Baseline state_dict); required with real data")
-    p.add_argument("--target", default="pred", choices=TARGETS,
-                   help="logit per label: pred = the argmax class, cls = the class AUC_AVG scores (CLS_WEIGHTS)")
-    p.add_argument("--cam-layer", default="layer4", choices=STAGES, help="encoder stage whose output the maps weight")
-    p.add_argument("--split", default="test", choices=("test", "valid"))
-    p.add_argument("--max-cases", default=64, type=int, help="cases of the split (or synthetic images) to map")
-    return p
+    return add_cam_args(cli.backbone_parser("SM3 Grad-CAM maps of a linear probe (MI355X)"))
 
 
-def run(model, data, target, layer):
-    """grad_cam over the batches of `data`; the collected outputs (CPU) and the seconds it took."""
-    from sm3hip.cam import grad_cam
-    maps, low, logits, targets, tcls = [], [], [[] for _ in NUM_CLASSES], [], []
-    torch.cuda.synchronize()
-    t0 = time.time()
-    for derm, clinic, lab in data:
-        out = grad_cam(model, derm, clinic, layer=layer, target=target)
-        maps.append(out["maps"].half().cpu())
-        low.append(out["low_res"].cpu())
-        for i, o in enumerate(out["logits"]):
-            logits[i].append(o.cpu())
-        targets.append(lab.cpu())
-        tcls.append(out["target_class"].cpu())
-    torch.cuda.synchronize()
-    return {"maps": torch.cat(maps), "low_res": torch.cat(low), "logits": [torch.cat(l) for l in logits],
-            "targets": torch.cat(targets), "target_class": torch.cat(tcls)}, time.time() - t0
+def per_batch(model, derm, clinic, lab, args):
+    out = cam.grad_cam(model, derm, clinic, layer=args.cam_layer, target=args.target)
+    return {"maps": out["maps"].half(), "low_res": out["low_res"], "logits": out["logits"], "targets": lab,
+            "target_class": out["target_class"]}
 
 
-def save(saved, args, seconds, tool):
-    os.makedirs(args.log_path, exist_ok=True)
-    torch.save(saved, os.path.join(args.log_path, "cam.pt"))
-    n = saved["maps"].shape[0]
-    stat = {"cases": n, "images_per_s": 2 * n / seconds, "seconds": seconds}  # derm + clinic
-    print(f"{tool} ({args.target}, {args.cam_layer}): {n} cases x {len(NUM_CLASSES)} labels, maps "
+def run(args, parser, tool, mlc):
+    saved, stat = cli.explain(args, parser, tool, mlc, per_batch, "cam.pt", target=args.target, layer=args.cam_layer)
+    print(f"{tool} ({args.target}, {args.cam_layer}): {stat['cases']} cases x {len(NUM_CLASSES)} labels, maps "
           f"{tuple(saved['maps'].shape)} | {stat['images_per_s']:.1f} images/s", flush=True)
     return stat
 
 
 def main(argv=None):
     parser = get_parser()
-    args = parser.parse_args(argv)
-    from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
-    require_baseline_arch(args.arch, "backbone_cam")
-    real = require_data(args, "backbone_cam")
-    if args.linear_path is not None and not os.path.isfile(args.linear_path):
-        raise SystemExit(f"backbone_cam: --linear-path {args.linear_path} does not exist")
-    if real and args.linear_path is None:
-        raise SystemExit("backbone_cam: --linear-path (backbone_eval's best_linear.pth) is required with real data")
-    if args.max_cases < 1:
-        raise SystemExit("backbone_cam: --max-cases must be at least 1")
-    if ignored_line(args, parser, real):
-        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
-    from src.models.baseline import Baseline
-    torch.manual_seed(args.seed)
-    dev = torch.device("cuda", 0)
-    gen = torch.Generator(device=dev).manual_seed(args.seed)
-    model = Baseline(args.arch, args.arch_weights)
-    if args.linear_path is not None:
-        load_linear(model, args.linear_path)
-        print(f"loaded linear probe from '{args.linear_path}'")
-    for m in (model.derm_backbone, model.clinic_backbone):
-        m.sm3_dtype = amp_dtype(args)
-    model.to(dev).eval()
-    if real:
-        from sm3hip.augment import chain
-        from sm3hip.imagestore import build_for
-        from src.utils.data.sampler import eval_batches
-        store = build_for(args, [args.split], dev)
-        split = store.splits[args.split]
-        n = min(args.max_cases, len(split))
-        aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
-        sels = [s[s < n] for s in eval_batches(len(split), args.batch_size)]
-        sels = [s for s in sels if s.numel()]
-        data = backbone_eval.real_batches(store, split, aug, sels, None, True)
-        indices = torch.cat(sels)
-    else:
-        n = args.max_cases
-        sizes = [min(args.batch_size, n - s) for s in range(0, n, args.batch_size)]
-        data = (backbone_eval.synthetic(b, args.img_sz, dev, gen) for b in sizes)
-        indices = torch.arange(n)
-    saved, seconds = run(model, data, args.target, args.cam_layer)
-    saved.update(indices=indices, target=args.target, layer=args.cam_layer, labels=list(CLASSES_NAME),
-                 split=args.split if real else "synthetic")
-    return save(saved, args, seconds, "backbone_cam")
+    return run(parser.parse_args(argv), parser, "backbone_cam", False)
 
 
 if __name__ == "__main__":

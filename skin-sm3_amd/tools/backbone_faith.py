@@ -16,7 +16,6 @@ AUC say that the map is faithful.
 """
 import os
 import sys
-import time
 
 SCRIPT_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_PATH = os.path.split(SCRIPT_DIR)[0]
@@ -28,69 +27,18 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 
 import torch  # noqa: E402
 
-import backbone_attr  # noqa: E402
-import backbone_eval  # noqa: E402
-from backbone_saliency import load_linear  # noqa: E402
-from sm3hip.cam import STAGES  # noqa: E402
-from sm3hip.faith import MODALITIES, MODES  # noqa: E402
+import explain_cli as cli  # noqa: E402
+from sm3hip import attr, cam, faith  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES  # noqa: E402
-
-METHODS = ("cam", "ig", "smoothgrad", "random")
-
-
-def add_faith_args(p):
-    """The flags the two faithfulness tools share: those of the attribution tools, --cam-layer and the curve's own."""
-    backbone_attr.add_attr_args(p, method_help="how the maps are made: " + ", ".join(METHODS),
-                                chunk_help="curve steps per encoder forward (default: from the free device memory); any value "
-                                           "gives the same bits")
-    p.set_defaults(method="cam")
-    p.add_argument("--cam-layer", default="layer4", help="cam: encoder stage whose output the maps weight (layer1 .. layer4)")
-    p.add_argument("--curve-steps", default=32, type=int, help="steps of the deletion / insertion curves (at most H * W)")
-    p.add_argument("--curve-mode", default="both", help="both, deletion or insertion")
-    p.add_argument("--modality", default="joint", help="joint (both images perturbed, each by its own map), derm or clinic")
-    return p
-
-
-def check_faith_args(args, tool, size):
-    """Refusals that need no device.  size: (H, W) of the images."""
-    if args.method not in METHODS:
-        raise SystemExit(f"{tool}: --method {args.method} is not available (one of {', '.join(METHODS)})")
-    if args.max_cases < 1:
-        raise SystemExit(f"{tool}: --max-cases must be at least 1")
-    hw = size[0] * size[1]
-    if hw % 4:
-        raise SystemExit(f"{tool}: the image's H * W ({size[0]} x {size[1]}) must be a multiple of 4")
-    if not 1 <= args.curve_steps <= hw:
-        raise SystemExit(f"{tool}: --curve-steps must be between 1 and H * W ({hw})")
-    if args.chunk is not None and not 1 <= args.chunk <= args.curve_steps:
-        raise SystemExit(f"{tool}: --chunk must be between 1 and --curve-steps ({args.curve_steps})")
-    if args.curve_mode not in MODES:
-        raise SystemExit(f"{tool}: --curve-mode {args.curve_mode} is not available (one of {', '.join(MODES)})")
-    if args.modality not in MODALITIES:
-        raise SystemExit(f"{tool}: --modality {args.modality} is not available (one of {', '.join(MODALITIES)})")
-    if args.method == "cam" and args.cam_layer not in STAGES:
-        raise SystemExit(f"{tool}: --cam-layer {args.cam_layer} is not available (one of {', '.join(STAGES)})")
-    if args.method == "ig" and args.steps < 1:
-        raise SystemExit(f"{tool}: --steps must be at least 1")
-    if args.method == "smoothgrad" and args.samples < 1:
-        raise SystemExit(f"{tool}: --samples must be at least 1")
-    if args.method == "smoothgrad" and args.sigma < 0:
-        raise SystemExit(f"{tool}: --sigma must be non-negative")
-    if args.attr_seed < 0:
-        raise SystemExit(f"{tool}: --attr-seed must be non-negative")
 
 
 def get_parser():
-    p = backbone_eval.get_parser()
-    p.description = "SM3 deletion / insertion faithfulness curves of a linear probe's attribution maps (MI355X)"
-    p.add_argument("--linear-path", type=str, default=None,
-                   help="backbone_eval's best_linear.pth (a Baseline state_dict); required with real data")
-    return add_faith_args(p)
+    return cli.add_faith_args(cli.backbone_parser(
+        "SM3 deletion / insertion faithfulness curves of a linear probe's attribution maps (MI355X)"))
 
 
 def make_maps(model, derm, clinic, args, gen):
     """(maps [N, 8, 2, H, W] fp32 on the images' device, target for the curves) by --method; gen: the CPU generator of random."""
-    from sm3hip import attr, cam
     if args.method == "random":
         N, _, H, W = derm.shape
         return torch.rand(N, len(NUM_CLASSES), 2, H, W, generator=gen).to(derm.device), args.target
@@ -104,39 +52,25 @@ def make_maps(model, derm, clinic, args, gen):
     return out["maps"], out["target_class"]  # the curves follow the classes the maps explain
 
 
-def run(model, data, args):
-    """Maps, then curves, over the batches of `data`; the collected outputs (CPU) and the seconds it took."""
-    from sm3hip import faith
-    gen = torch.Generator().manual_seed(args.attr_seed)
-    curves = [n for n in ("deletion", "insertion") if args.curve_mode in ("both", n)]
-    keys = curves + [n + "_auc" for n in curves]
-    got = {k: [] for k in keys + ["targets", "target_class"]}
-    logits, base_logits = [[] for _ in NUM_CLASSES], [[] for _ in NUM_CLASSES]
-    torch.cuda.synchronize()
-    t0 = time.time()
-    for derm, clinic, lab in data:
-        maps, target = make_maps(model, derm, clinic, args, gen)
+def run(args, parser, tool, mlc):
+    """Maps, then curves, batch by batch; the report of the mean AUCs."""
+    gens = []  # the CPU generator of --method random: made at the first batch, after every refusal
+
+    def per_batch(model, derm, clinic, lab, args):
+        if not gens:
+            gens.append(torch.Generator().manual_seed(args.attr_seed))
+        maps, target = make_maps(model, derm, clinic, args, gens[0])
         out = faith.deletion_insertion(model, derm, clinic, maps, target=target, steps=args.curve_steps, modality=args.modality,
                                        mode=args.curve_mode, chunk=args.chunk)
-        for k in keys:
-            got[k].append(out[k].cpu())
-        for i in range(len(NUM_CLASSES)):
-            logits[i].append(out["logits"][i].cpu())
-            base_logits[i].append(out["baseline_logits"][i].cpu())
-        got["targets"].append(lab.cpu())
-        got["target_class"].append(out["target_class"].cpu())
-    torch.cuda.synchronize()
-    saved = {k: torch.cat(v) for k, v in got.items()}
-    saved.update(logits=[torch.cat(l) for l in logits], baseline_logits=[torch.cat(l) for l in base_logits])
-    return saved, time.time() - t0
+        curves = [n for n in ("deletion", "insertion") if args.curve_mode in ("both", n)]
+        got = {k: out[k] for k in curves + [n + "_auc" for n in curves]}
+        got.update(targets=lab, target_class=out["target_class"], logits=out["logits"], baseline_logits=out["baseline_logits"])
+        return got
 
-
-def save(saved, args, seconds, tool):
-    os.makedirs(args.log_path, exist_ok=True)
-    torch.save(saved, os.path.join(args.log_path, "faith.pt"))
-    n = saved["target_class"].shape[0]
-    stat = {"cases": n, "images_per_s": 2 * n / seconds, "seconds": seconds}  # derm + clinic
-    print(f"{tool} ({args.method}, {args.target}, {args.modality}, {args.curve_steps} curve steps): {n} cases x "
+    saved, stat = cli.explain(args, parser, tool, mlc, per_batch, "faith.pt",
+                              check=lambda a, t: cli.check_faith_args(a, t, cli.image_size(a, mlc)), target=args.target,
+                              method=args.method, modality=args.modality, curve_steps=args.curve_steps)
+    print(f"{tool} ({args.method}, {args.target}, {args.modality}, {args.curve_steps} curve steps): {stat['cases']} cases x "
           f"{len(NUM_CLASSES)} labels | {stat['images_per_s']:.2f} images/s", flush=True)
     for name in ("deletion", "insertion"):
         if name + "_auc" in saved:
@@ -149,49 +83,7 @@ def save(saved, args, seconds, tool):
 
 def main(argv=None):
     parser = get_parser()
-    args = parser.parse_args(argv)
-    from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
-    require_baseline_arch(args.arch, "backbone_faith")
-    check_faith_args(args, "backbone_faith", tuple(args.img_sz))
-    real = require_data(args, "backbone_faith")
-    if args.linear_path is not None and not os.path.isfile(args.linear_path):
-        raise SystemExit(f"backbone_faith: --linear-path {args.linear_path} does not exist")
-    if real and args.linear_path is None:
-        raise SystemExit("backbone_faith: --linear-path (backbone_eval's best_linear.pth) is required with real data")
-    if ignored_line(args, parser, real):
-        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
-    from src.models.baseline import Baseline
-    torch.manual_seed(args.seed)
-    dev = torch.device("cuda", 0)
-    gen = torch.Generator(device=dev).manual_seed(args.seed)
-    model = Baseline(args.arch, args.arch_weights)
-    if args.linear_path is not None:
-        load_linear(model, args.linear_path)
-        print(f"loaded linear probe from '{args.linear_path}'")
-    for m in (model.derm_backbone, model.clinic_backbone):
-        m.sm3_dtype = amp_dtype(args)
-    model.to(dev).eval()
-    if real:
-        from sm3hip.augment import chain
-        from sm3hip.imagestore import build_for
-        from src.utils.data.sampler import eval_batches
-        store = build_for(args, [args.split], dev)
-        split = store.splits[args.split]
-        n = min(args.max_cases, len(split))
-        aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
-        sels = [s[s < n] for s in eval_batches(len(split), args.batch_size)]
-        sels = [s for s in sels if s.numel()]
-        data = backbone_eval.real_batches(store, split, aug, sels, None, True)
-        indices = torch.cat(sels)
-    else:
-        n = args.max_cases
-        sizes = [min(args.batch_size, n - s) for s in range(0, n, args.batch_size)]
-        data = (backbone_eval.synthetic(b, args.img_sz, dev, gen) for b in sizes)
-        indices = torch.arange(n)
-    saved, seconds = run(model, data, args)
-    saved.update(indices=indices, target=args.target, method=args.method, modality=args.modality, curve_steps=args.curve_steps,
-                 labels=list(CLASSES_NAME), split=args.split if real else "synthetic")
-    return save(saved, args, seconds, "backbone_faith")
+    return run(parser.parse_args(argv), parser, "backbone_faith", False)
 
 
 if __name__ == "__main__":

@@ -16,7 +16,6 @@ split; with --data-name synthetic, in the generated stream).
 """
 import os
 import sys
-import time
 
 SCRIPT_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_PATH = os.path.split(SCRIPT_DIR)[0]
@@ -28,29 +27,15 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 
 import torch  # noqa: E402
 
-import backbone_eval  # noqa: E402
-from sm3hip.metrics import CLASSES_NAME, CLS_WEIGHTS, NUM_CLASSES  # noqa: E402
-
-TARGETS = ("pred", "cls")
+import explain_cli as cli  # noqa: E402
+from explain_cli import load_linear  # noqa: E402,F401  (kept reachable as backbone_saliency.load_linear)
+from sm3hip.explain import target_class  # noqa: E402
+from sm3hip.metrics import NUM_CLASSES  # noqa: E402
 
 
 def get_parser():
-    p = backbone_eval.get_parser()
-    p.description = "SM3 per-label input-gradient maps of a linear probe (MI355X)"
-    p.add_argument("--linear-path", type=str, default=None,
-                   help="backbone_eval's best_linear.pth (a Baseline state_dict); required with real data")
-    p.add_argument("--target", default="pred", choices=TARGETS,
-                   help="logit per label: pred = the argmax class, cls = the class AUC_AVG scores (CLS_WEIGHTS)")
-    p.add_argument("--split", default="test", choices=("test", "valid"))
-    p.add_argument("--max-cases", default=64, type=int, help="cases of the split (or synthetic images) to map")
-    return p
-
-
-def load_linear(model, path):
-    """backbone_eval's best_linear.pth ({"state_dict": ...}) or a bare state_dict; a "module." prefix is dropped."""
-    state = torch.load(path, map_location="cpu")
-    state = state.get("state_dict", state)
-    model.load_state_dict({(k[7:] if k.startswith("module.") else k): v for k, v in state.items()})
+    p = cli.backbone_parser("SM3 per-label input-gradient maps of a linear probe (MI355X)")
+    return cli.add_cases_args(cli.add_target_arg(p))
 
 
 def saliency_batch(model, derm, clinic, target_class):
@@ -66,76 +51,20 @@ def saliency_batch(model, derm, clinic, target_class):
     return torch.stack(maps, dim=1)
 
 
+def per_batch(model, derm, clinic, lab, args):
+    with torch.no_grad():
+        outs = model([derm, clinic])
+    tc = target_class(outs, args.target, derm.shape[0], derm.device)
+    return {"maps": saliency_batch(model, derm, clinic, tc).half(), "logits": [o.float() for o in outs], "targets": lab,
+            "target_class": tc}
+
+
 def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
-    from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
-    require_baseline_arch(args.arch, "backbone_saliency")
-    real = require_data(args, "backbone_saliency")
-    if args.linear_path is not None and not os.path.isfile(args.linear_path):
-        raise SystemExit(f"backbone_saliency: --linear-path {args.linear_path} does not exist")
-    if real and args.linear_path is None:
-        raise SystemExit("backbone_saliency: --linear-path (backbone_eval's best_linear.pth) is required with real data")
-    if args.max_cases < 1:
-        raise SystemExit("backbone_saliency: --max-cases must be at least 1")
-    if ignored_line(args, parser, real):
-        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
-    from src.models.baseline import Baseline
-    torch.manual_seed(args.seed)
-    dev = torch.device("cuda", 0)
-    gen = torch.Generator(device=dev).manual_seed(args.seed)
-    model = Baseline(args.arch, args.arch_weights)
-    if args.linear_path is not None:
-        load_linear(model, args.linear_path)
-        print(f"loaded linear probe from '{args.linear_path}'")
-    for p in model.parameters():
-        p.requires_grad_(False)
-    for m in (model.derm_backbone, model.clinic_backbone):
-        m.sm3_dtype = amp_dtype(args)
-    model.to(dev).eval()
-    if real:
-        from sm3hip.augment import chain
-        from sm3hip.imagestore import build_for
-        from src.utils.data.sampler import eval_batches
-        store = build_for(args, [args.split], dev)
-        split = store.splits[args.split]
-        n = min(args.max_cases, len(split))
-        aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
-        sels = [s[s < n] for s in eval_batches(len(split), args.batch_size)]
-        sels = [s for s in sels if s.numel()]
-        data = backbone_eval.real_batches(store, split, aug, sels, None, True)
-        indices = torch.cat(sels)
-    else:
-        n = args.max_cases
-        sizes = [min(args.batch_size, n - s) for s in range(0, n, args.batch_size)]
-        data = (backbone_eval.synthetic(b, args.img_sz, dev, gen) for b in sizes)
-        indices = torch.arange(n)
-    maps, logits, targets, tcls = [], [[] for _ in NUM_CLASSES], [], []
-    torch.cuda.synchronize()
-    t0 = time.time()
-    for derm, clinic, lab in data:
-        with torch.no_grad():
-            outs = model([derm, clinic])
-        if args.target == "pred":
-            tc = torch.stack([o.argmax(dim=1) for o in outs], dim=1)
-        else:
-            tc = torch.tensor(CLS_WEIGHTS, dtype=torch.long, device=dev).expand(derm.shape[0], -1).contiguous()
-        maps.append(saliency_batch(model, derm, clinic, tc).half().cpu())
-        for i, o in enumerate(outs):
-            logits[i].append(o.float().cpu())
-        targets.append(lab.cpu())
-        tcls.append(tc.cpu())
-    torch.cuda.synchronize()
-    seconds = time.time() - t0
-    maps = torch.cat(maps)
-    saved = {"maps": maps, "logits": [torch.cat(l) for l in logits], "targets": torch.cat(targets),
-             "target_class": torch.cat(tcls), "indices": indices, "target": args.target, "labels": list(CLASSES_NAME),
-             "split": args.split if real else "synthetic"}
-    os.makedirs(args.log_path, exist_ok=True)
-    torch.save(saved, os.path.join(args.log_path, "saliency.pt"))
-    stat = {"cases": maps.shape[0], "images_per_s": 2 * maps.shape[0] / seconds, "seconds": seconds}  # derm + clinic
-    print(f"saliency ({args.target}): {maps.shape[0]} cases x {len(NUM_CLASSES)} labels, maps "
-          f"{tuple(maps.shape)} | {stat['images_per_s']:.1f} images/s", flush=True)
+    saved, stat = cli.explain(args, parser, "backbone_saliency", False, per_batch, "saliency.pt", freeze=True, target=args.target)
+    print(f"saliency ({args.target}): {stat['cases']} cases x {len(NUM_CLASSES)} labels, maps "
+          f"{tuple(saved['maps'].shape)} | {stat['images_per_s']:.1f} images/s", flush=True)
     return stat
 
 

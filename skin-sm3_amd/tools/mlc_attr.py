@@ -20,68 +20,18 @@ for _p in (ROOT_PATH, SCRIPT_DIR):
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in device memory: see sm3hip/__init__.py
 
-import torch  # noqa: E402
-
 import backbone_attr  # noqa: E402
-import backbone_eval  # noqa: E402
-import mlc_cam  # noqa: E402
-import mlc_eval  # noqa: E402
-from sm3hip.metrics import CLASSES_NAME  # noqa: E402
+import explain_cli as cli  # noqa: E402
 
 
 def get_parser():
-    p = mlc_eval.get_parser()
-    p.description = "SM3 Integrated Gradients / SmoothGrad attributions of the multi-label model (MI355X)"
-    p.add_argument("--checkpoint", type=str, default=None,
-                   help="a checkpoint inference.py loads (best_linear.pth / best_finetune.pth); required with real data")
-    p.set_defaults(log_path="./logs/mlc_attr")
-    return backbone_attr.add_attr_args(p)
+    return cli.add_attr_args(cli.mlc_parser(
+        "SM3 Integrated Gradients / SmoothGrad attributions of the multi-label model (MI355X)", "./logs/mlc_attr"))
 
 
 def main(argv=None):
     parser = get_parser()
-    args = parser.parse_args(argv)
-    from src.utils.misc import amp_dtype, require_data, require_mlc_arch, require_mlc_proj
-    require_mlc_arch(args.arch, "mlc_attr")
-    require_mlc_proj(args, "mlc_attr")
-    backbone_attr.check_attr_args(args, "mlc_attr")
-    real = require_data(args, "mlc_attr")
-    if args.checkpoint is not None and not os.path.isfile(args.checkpoint):
-        raise SystemExit(f"mlc_attr: --checkpoint {args.checkpoint} does not exist")
-    if real and args.checkpoint is None:
-        raise SystemExit("mlc_attr: --checkpoint (a best_linear.pth / best_finetune.pth) is required with real data")
-    torch.manual_seed(args.seed)
-    dev = torch.device("cuda", 0)
-    gen = torch.Generator(device=dev).manual_seed(args.seed)
-    model = mlc_cam.build(args)
-    if args.checkpoint is not None:
-        mlc_cam.load_checkpoint(model, args.checkpoint)
-        print(f"loaded model weights from '{args.checkpoint}'")
-    for m in (model.extractor.derm_backbone, model.extractor.clinic_backbone):
-        m.sm3_dtype = amp_dtype(args)
-    model.to(dev).eval()
-    size = (args.test_sz, args.test_sz)
-    if real:
-        from sm3hip.augment import chain
-        from sm3hip.imagestore import build_for
-        from src.utils.data.sampler import eval_batches
-        store = build_for(args, [args.split], dev)
-        split = store.splits[args.split]
-        n = min(args.max_cases, len(split))
-        aug = chain("mlc_eval", size, args.mean, args.std)
-        sels = [s[s < n] for s in eval_batches(len(split), args.batch_size)]
-        sels = [s for s in sels if s.numel()]
-        data = backbone_eval.real_batches(store, split, aug, sels, None, True)
-        indices = torch.cat(sels)
-    else:
-        n = args.max_cases
-        sizes = [min(args.batch_size, n - s) for s in range(0, n, args.batch_size)]
-        data = (mlc_eval.synthetic(b, size, dev, gen) for b in sizes)
-        indices = torch.arange(n)
-    saved, seconds = backbone_attr.run(model, data, args)
-    saved.update(indices=indices, target=args.target, method=args.method, labels=list(CLASSES_NAME),
-                 split=args.split if real else "synthetic", mlc_proj=args.mlc_proj)
-    return backbone_attr.save(saved, args, seconds, "mlc_attr")
+    return backbone_attr.run(parser.parse_args(argv), parser, "mlc_attr", True)
 
 
 if __name__ == "__main__":
