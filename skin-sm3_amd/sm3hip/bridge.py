@@ -32,7 +32,7 @@ def _configure_sync(module, eng):
         if eng.stat_sync is None:
             eng.world_size = dist.get_world_size()
             eng.stat_sync = lambda t: dist.all_reduce(t)
-    elif eng.__dict__.get("_explicit_sync") is None:
+    elif eng._explicit_sync is None:
         eng.stat_sync, eng.world_size = None, 1
 
 

@@ -14,147 +14,24 @@ Data layout in HBM
   gradients     one flat fp32 buffer with the same offsets (weight gradients are accumulated into it
                 by the wgrad kernel, so the two views of a step simply add up)
   per-step      `dtype` copies of every filter bank in forward order and in data-gradient order
+
+What describes the network and holds nothing per step -- the parameter store, the units, the form a block takes, the records
+a forward pass saves -- is in sm3hip/plan.py.
 """
-import math
+import os
 from collections import OrderedDict
+from contextlib import contextmanager
 
 import torch
 
 from . import ops
-from ._lib import SM3_BF16, SM3_F16, SM3_F32
+from ._lib import SM3_BF16, SM3_F16
+from .plan import (TWO_PASS, BlockRec, EncoderCtx, ParamStore, ProjectorPlan, Rec, block_form, enc_mod_out_dim, enc_plan,
+                   stage_of)
+from .plan import EncoderPlan  # noqa: F401  (re-exported: the tests import it from here, as they do ParamStore)
 
-import os as _os
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
-RESNET50_LAYERS = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))
-
-
-# ------------------------------------------------------------------------------------------
-# flat parameter / gradient storage
-# ------------------------------------------------------------------------------------------
-class ParamStore:
-    """All parameters of a module in one flat fp32 buffer (64-byte aligned slots); parameters become
-    views, conv weights with channels_last strides so their memory is [Cout][kh][kw][Cin]."""
-
-    def __init__(self, module, device):
-        self.module = module
-        self.device = device
-        self.names, self.offsets, self.shapes = [], {}, {}
-        off = 0
-        for name, p in module.named_parameters():
-            self.names.append(name)
-            self.offsets[name] = off
-            self.shapes[name] = tuple(p.shape)
-            off += (p.numel() + 15) // 16 * 16
-        self.total = off
-        self.flat_p = torch.zeros(off, dtype=torch.float32, device=device)
-        self.flat_g = torch.zeros(off, dtype=torch.float32, device=device)
-        self._bind()
-
-    def _view(self, flat, name):
-        shape = self.shapes[name]
-        n = math.prod(shape) if shape else 1
-        v = flat[self.offsets[name]: self.offsets[name] + n]
-        if len(shape) == 4:
-            o, i, h, w = shape
-            return v.view(o, h, w, i).permute(0, 3, 1, 2)  # OIHW shape, OHWI memory
-        return v.view(shape)
-
-    def _bind(self):
-        params = dict(self.module.named_parameters())
-        with torch.no_grad():
-            for name in self.names:
-                p = params[name]
-                v = self._view(self.flat_p, name)
-                v.copy_(p.data.to(device=self.device, dtype=torch.float32))
-                p.data = v
-                p.grad = None
-        self._ptrs = {n: params[n].data_ptr() for n in self.names}
-
-    def bound(self):
-        params = dict(self.module.named_parameters())
-        return all(params[n].data_ptr() == self._ptrs[n] and params[n].device == self.flat_p.device
-                   for n in self.names)
-
-    def rebind_if_needed(self):
-        if not self.bound():
-            self._bind()
-
-    def flat2d(self, flat, name):
-        """[Cout, taps*Cin] (conv / linear) or [C] view of a slot."""
-        shape = self.shapes[name]
-        n = math.prod(shape)
-        v = flat[self.offsets[name]: self.offsets[name] + n]
-        return v.view(shape[0], -1) if len(shape) >= 2 else v
-
-    def grad_views(self, flat=None):
-        flat = self.flat_g if flat is None else flat
-        return [self._view(flat, n) for n in self.names]
-
-
-# ------------------------------------------------------------------------------------------
-# layer units
-# ------------------------------------------------------------------------------------------
-class ConvUnit:
-    """groups > 1: a grouped 3x3 convolution (ResNeXt conv2, Ci == Co) on the kernels of csrc/gconv.hip, whose banks are
-    [9][Co / groups][Co] in forward and in data-gradient order (sm3_gconv_weight_prep); none of the dense-kernel forms
-    (halo-resident A image, nine-tap owner weight gradient, fused data-gradient epilogues) applies to it.
-    The stem unit (stem=True) only holds the direct stem's filter bank (csrc/stem.hip); its kernels take no descriptor."""
-
-    def __init__(self, name, Ci, Co, k, stride, pad, stem=False, groups=1):
-        self.name, self.Ci, self.Co, self.k, self.stride, self.pad, self.stem = name, Ci, Co, k, stride, pad, stem
-        self.groups = groups
-        if groups > 1 and (k != 3 or pad != 1 or Ci != Co or stem):
-            raise ValueError("grouped convolutions: 3x3, pad 1, Ci == Co only")
-        self.taps = k * k
-        self.w_fwd = self.w_dgrad = None
-        self._fd, self._dd = {}, {}
-
-    def alloc(self, dtype, device, need_dgrad=True):
-        tdt = ops.TORCH_DTYPE[dtype]
-        if self.stem:
-            self.w_fwd = torch.empty(self.Co, ops.STEM_KDIRECT, dtype=tdt, device=device)
-        elif self.groups > 1:
-            n = self.taps * self.Co * (self.Ci // self.groups)
-            self.w_fwd = torch.empty(n, dtype=tdt, device=device)
-            self.w_dgrad = torch.empty(n, dtype=tdt, device=device)
-        else:
-            self.w_fwd = torch.empty(self.Co, self.taps * self.Ci, dtype=tdt, device=device)
-            if need_dgrad:
-                self.w_dgrad = torch.empty(self.Ci, self.taps, self.Co, dtype=tdt, device=device)
-
-    def refresh(self, dtype, master2d):
-        if self.groups > 1:
-            ops.gconv_weight_prep(dtype, master2d, self.Co, self.groups, self.w_fwd, self.w_dgrad)
-        else:
-            ops.weight_prep(dtype, master2d, self.Co, self.taps, self.Ci, self.w_fwd, self.taps * self.Ci,
-                            self.w_dgrad)
-
-    def fwd_desc(self, dtype, N, H, W):
-        key = (dtype, N, H, W)
-        if key not in self._fd:
-            self._fd[key] = ops.fwd_desc(dtype, N, H, W, self.Ci, self.Co, self.k, self.stride, self.pad)
-        return self._fd[key]
-
-    def compact_dgrad_desc(self, dtype, N, Hs, Ws):
-        """Data gradient of a 1x1 / stride-2 convolution at the pixels it touches only: a plain GEMM over the
-        [N, Hs, Ws, Co] output gradient with the transposed filter bank."""
-        key = ("cdg", dtype, N, Hs, Ws)
-        if key not in self._dd:
-            self._dd[key] = ops.fwd_desc(dtype, N, Hs, Ws, self.Co, self.Ci, 1, 1, 0)
-        return self._dd[key]
-
-    def dgrad_descs(self, dtype, N, H, W):
-        key = (dtype, N, H, W)
-        if key not in self._dd:
-            self._dd[key] = ops.dgrad_descs(dtype, N, H, W, self.Ci, self.Co, self.k, self.stride, self.pad)
-        return self._dd[key]
-
-
-class BNUnit:
-    def __init__(self, name, C, affine=True):
-        self.name, self.C, self.affine = name, C, affine
-
 
 
 _LANE_POOL = {}
@@ -174,7 +51,7 @@ def lane_stream_pool(device, n):
     pool = _LANE_POOL.setdefault(idx, [])
     if len(pool) >= n:
         return pool[:n]
-    if _os.environ.get("SM3_STREAM_CALIBRATE", "1") == "0" or not hasattr(torch.cuda, "_sleep"):
+    if os.environ.get("SM3_STREAM_CALIBRATE", "1") == "0" or not hasattr(torch.cuda, "_sleep"):
         pool.extend(torch.cuda.Stream(device=device) for _ in range(n - len(pool)))
         return pool[:n]
     import time
@@ -208,102 +85,21 @@ def lane_stream_pool(device, n):
     return pool[:n]
 
 
-class Rec:
-    """What one conv+BN(+act) application saves for backward."""
-    __slots__ = ("cu", "bu", "N", "H", "W", "Ho", "Wo", "x_in", "xo", "mean", "invstd", "y", "relu", "mask", "V",
-                 "frozen_stats", "scale", "shift", "colsum", "linbn", "gram", "Tm", "in_s")
-
-
-class EncoderPlan:
-    """Units of a torchvision ResNet encoder.  block="bottleneck": c1 (1x1) / b1, c2 (3x3, stride s) / b2, c3 (1x1, x4) /
-    b3 per block; block="basic" (resnet18/34): c1 (3x3, stride s) / b1, c2 (3x3) / b2.  cd / bd (1x1 downsample, stride
-    s) where the block changes the stride or the width (reference resnet.py:251-262) -- every stage entry of a Bottleneck
-    network, layer2..4 of a BasicBlock one.  The last unit of a block is always its join (bn + identity + ReLU)."""
-
-    def __init__(self, prefix, block_counts=(3, 4, 6, 3), block="bottleneck", groups=1, width_per_group=64):
-        """groups / width_per_group (Bottleneck only): a ResNeXt -- c1 / c2 / c3 are inplanes -> width -> width -> 4 * planes,
-        width = int(planes * width_per_group / 64) * groups, c2 grouped (reference resnet.py:142-148)."""
-        if block not in ("bottleneck", "basic"):
-            raise ValueError(block)
-        if block == "basic" and (groups != 1 or width_per_group != 64):
-            raise ValueError("BasicBlock only supports groups=1 and base_width=64")
-        self.prefix = prefix
-        self.basic = block == "basic"
-        self.stem = ConvUnit(prefix + "conv1", 3, 64, 7, 2, 3, stem=True)
-        self.stem_bn = BNUnit(prefix + "bn1", 64)
-        self.blocks = []
-        exp = 1 if self.basic else 4
-        inpl = 64
-        for li, ((planes, _, stride), nblocks) in enumerate(zip(RESNET50_LAYERS, block_counts), start=1):
-            for b in range(nblocks):
-                p = f"{prefix}layer{li}.{b}."
-                s = stride if b == 0 else 1
-                if self.basic:
-                    blk = {
-                        "c1": ConvUnit(p + "conv1", inpl, planes, 3, s, 1), "b1": BNUnit(p + "bn1", planes),
-                        "c2": ConvUnit(p + "conv2", planes, planes, 3, 1, 1), "b2": BNUnit(p + "bn2", planes),
-                    }
-                else:
-                    wd = int(planes * (width_per_group / 64.0)) * groups
-                    blk = {
-                        "c1": ConvUnit(p + "conv1", inpl, wd, 1, 1, 0), "b1": BNUnit(p + "bn1", wd),
-                        "c2": ConvUnit(p + "conv2", wd, wd, 3, s, 1, groups=groups), "b2": BNUnit(p + "bn2", wd),
-                        "c3": ConvUnit(p + "conv3", wd, planes * 4, 1, 1, 0), "b3": BNUnit(p + "bn3", planes * 4),
-                    }
-                if s != 1 or inpl != planes * exp:
-                    blk["cd"] = ConvUnit(p + "downsample.0", inpl, planes * exp, 1, s, 0)
-                    blk["bd"] = BNUnit(p + "downsample.1", planes * exp)
-                    inpl = planes * exp
-                self.blocks.append(blk)
-        self.out_dim = inpl
-
-    def conv_units(self):
-        yield self.stem
-        for blk in self.blocks:
-            for k in ("c1", "c2", "c3", "cd"):
-                if k in blk:
-                    yield blk[k]
-
-
-class ProjectorPlan:
-    def __init__(self, prefix, in_dim, proj_dim):
-        self.prefix = prefix
-        self.l0 = ConvUnit(prefix + "0", in_dim, in_dim, 1, 1, 0)
-        self.b1 = BNUnit(prefix + "1", in_dim)
-        self.l3 = ConvUnit(prefix + "3", in_dim, in_dim, 1, 1, 0)
-        self.b4 = BNUnit(prefix + "4", in_dim)
-        self.l6 = ConvUnit(prefix + "6", in_dim, proj_dim, 1, 1, 0)
-        self.b7 = BNUnit(prefix + "7", proj_dim, affine=False)
-
-    def conv_units(self):
-        return (self.l0, self.l3, self.l6)
-
 
 # ------------------------------------------------------------------------------------------
 # the engine
 # ------------------------------------------------------------------------------------------
-def enc_mod_out_dim(enc_mod):
-    """Width of the pooled features of a src.models.resnet.ResNet: 512 (BasicBlock) or 2048 (Bottleneck)."""
-    return 512 if enc_block(enc_mod) == "basic" else 512 * 4
-
-
-def enc_block(enc_mod):
-    return getattr(enc_mod, "block_type", "bottleneck")
-
-
-def enc_plan(prefix, enc_mod):
-    """The EncoderPlan of a src.models.resnet.ResNet: block type, block counts, groups and width per group from the module."""
-    return EncoderPlan(prefix, enc_mod.block_counts, enc_block(enc_mod), getattr(enc_mod, "groups", 1),
-                       getattr(enc_mod, "base_width", 64))
-
-
 class SM3Engine:
     """Runs SimCLRSkinV3 / V32 (and a bare encoder) on the HIP kernels.
 
     module      the nn.Module that owns the parameters/buffers (src.models.simclr.SimCLRSkinV32 mirror)
-    dtype       torch.bfloat16 (MFMA bf16, fp32 accumulate) or torch.float32 (exact-f32 MFMA)
+    dtype       torch.bfloat16 / torch.float16 (16-bit MFMA, fp32 accumulate) or torch.float32 (exact-f32 MFMA)
+    kind        see __init__
+
+    Attributes the caller sets after construction:
     stat_sync   None, or a callable(t: fp64 CUDA tensor) that sums t over data-parallel ranks in place
                 (SyncBatchNorm semantics, tools/backbone_train.py:510); world_size scales the counts.
+    grad_ready  None, or a callback(first_param_name, last_param_name) for gradient-bucket overlap
     """
 
     def __init__(self, module, dtype=torch.bfloat16, kind="v32"):
@@ -316,8 +112,8 @@ class SM3Engine:
         self.store = None
         self.stat_sync = None
         self.world_size = 1
-        self.grad_ready = None  # callback(first_param_name, last_param_name) for gradient-bucket overlap
-        self.fuse_bn_bwd = True  # BN-backward phase 1 inside the data-gradient epilogue (sm3_conv_dgrad_bnfuse)
+        self.grad_ready = None
+        self._explicit_sync = None  # True: stat_sync was installed by a trainer, the bridge leaves it alone
         self.branches = OrderedDict()
         self.cross = None
         self.meta = None
@@ -343,30 +139,39 @@ class SM3Engine:
             self.branches["main"] = (enc_plan("", module), None)
         else:
             raise ValueError(kind)
+        self.buffers = None  # the module's named buffers (prepare)
         self._ws = {}
         self._allocated = False
         self._lane = "main"
-        self._V = 1  # views in the batch of the encoder pass being enqueued (1, or 2 back to back)
+        self._V = 1  # views in the batch of the encoder pass being enqueued: 2 back to back in a train-mode pair pass, else 1
+        self._data_only = False  # inside a data-only backward: no weight gradient, no gradient-ready notification
+        self._no_stat_update = False  # momentum-target pass (set by the trainer): batch statistics, buffers untouched
+        self.weights_dirty = True  # the masters were rewritten behind the engine's back: refresh_weights skips its hash
+        self._wprep_cache, self._wprep_key, self._hash_tracks_banks = {}, None, False  # refresh_weights
+        self._lane_prep = {}  # filter-bank jobs that refresh_weights left to prep_lane
+        self._lin_descs = {}
+        self.last_feats = None  # fp32 pooled features of the latest bridge forward, per branch
+        self._faith_saved_bytes = {}  # sm3hip.faith: bytes of saved records per image, by (dtype, image shape)
         # Both views of a branch through the encoder as ONE batch of 2B images -- half the convolution /
         # weight-gradient / BatchNorm launches, longer K loops per weight-gradient workgroup, one SyncBN statistics
         # all-reduce per BatchNorm for both views -- with BatchNorm statistics still per view (simclr.py:58-59).
         # Needs every feature map of a view to be a multiple of 128 rows (B a multiple of 128 at 224x224).
-        self.pair_views = _os.environ.get("SM3_PAIR_VIEWS", "1") != "0"
+        self.pair_views = os.environ.get("SM3_PAIR_VIEWS", "1") != "0"
         self.two_streams = True
         self._streams, self._streams_dev = None, None
         # The 7x7 stem reads the NCHW images directly (csrc/stem.hip): no im2col matrix, BN-backward apply fused into the
         # stem weight gradient; 16-bit MFMA in the throughput modes, v_mfma_f32_32x32x2_f32 in the exact-f32 mode.
         # BatchNorm backward by linearity for conv3 -> bn3 of every Bottleneck (csrc/linbn.hip): no bn3 backward-apply
         # pass and no backward read of conv3's output.  16-bit modes only; the exact-f32 parity mode keeps two passes.
-        self.linbn = self.dtype in (SM3_BF16, SM3_F16) and _os.environ.get("SM3_LINBN", "1") != "0"
+        self.linbn = self.dtype in (SM3_BF16, SM3_F16) and os.environ.get("SM3_LINBN", "1") != "0"
         # ... and, for the blocks without a downsample branch, the forward half of it: bn3's batch statistics from the
         # moments of conv3's input, bn3 + residual + ReLU inside conv3's epilogue -- conv3's output never reaches HBM
-        self.linbn_fwd = _os.environ.get("SM3_LINBN_FWD", "1") != "0"
+        self.linbn_fwd = os.environ.get("SM3_LINBN_FWD", "1") != "0"
         # ... and the downsample conv -> BatchNorm of a stage's first block in the backward pass
-        self.linbn_ds = _os.environ.get("SM3_LINBN_DS", "1") != "0"
-        self.linbn_join = _os.environ.get("SM3_LINBN_JOIN", "1") != "0"
-        self.linbn_merge = _os.environ.get("SM3_LINBN_MERGE", "1") != "0"  # banks + post in one launch (A/B switch)
-        self.lane_cross = _os.environ.get("SM3_LANE_CROSS", "1") != "0"  # cross-modal projector passes inside the lanes
+        self.linbn_ds = os.environ.get("SM3_LINBN_DS", "1") != "0"
+        self.linbn_join = os.environ.get("SM3_LINBN_JOIN", "1") != "0"
+        self.linbn_merge = os.environ.get("SM3_LINBN_MERGE", "1") != "0"  # banks + post in one launch (A/B switch)
+        self.lane_cross = os.environ.get("SM3_LANE_CROSS", "1") != "0"  # cross-modal projector passes inside the lanes
         if self.cross is not None and self.cross[0] is self.cross[1]:
             # SimCLRSkinV3: ONE cross projector for both modalities -- inside the lanes its parameter gradients would receive
             # the two modalities' addends in whichever order the streams run; on the main stream the order is the program's
@@ -374,10 +179,10 @@ class SM3Engine:
         # Weight gradients as functions of their inputs (round 6): every split-K product of the step is combined by a
         # fixed-order sum of plain-store slabs (sm3_conv_wgrad_det, sm3_stem_wgrad_bn with slabs) instead of float atomics,
         # so two runs of a training produce the same bits.  SM3_WGRAD_DET=0: the atomic forms (A/B switch).
-        self.det_wgrad = _os.environ.get("SM3_WGRAD_DET", "1") != "0"
+        self.det_wgrad = os.environ.get("SM3_WGRAD_DET", "1") != "0"
         # 16-bit modes: direct stem kernels on images rounded once per step and staged by LDS-DMA (sm3_stem_image_prep,
         # sm3_stem_conv_fwd16, sm3_stem_wgrad_bn16; bit-identical to the fp32-image kernels).  SM3_STEM16=0: the round-3 kernels.
-        self.stem16 = self.dtype in (SM3_BF16, SM3_F16) and _os.environ.get("SM3_STEM16", "1") != "0"
+        self.stem16 = self.dtype in (SM3_BF16, SM3_F16) and os.environ.get("SM3_STEM16", "1") != "0"
 
     # ---- setup ---------------------------------------------------------------------------
     def _all_conv_units(self):
@@ -416,7 +221,7 @@ class SM3Engine:
         prep_lane(key), called at the head of that branch's lane -- the two launches then overlap instead of both lanes
         waiting for one launch over everything."""
         key = (self.store.flat_p.data_ptr(), len(self.store.names), self.dtype)
-        cache = self.__dict__.setdefault("_wprep_cache", {})
+        cache = self._wprep_cache
         if key not in cache:
             groups = {k: ([], [], []) for k in list(self.branches) + [None]}
             for cu in self._all_conv_units():
@@ -442,9 +247,9 @@ class SM3Engine:
         # miss `p.data` writes and raw-pointer kernels, a stale bank would be a silent error.  A caller that knows it just
         # rewrote the masters (the fused optimizer step) sets weights_dirty and skips the hash.
         only_if = None
-        if not self.__dict__.get("weights_dirty", True) and self.__dict__.get("_wprep_key") == key:
+        if not self.weights_dirty and self._wprep_key == key:
             ops.weights_changed(self.store.flat_p, hstate, changed)
-            if self.__dict__.get("_hash_tracks_banks", False):
+            if self._hash_tracks_banks:
                 only_if = changed
             self._hash_tracks_banks = True  # from here on the hash state is that of the masters the banks were made from
         else:
@@ -467,7 +272,7 @@ class SM3Engine:
 
     def prep_lane(self, key):
         """The filter banks of branch `key`, on the current (= that branch's lane) stream; see refresh_weights."""
-        job = self.__dict__.get("_lane_prep", {}).pop(key, None)
+        job = self._lane_prep.pop(key, None)
         if job is not None:
             self._prep(*job)
 
@@ -540,10 +345,49 @@ class SM3Engine:
     def _g(self, name):
         return self.store.flat2d(self.store.flat_g, name)
 
+    def _bn_affine(self, bu, grad=False):
+        """(weight, bias) of a BatchNorm unit in the flat parameter buffer, or (grad=True) their slots in the flat gradient
+        buffer; (None, None) for a unit without affine parameters."""
+        if not bu.affine:
+            return None, None
+        view = self._g if grad else self._p
+        return view(bu.name + ".weight"), view(bu.name + ".bias")
+
+    def _bn_finalize(self, bu, sums, count, scale, shift, mean, invstd, groups, V):
+        """Batch sums -> scale / shift / mean / invstd of a train-mode BatchNorm, and its running statistics -- which a
+        momentum-target pass leaves untouched."""
+        gamma, beta = self._bn_affine(bu)
+        rm = rv = nbt = None
+        if not self._no_stat_update:
+            rm, rv = self.buffers[bu.name + ".running_mean"], self.buffers[bu.name + ".running_var"]
+            nbt = self.buffers[bu.name + ".num_batches_tracked"]
+        ops.bn_finalize(sums, count, bu.C, gamma, beta, BN_EPS, BN_MOMENTUM, rm, rv, nbt, scale, shift, mean, invstd,
+                        groups=groups, views=V)
+
+    @contextmanager
+    def _views(self, V):
+        """The encoder pass enqueued inside holds V views back to back."""
+        self._V = V
+        try:
+            yield
+        finally:
+            self._V = 1
+
+    @contextmanager
+    def _params_backward(self, params):
+        """params=False: the backward pass enqueued inside is data-only (and stays so inside an enclosing data-only one)."""
+        prev = self._data_only
+        self._data_only = prev or not params
+        try:
+            yield
+        finally:
+            self._data_only = prev
+
     # ---- conv + BN (+residual) (+ReLU) ---------------------------------------------------
-    def conv_bn(self, cu, bu, x, N, H, W, relu, residual=None, train=True, save=None, out_f32=False, y_out=None,
+    def conv_bn(self, cu, bu, x, N, H, W, relu, residual=None, train=True, save=False, out_f32=False, y_out=None,
                 apply=True, scale_shift=None, res_affine=None, pending=None, colsum=None):
-        """One conv + BatchNorm (+residual) (+ReLU) unit on N images.  With self._V == 2 the batch is two views back
+        """One conv + BatchNorm (+residual) (+ReLU) unit on N images -> (output, Ho, Wo, its Rec if `save` else None).
+        With self._V == 2 the batch is two views back
         to back (N = 2B): one convolution launch, BatchNorm statistics / running-statistics updates per view.
         apply=False: stop after the statistics -- returns the pre-BatchNorm tensor, scale/shift are left in
         `scale_shift` for the consumer that applies them (the join of a downsample block, the stem's fused
@@ -568,22 +412,21 @@ class SM3Engine:
         xo = torch.empty(rows, C, dtype=self.tdt, device=dev)
         scale, shift = scale_shift if scale_shift is not None else (self._work("scale", 2 * 2048),
                                                                     self._work("shift", 2 * 2048))
-        gamma = self._p(bu.name + ".weight") if bu.affine else None
-        beta = self._p(bu.name + ".bias") if bu.affine else None
-        rm, rv = self.buffers[bu.name + ".running_mean"], self.buffers[bu.name + ".running_var"]
-        track = not self.__dict__.get("_no_stat_update", False)  # momentum-target pass: batch statistics, buffers untouched
         mean = invstd = None
-        if train:
-            prow = ops.stem_partial_rows(N, H, W) if direct else ops.conv_partial_rows(d)
-            if V > 1 and ((rows_v % 128 and not direct) or prow % V):
-                raise ValueError("two views in one batch need a multiple of 128 rows per view")
-            partials = self._work("partials", prow * 2 * C)
+
+        def convolve(partials):  # -> xo; partials: the per-tile BatchNorm sums come with it
             if direct:
                 (ops.stem_conv_fwd16 if isinstance(x, ops.StemImage) else ops.stem_conv_fwd)(self.dtype, x, cu.w_fwd, xo, partials)
             elif cu.groups > 1:
                 ops.gconv_fwd(self.dtype, x, cu.w_fwd, xo, partials, N, H, W, C, cu.groups, cu.stride)
             else:
                 ops.conv_gemm(d, x, cu.w_fwd, xo, None, partials)
+        if train:
+            prow = ops.stem_partial_rows(N, H, W) if direct else ops.conv_partial_rows(d)
+            if V > 1 and ((rows_v % 128 and not direct) or prow % V):
+                raise ValueError("two views in one batch need a multiple of 128 rows per view")
+            partials = self._work("partials", prow * 2 * C)
+            convolve(partials)
             count, groups = rows_v, 1
             mean = torch.empty(V * C, dtype=torch.float32, device=dev)
             invstd = torch.empty(V * C, dtype=torch.float32, device=dev)
@@ -613,30 +456,24 @@ class SM3Engine:
                 sums, groups = ops.bn_stats_reduce(partials, prow // V, C, None, views=V)
 
             def finalize(sums=sums, groups=groups):
-                ops.bn_finalize(sums, count, C, gamma, beta, BN_EPS, BN_MOMENTUM, rm if track else None,
-                                rv if track else None,
-                                self.buffers[bu.name + ".num_batches_tracked"] if track else None,
-                                scale, shift, mean, invstd, groups=groups, views=V)
+                self._bn_finalize(bu, sums, count, scale, shift, mean, invstd, groups, V)
             if deferred:
                 pending.append((V * 2 * C, finalize))
             else:
                 finalize()
-        elif save is None and not out_f32 and apply and cu.groups == 1:
-            # inference: conv + running-statistics BN (+residual) (+ReLU) in ONE launch, no pre-BN tensor in HBM
-            # (a grouped unit takes the two-pass form below: grouped convolution, then the BatchNorm apply pass)
-            if y_out is None:
-                y_out = xo
-            ops.conv_bn_eval(d, x, cu.w_fwd, gamma, beta, rm, rv, BN_EPS, residual, relu, y_out)
-            return y_out, Ho, Wo
         else:
-            if direct:
-                (ops.stem_conv_fwd16 if isinstance(x, ops.StemImage) else ops.stem_conv_fwd)(self.dtype, x, cu.w_fwd, xo, None)
-            elif cu.groups > 1:
-                ops.gconv_fwd(self.dtype, x, cu.w_fwd, xo, None, N, H, W, C, cu.groups, cu.stride)
-            else:
-                ops.conv_gemm(d, x, cu.w_fwd, xo, None, None)
+            gamma, beta = self._bn_affine(bu)
+            rm, rv = self.buffers[bu.name + ".running_mean"], self.buffers[bu.name + ".running_var"]
+            if not save and not out_f32 and apply and cu.groups == 1:
+                # inference: conv + running-statistics BN (+residual) (+ReLU) in ONE launch, no pre-BN tensor in HBM
+                # (a grouped unit takes the two-pass form below: grouped convolution, then the BatchNorm apply pass)
+                if y_out is None:
+                    y_out = xo
+                ops.conv_bn_eval(d, x, cu.w_fwd, gamma, beta, rm, rv, BN_EPS, residual, relu, y_out)
+                return y_out, Ho, Wo, None
+            convolve(None)
             ops.bn_eval_scale_shift(gamma, beta, rm, rv, BN_EPS, C, scale, shift)
-            if save is not None:
+            if save:
                 # eval-mode BatchNorm inside an autograd graph (module.eval() with trainable parameters): the statistics
                 # are constants, so backward is dx = gamma * invstd * dz and d(gamma), d(beta) are the plain sums --
                 # bn_backward runs the same kernels with the batch-statistics terms zeroed (Rec.frozen_stats)
@@ -647,52 +484,50 @@ class SM3Engine:
         else:
             if y_out is None:
                 y_out = torch.empty(rows, C, dtype=torch.float32 if out_f32 else self.tdt, device=dev)
-            if save is not None and relu:  # 1 bit per element of (y > 0): what backward needs instead of re-reading y
+            if save and relu:  # 1 bit per element of (y > 0): what backward needs instead of re-reading y
                 mask = torch.empty(rows * C // (16 // ops._sz(self.dtype)), dtype=torch.uint8, device=dev)
             cs = None
             if res_affine is not None:
                 ops.bn_add_bn_act(self.dtype, xo, scale, shift, residual, res_affine[0], res_affine[1], relu, y_out,
                                   rows_v, C, mask=mask, views=V)
             else:
-                if colsum is not None and save is not None and train and not out_f32:
+                if colsum is not None and save and train and not out_f32:
                     cs = colsum  # += column sums of this unit's output: first moment of the next convolution's input (linbn)
                 ops.bn_act(self.dtype, xo, scale, shift, residual, relu, y_out, rows_v, C, out_f32=out_f32, mask=mask,
                            views=V, colsum=cs)
-        if save is not None:
-            r = Rec()
-            r.cu, r.bu, r.N, r.H, r.W, r.Ho, r.Wo = cu, bu, N, H, W, Ho, Wo
-            r.x_in, r.xo, r.mean, r.invstd, r.y, r.relu, r.mask = x, xo, mean, invstd, y_out, relu, mask
-            r.V = V
-            r.frozen_stats = not train
-            r.scale = r.shift = None
-            r.colsum = cs if apply else None
-            r.linbn = False
-            r.gram = r.Tm = None
-            save.append(r)
-        return (y_out if apply else xo), Ho, Wo
+        r = None
+        if save:
+            r = Rec(cu, bu, N, H, W, Ho, Wo, x_in=x, xo=xo, mean=mean, invstd=invstd, y=y_out, relu=relu, mask=mask, V=V,
+                    frozen_stats=not train, colsum=cs if apply else None)
+        return (y_out if apply else xo), Ho, Wo, r
+
+    def _phase1(self, r, dy, fused_rows):
+        """Phase 1 of unit r's BatchNorm backward: (rows per view, partial sums [V][rows][2][C] of (dz, dz * xhat)).
+        fused_rows None: one pass over dy, which masks it in place when the unit has a ReLU; otherwise dy came out of a
+        data-gradient launch that masked it and left `fused_rows` rows in the "fz_partials" workspace
+        (conv_backward(..., fuse=r))."""
+        if fused_rows is not None:
+            return fused_rows, self._ws[(self._lane, "fz_partials")]
+        C, V = r.cu.Co, r.V
+        rows = r.N * r.Ho * r.Wo // V
+        prow = ops.bn_bwd_partial_rows(rows, C)
+        bpart = self._work("partials", V * prow * 2 * C)
+        ops.bn_bwd_reduce(self.dtype, dy, None, r.xo, r.mean, r.invstd, dy if r.relu else None, rows, C, bpart,
+                          mask=r.mask if r.relu else None, views=V)
+        return prow, bpart
 
     def bn_backward(self, r, dy, keep_dz, fused_rows=None):
-        """dy: gradient w.r.t. the unit's output (post-activation).  Masks it in place when the unit has a
-        ReLU.  Returns (gradient w.r.t. the conv output, dz = masked dy).  fused_rows: dy was produced by a
-        data-gradient launch that already masked it and left `fused_rows` rows of partial sums in the
-        "fz_partials" workspace (conv_backward(..., fuse=r)): phase 1 is skipped."""
+        """dy: gradient w.r.t. the unit's output (post-activation), masked in place by the unit's ReLU (_phase1).
+        Returns (gradient w.r.t. the conv output, dz = masked dy)."""
         C = r.cu.Co
         V = r.V
         rows = r.xo.shape[0] // V  # per view
-        if fused_rows is None:
-            prow = ops.bn_bwd_partial_rows(rows, C)
-            bpart = self._work("partials", V * prow * 2 * C)
-            ops.bn_bwd_reduce(self.dtype, dy, None, r.xo, r.mean, r.invstd, dy if r.relu else None, rows, C, bpart,
-                              mask=r.mask if r.relu else None, views=V)
-        else:  # [V][fused_rows][2][C], left by the data-gradient launches
-            prow, bpart = fused_rows, self._ws[(self._lane, "fz_partials")]
+        prow, bpart = self._phase1(r, dy, fused_rows)
         lsums, gsums, count = self._bn_backward_sums(r, bpart, prow)
         dxo = torch.empty_like(r.xo) if keep_dz else dy
-        gamma = self._p(r.bu.name + ".weight") if r.bu.affine else None
-        dgamma = self._g(r.bu.name + ".weight") if r.bu.affine else None
-        dbeta = self._g(r.bu.name + ".bias") if r.bu.affine else None
-        ops.bn_bwd_apply(self.dtype, dy, r.xo, r.mean, r.invstd, gamma, gsums, count, lsums, dgamma, dbeta, dxo,
-                         rows, C, views=V)
+        dgamma, dbeta = self._bn_affine(r.bu, grad=True)
+        ops.bn_bwd_apply(self.dtype, dy, r.xo, r.mean, r.invstd, self._bn_affine(r.bu)[0], gsums, count, lsums, dgamma, dbeta,
+                         dxo, rows, C, views=V)
         return dxo, dy
 
     def _bn_backward_sums(self, r, bpart, prow):
@@ -720,12 +555,7 @@ class SM3Engine:
         Returns (d conv3 output, d downsample-conv output)."""
         C, V = r3.cu.Co, r3.V
         rows = r3.xo.shape[0] // V
-        if fused_rows is None:
-            prow = ops.bn_bwd_partial_rows(rows, C)
-            bpart = self._work("partials", V * prow * 2 * C)
-            ops.bn_bwd_reduce(self.dtype, dy, None, r3.xo, r3.mean, r3.invstd, dy, rows, C, bpart, mask=r3.mask, views=V)
-        else:
-            prow, bpart = fused_rows, self._ws[(self._lane, "fz_partials")]
+        prow, bpart = self._phase1(r3, dy, fused_rows)
         n = V * 2 * C
         lsums = self._work("lsums2", 2 * 2 * 2 * 2048, torch.float64)  # [bn3 | downsample][V][2C]
         ops.bn_stats_reduce(bpart, prow, C, lsums, views=V)
@@ -745,21 +575,12 @@ class SM3Engine:
         dx3 = torch.empty_like(r3.xo)
 
         def side(r, g, l, dx):
-            aff = r.bu.affine
-            return dict(x=r.xo, mean=r.mean, invstd=r.invstd, gamma=self._p(r.bu.name + ".weight") if aff else None,
-                        gsums=g, lsums=l, dgamma=self._g(r.bu.name + ".weight") if aff else None,
-                        dbeta=self._g(r.bu.name + ".bias") if aff else None, dx=dx)
+            dgamma, dbeta = self._bn_affine(r.bu, grad=True)
+            return dict(x=r.xo, mean=r.mean, invstd=r.invstd, gamma=self._bn_affine(r.bu)[0], gsums=g, lsums=l,
+                        dgamma=dgamma, dbeta=dbeta, dx=dx)
         ops.bn_bwd_apply2(self.dtype, dy, count, side(r3, gsums[:n], lsums[:n], dx3),
                           side(rd, gsums[n: 2 * n], lsums[n: 2 * n], dy), rows, C, views=V)
         return dx3, dy
-
-    def _lin_desc(self, dtype, M, K, N):
-        """Descriptor of a plain [M, K] x [N, K]^T product through the gather-GEMM."""
-        cache = self.__dict__.setdefault("_lin_descs", {})
-        key = (dtype, M, K, N)
-        if key not in cache:
-            cache[key] = ops.fwd_desc(dtype, M, 1, 1, K, N, 1, 1, 0)
-        return cache[key]
 
     def _slab_buf(self, n, V):
         """Workspace for a plain-store split-K launch (ops.conv_wgrad_slabs): up to SLAB_CAP slabs of n floats per view,
@@ -770,17 +591,17 @@ class SM3Engine:
     def _lin_conv_desc(self, dtype, N, H, W, Ci, Co):
         """Descriptor of a 1x1 / stride-1 convolution Ci -> Co over an [N, H, W] map (weight-gradient-kernel launches
         that are not tied to a ConvUnit: the Gram matrix of an activation)."""
-        cache = self.__dict__.setdefault("_lin_descs", {})
+        cache = self._lin_descs
         key = ("conv", dtype, N, H, W, Ci, Co)
         if key not in cache:
             cache[key] = ops.fwd_desc(dtype, N, H, W, Ci, Co, 1, 1, 0)
         return cache[key]
 
-    def conv3_bn3_fused(self, cu, bu, r2, y2, idn, N, H, W, save):
+    def conv3_bn3_fused(self, cu, bu, r2, y2, idn, N, H, W):
         """conv3 -> bn3 (train mode) -> + identity -> ReLU of a Bottleneck (resnet.py:162-172) without its pre-BatchNorm
         tensor: bn3's batch sums are linear / quadratic forms of the moments of y2 (r2.colsum = sum y2, r2.gram =
         y2^T y2; sm3_linbn_fwd_stats), so its scale / shift are known BEFORE conv3 runs and conv3 applies them, the residual
-        and the ReLU in its own epilogue (sm3_conv_bn_act_fused)."""
+        and the ReLU in its own epilogue (sm3_conv_bn_act_fused).  Returns (y3, Ho, Wo, conv3's Rec)."""
         dev = y2.device
         C, p, V = cu.Co, cu.Ci, self._V
         d = cu.fwd_desc(self.dtype, N, H, W)
@@ -803,34 +624,20 @@ class SM3Engine:
         scale, shift = self._work("scale", 2 * 2048), self._work("shift", 2 * 2048)
         mean = torch.empty(V * C, dtype=torch.float32, device=dev)
         invstd = torch.empty(V * C, dtype=torch.float32, device=dev)
-        track = not self.__dict__.get("_no_stat_update", False)
-        ops.bn_finalize(ws, count, C, self._p(bu.name + ".weight") if bu.affine else None,
-                        self._p(bu.name + ".bias") if bu.affine else None, BN_EPS, BN_MOMENTUM,
-                        self.buffers[bu.name + ".running_mean"] if track else None,
-                        self.buffers[bu.name + ".running_var"] if track else None,
-                        self.buffers[bu.name + ".num_batches_tracked"] if track else None,
-                        scale, shift, mean, invstd, groups=groups, views=V)
+        self._bn_finalize(bu, ws, count, scale, shift, mean, invstd, groups, V)
         y3 = torch.empty(rows, C, dtype=self.tdt, device=dev)
         mask = torch.empty(rows * C // (16 // ops._sz(self.dtype)), dtype=torch.uint8, device=dev)
         ops.conv_bn_act_fused(d, y2, cu.w_fwd, scale, shift, idn, True, y3, mask, views=V)
-        r = Rec()
-        r.cu, r.bu, r.N, r.H, r.W, r.Ho, r.Wo = cu, bu, N, H, W, d.Ho, d.Wo
-        r.x_in, r.xo, r.mean, r.invstd, r.y, r.relu, r.mask = y2, None, mean, invstd, y3, True, mask
-        r.V = V
-        r.frozen_stats = False
-        r.scale = r.shift = None
-        r.colsum = r.gram = None
-        r.linbn = True
-        r.Tm = Tm
-        save.append(r)
-        return y3, d.Ho, d.Wo
+        return y3, d.Ho, d.Wo, Rec(cu, bu, N, H, W, d.Ho, d.Wo, x_in=y2, mean=mean, invstd=invstd, y=y3, relu=True, mask=mask,
+                                   V=V, linbn=True, Tm=Tm)
 
-    def join_fused(self, blk, r2, y2, cur, N, h, w, h2, w2, save):
+    def join_fused(self, blk, r2, y2, cur, N, h, w, h2, w2):
         """The whole join of a Bottleneck with a downsample branch -- conv3 -> bn3, downsample conv -> its BatchNorm, add,
         ReLU (resnet.py:162-172) -- as ONE two-segment GEMM over [y2 | strided block input]: both units' batch statistics
         come from input moments (sm3_linbn_fwd_stats; data parallel: one exchange for the two), their scales go into the
         filter banks and their shifts into the column bias (sm3_linbn_scale_banks).  Neither pre-BatchNorm tensor exists;
-        the compact block input and its moments are kept for the backward pass."""
+        the compact block input and its moments are kept for the backward pass.
+        Returns (y3, h2, w2, the downsample unit's Rec, conv3's Rec)."""
         dev = y2.device
         c3, b3, cd, bd = blk["c3"], blk["b3"], blk["cd"], blk["bd"]
         C, p, Cin, V = c3.Co, c3.Ci, cd.Ci, self._V
@@ -838,20 +645,7 @@ class SM3Engine:
         rows_v = M // V
         if V > 1 and rows_v % 128:
             raise ValueError("two views in one batch need a multiple of 128 rows per view")
-        # moments of the (strided) block input
-        crow = ops.subsample_colsum_rows(self.dtype, rows_v, Cin)
-        csd = self._work("linbn_cs", V * crow * Cin)
-        if cd.stride == 1:
-            in_s = cur
-            ops.subsample_colsum(self.dtype, cur, None, csd, N, h, w, Cin, 1, V)
-        else:
-            in_s = torch.empty(M, Cin, dtype=self.tdt, device=dev)
-            ops.subsample_colsum(self.dtype, cur, in_s, csd, N, h, w, Cin, cd.stride, V)
-        slabs, cap = self._slab_buf(Cin * Cin, V)
-        ns = ops.conv_wgrad_slabs(self._lin_conv_desc(self.dtype, N, h2, w2, Cin, Cin), in_s, in_s, slabs, views=V, cap=cap)
-        Gd = torch.empty(V * Cin * Cin, dtype=torch.float32, device=dev)
-        sd = torch.empty(V * Cin, dtype=torch.float64, device=dev)
-        ops.linbn_moments(slabs, ns, Cin * Cin, Gd, views=V, colsum=csd, colsum_rows=crow, s_out=sd, p=Cin)
+        in_s, Gd, sd = self._strided_input_moments(cd, cur, N, h, w, h2, w2, V, keep=True)
         # batch statistics of both units
         g3, gd = p // 32, Cin // 32
         n3, nd = V * g3 * 2 * C, V * gd * 2 * C
@@ -871,18 +665,12 @@ class SM3Engine:
             self.stat_sync(gs[: 2 * nf])
             units = ((b3, gs[:nf], 1, ""), (bd, gs[nf: 2 * nf], 1, "_d"))
             count = rows_v * self.world_size
-        track = not self.__dict__.get("_no_stat_update", False)
         out = []
         for bu, wsl, groups, tag in units:
             scale, shift = self._work("scale" + tag, 2 * 2048), self._work("shift" + tag, 2 * 2048)
             mean = torch.empty(V * C, dtype=torch.float32, device=dev)
             invstd = torch.empty(V * C, dtype=torch.float32, device=dev)
-            ops.bn_finalize(wsl, count, C, self._p(bu.name + ".weight") if bu.affine else None,
-                            self._p(bu.name + ".bias") if bu.affine else None, BN_EPS, BN_MOMENTUM,
-                            self.buffers[bu.name + ".running_mean"] if track else None,
-                            self.buffers[bu.name + ".running_var"] if track else None,
-                            self.buffers[bu.name + ".num_batches_tracked"] if track else None,
-                            scale, shift, mean, invstd, groups=groups, views=V)
+            self._bn_finalize(bu, wsl, count, scale, shift, mean, invstd, groups, V)
             out.append((scale, shift, mean, invstd))
         (sc3, sh3, mean3, inv3), (scd, shd, meand, invd) = out
         w3s = self._work("linbn_w3s", V * C * p, self.tdt)
@@ -893,17 +681,32 @@ class SM3Engine:
         mask = torch.empty(M * C // (16 // ops._sz(self.dtype)), dtype=torch.uint8, device=dev)
         ops.conv_seg_act(self._lin_conv_desc(self.dtype, N, h2, w2, p, C), y2, w3s, in_s, wds, bias, y3, mask, True,
                          views=V, w_view_stride=C * p, w1_view_stride=C * Cin)
-        rd, r3 = Rec(), Rec()
-        for r in (rd, r3):
-            r.N, r.Ho, r.Wo, r.V, r.frozen_stats, r.linbn = N, h2, w2, V, False, True
-            r.scale = r.shift = r.xo = r.colsum = r.gram = r.in_s = None
-        rd.cu, rd.bu, rd.H, rd.W, rd.x_in, rd.mean, rd.invstd, rd.y, rd.relu, rd.mask = cd, bd, h, w, cur, meand, invd, None, False, None
-        rd.in_s, rd.gram, rd.colsum, rd.Tm = in_s, Gd, sd, Tmd
-        r3.cu, r3.bu, r3.H, r3.W, r3.x_in, r3.mean, r3.invstd, r3.y, r3.relu, r3.mask = c3, b3, h2, w2, y2, mean3, inv3, y3, True, mask
-        r3.Tm = Tm3
-        save.append(rd)
-        save.append(r3)
-        return y3, h2, w2
+        rd = Rec(cd, bd, N, h, w, h2, w2, x_in=cur, mean=meand, invstd=invd, V=V, linbn=True, in_s=in_s, gram=Gd, colsum=sd,
+                 Tm=Tmd)
+        r3 = Rec(c3, b3, N, h2, w2, h2, w2, x_in=y2, mean=mean3, invstd=inv3, y=y3, relu=True, mask=mask, V=V, linbn=True,
+                 Tm=Tm3)
+        return y3, h2, w2, rd, r3
+
+    def _strided_input_moments(self, cd, x, N, h, w, hs, ws, V, keep):
+        """Moments of a block's input x [N, h, w, Cin] at the pixels its downsample convolution cd reads -> (in_s, Gd, sd): the
+        compact input [N * hs * ws, Cin] (x itself at stride 1), its Gram matrix [V][Cin][Cin] and its column sums [V][Cin]
+        (fp64).  keep: Gd / sd are fresh tensors, for a saved record to hold until the backward pass (join_fused);
+        otherwise lane workspaces, good until the caller's launches have read them (conv3_backward_linbn)."""
+        Cin, M = cd.Ci, N * hs * ws
+        crow = ops.subsample_colsum_rows(self.dtype, M // V, Cin)
+        csd = self._work("linbn_cs", V * crow * Cin)
+        in_s = x if cd.stride == 1 else torch.empty(M, Cin, dtype=self.tdt, device=x.device)
+        ops.subsample_colsum(self.dtype, x, None if cd.stride == 1 else in_s, csd, N, h, w, Cin, cd.stride, V)
+        slabs, cap = self._slab_buf(Cin * Cin, V)
+        ns = ops.conv_wgrad_slabs(self._lin_conv_desc(self.dtype, N, hs, ws, Cin, Cin), in_s, in_s, slabs, views=V, cap=cap)
+        if keep:
+            Gd = torch.empty(V * Cin * Cin, dtype=torch.float32, device=x.device)
+            sd = torch.empty(V * Cin, dtype=torch.float64, device=x.device)
+        else:
+            Gd = self._work("linbn_Gd", V * Cin * Cin)
+            sd = self._work("linbn_sd", V * Cin, torch.float64)
+        ops.linbn_moments(slabs, ns, Cin * Cin, Gd, views=V, colsum=csd, colsum_rows=crow, s_out=sd, p=Cin)
+        return in_s, Gd, sd
 
     def _lin_unit_products(self, tag, cu, N, Hs, Ws, y_in, dz, V):
         """P = dz^T y_in [V][C][Cin] of an expanding 1x1 conv unit over compact pixels: plain-store split-K slabs of the
@@ -930,27 +733,29 @@ class SM3Engine:
             ops.linbn_post(self.dtype, wbn, cu.w_dgrad, Hn, P, G, Tm, s, coef, self._g(cu.name + ".weight"), C, p, V)
         return wa[: V * p * C], Hn[: V * p * p], cconst[: V * p]
 
-    def conv3_backward_linbn(self, r3, r2, dz, bpart, prow, rd=None, lin_d=False):
-        """Backward of conv3 -> bn3 BY LINEARITY (csrc/linbn.hip; reference: the autograd backward of
+    def conv3_backward_linbn(self, br, dz, bpart, prow):
+        """Backward of conv3 -> bn3 of the block br BY LINEARITY (csrc/linbn.hip; reference: the autograd backward of
         src/models/resnet.py:162-163).  dz: the masked gradient of the block output [M, C]; bpart: its partial rows
         [V][prow][2][C] (only sum(dz) is used) as left by the producing data-gradient launch.
         No pass over bn3's input or output: the weight gradient runs on dz itself, the data gradient is one GEMM over the
         two K segments [dz | y2]; the moments of y2 (r2.colsum, r2.gram) and W G (r3.Tm) came with the forward pass.
         Accumulates d(conv3.weight), d(bn3.weight/bias).
-        rd: the downsample unit of the block, whose BatchNorm received the same dz (resnet.py:164-172), with its statistics
-        in the SAME SyncBN exchange as bn3's.  lin_d: it goes by linearity too -- the moments of the (strided) block input
-        are taken here, its weight gradient and BatchNorm parameter gradients are accumulated, and the ingredients of its
+        br.rd: the downsample unit of the block, whose BatchNorm received the same dz (resnet.py:164-172), with its statistics
+        in the SAME SyncBN exchange as bn3's.  br.form.lin_d: it goes by linearity too -- the moments of the (strided) block
+        input are taken here (unless the fused join kept them), its weight gradient and BatchNorm parameter gradients are
+        accumulated, and the ingredients of its
         data gradient are returned for the caller to launch (sm3_conv_gather_gemm_seg: it joins conv1's data gradient);
         otherwise its two-pass backward runs alongside, the apply pass in place over dz once the GEMMs have read it.
         Returns (dz2 = masked gradient of bn2's output, bn2's phase-1 partial rows per view,
                  d(downsample conv output) | dict(x1, wa, hn, const) | None)."""
+        r2, r3, rd, lin_d = br.r2, br.r3, br.rd, br.form.lin_d
         cu, bu = r3.cu, r3.bu
         C, p, V = cu.Co, cu.Ci, r3.V
         M = r3.N * r3.Ho * r3.Wo
         rows = M // V
         y2 = r3.x_in
-        aff = bu.affine
-        gamma = self._p(bu.name + ".weight") if aff else None
+        gamma = self._bn_affine(bu)[0]
+        dgamma, dbeta = self._bn_affine(bu, grad=True)
         local = rows if self.stat_sync is None else 0  # single rank: the local sums are the global ones
         # 1. P = dz^T y2 [V][C][p]: the weight-gradient kernel on dz itself
         P = self._lin_unit_products("", cu, r3.N, r3.Ho, r3.Wo, y2, dz, V)
@@ -961,38 +766,23 @@ class SM3Engine:
         lsums = self._work("lsums2", 2 * 2 * 2 * 2048, torch.float64)
         coef = self._work("linbn_coef", V * 4 * C)
         ws, groups = ops.bn_stats_reduce(bpart, prow, C, None, views=V)  # stage A; stage B runs inside linbn_stats
-        ops.linbn_stats(self.dtype, P, cu.w_fwd, r3.mean, r3.invstd, gamma, ws, groups, lsums,
-                        self._g(bu.name + ".weight") if aff else None, self._g(bu.name + ".bias") if aff else None,
-                        local, coef, C, p, V)
+        ops.linbn_stats(self.dtype, P, cu.w_fwd, r3.mean, r3.invstd, gamma, ws, groups, lsums, dgamma, dbeta, local, coef,
+                        C, p, V)
         if lin_d:
             # the downsample unit: moments of its (strided) input, taken now; same dz, same sum(dz)
             cd, bd = rd.cu, rd.bu
             Cin = cd.Ci
-            affd = bd.affine
-            gamma_d = self._p(bd.name + ".weight") if affd else None
-            Tmd = None
-            if rd.linbn:  # the forward pass ran the join by linearity (join_fused) and kept the moments
+            gamma_d = self._bn_affine(bd)[0]
+            dgamma_d, dbeta_d = self._bn_affine(bd, grad=True)
+            if br.form.join_fused:  # the forward pass ran the join by linearity and kept the moments
                 in_s, Gd, sd, Tmd = rd.in_s, rd.gram, rd.colsum, rd.Tm
             else:
-                crow = ops.subsample_colsum_rows(self.dtype, rows, Cin)
-                csd = self._work("linbn_cs", V * crow * Cin)
-                if cd.stride == 1:
-                    in_s = rd.x_in
-                    ops.subsample_colsum(self.dtype, rd.x_in, None, csd, rd.N, rd.H, rd.W, Cin, 1, V)
-                else:
-                    in_s = torch.empty(M, Cin, dtype=self.tdt, device=dz.device)
-                    ops.subsample_colsum(self.dtype, rd.x_in, in_s, csd, rd.N, rd.H, rd.W, Cin, cd.stride, V)
-                slabs, cap = self._slab_buf(Cin * Cin, V)
-                ns = ops.conv_wgrad_slabs(self._lin_conv_desc(self.dtype, rd.N, rd.Ho, rd.Wo, Cin, Cin), in_s, in_s, slabs,
-                                          views=V, cap=cap)
-                Gd = self._work("linbn_Gd", V * Cin * Cin)
-                sd = self._work("linbn_sd", V * Cin, torch.float64)
-                ops.linbn_moments(slabs, ns, Cin * Cin, Gd, views=V, colsum=csd, colsum_rows=crow, s_out=sd, p=Cin)
+                in_s, Gd, sd = self._strided_input_moments(cd, rd.x_in, rd.N, rd.H, rd.W, rd.Ho, rd.Wo, V, keep=False)
+                Tmd = None
             Pd = self._lin_unit_products("d", cd, rd.N, rd.Ho, rd.Wo, in_s, dz, V)
             coef_d = self._work("linbn_coef_d", V * 4 * C)
-            ops.linbn_stats(self.dtype, Pd, cd.w_fwd, rd.mean, rd.invstd, gamma_d, ws, groups, lsums[n: 2 * n],
-                            self._g(bd.name + ".weight") if affd else None, self._g(bd.name + ".bias") if affd else None,
-                            local, coef_d, C, Cin, V)
+            ops.linbn_stats(self.dtype, Pd, cd.w_fwd, rd.mean, rd.invstd, gamma_d, ws, groups, lsums[n: 2 * n], dgamma_d,
+                            dbeta_d, local, coef_d, C, Cin, V)
         elif rd is not None:
             prow_d = ops.bn_bwd_partial_rows(rows, C)
             dpart = self._work("partials_d", V * prow_d * 2 * C)
@@ -1025,17 +815,16 @@ class SM3Engine:
                                           part, 0, views=V, row_offset_view1=total // V, w_view_stride=p * C,
                                           w1_view_stride=p * p)
         if rd is not None and not lin_d:  # the downsample BatchNorm's apply pass, in place over dz (its last reader: 4.)
-            affd = rd.bu.affine
-            ops.bn_bwd_apply(self.dtype, dz, rd.xo, rd.mean, rd.invstd, self._p(rd.bu.name + ".weight") if affd else None,
-                             gsums[n: 2 * n], count, lsums[n: 2 * n], self._g(rd.bu.name + ".weight") if affd else None,
-                             self._g(rd.bu.name + ".bias") if affd else None, dz, rows, C, views=V)
+            dgamma_d, dbeta_d = self._bn_affine(rd.bu, grad=True)
+            ops.bn_bwd_apply(self.dtype, dz, rd.xo, rd.mean, rd.invstd, self._bn_affine(rd.bu)[0], gsums[n: 2 * n], count,
+                             lsums[n: 2 * n], dgamma_d, dbeta_d, dz, rows, C, views=V)
             ds = dz
         return dz2, nrows // V, ds
 
     def _wgrad(self, cu, r, dxo):
         """Weight gradient of a unit, accumulated into the flat gradient buffer on the lane's stream (nothing in a
         data-only backward)."""
-        if self.__dict__.get("_data_only"):
+        if self._data_only:
             return
         gw = self._g(cu.name + ".weight")
         if cu.groups > 1:
@@ -1077,9 +866,8 @@ class SM3Engine:
             return into, None
         if full:
             dx = torch.empty(r.N * r.H * r.W, cu.Ci, dtype=self.tdt, device=dxo.device)
-            V = fuse.V if fuse is not None else 1
-            if fuse is not None and self.fuse_bn_bwd and (
-                    V == 1 or all((dd.N * dd.Ho * dd.Wo) % 256 == 0 for dd in descs)):
+            if fuse is not None and cu.dgrad_fusable(self.dtype, r.N, r.H, r.W, fuse.V):
+                V = fuse.V
                 total = sum(ops.conv_partial_rows(dd) for dd in descs)
                 part = self._work("fz_partials", total * 2 * cu.Ci)  # [V][total / V][2][Ci]
                 per_view = total // V
@@ -1135,16 +923,10 @@ class SM3Engine:
             x = torch.cat(xs, 0)
         elif len(xs) == 1:
             x = xs[0]
-        self._V = views if train else 1
-        try:
+        with self._views(views if train else 1):
             self._encoder_forward(plan, x, train, feat_f32, feat_t, save, taps, keep)
-        finally:
-            self._V = 1
 
-    @staticmethod
-    def stage_of(blk):
-        """"layer1" ... "layer4": the stage a block of an EncoderPlan belongs to."""
-        return blk["c1"].name.rsplit(".", 3)[-3]
+    stage_of = staticmethod(stage_of)
 
     def _encoder_forward(self, plan, x, train, feat_f32, feat_t, save, taps=None, keep_out=None):
         if self.stem16:
@@ -1159,21 +941,20 @@ class SM3Engine:
             dev0 = x.device
         N, _, H, W = x.shape
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        recs = [] if save is not None else None
+        saving = save is not None
         Hp, Wp = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
         p = torch.empty(N * Hp * Wp, 64, dtype=self.tdt, device=dev0)
-        amax = torch.empty(N * Hp * Wp * 64, dtype=torch.uint8, device=dev0) if save is not None else None
-        lazy = train or save is not None  # not the single-launch conv+evalBN inference path
+        amax = torch.empty(N * Hp * Wp * 64, dtype=torch.uint8, device=dev0) if saving else None
         # the 7x7 convolution reads the NCHW images directly; stem BatchNorm + ReLU + max-pool in ONE pass over the pre-BN
         # stem output: the post-ReLU map (the largest activation of the network) and its ReLU mask are never stored;
         # backward recomputes the mask
-        V = self._V if train else 1
+        V = self._V
         sc = torch.empty(V * 64, dtype=torch.float32, device=dev0)
         sh = torch.empty(V * 64, dtype=torch.float32, device=dev0)
-        xo, _, _ = self.conv_bn(plan.stem, plan.stem_bn, x, N, H, W, True, None, train, recs, apply=False,
-                                scale_shift=(sc, sh))
-        if recs is not None:
-            recs[0].scale, recs[0].shift = sc, sh
+        xo, _, _, rs = self.conv_bn(plan.stem, plan.stem_bn, x, N, H, W, True, None, train, saving, apply=False,
+                                    scale_shift=(sc, sh))
+        if saving:
+            rs.scale, rs.shift = sc, sh
         ops.bn_relu_maxpool_fwd(self.dtype, xo, sc, sh, p, N, Ho, Wo, 64, amax, views=V)
         del xo
         cur, h, w = p, Hp, Wp
@@ -1183,106 +964,85 @@ class SM3Engine:
         kept = keep = None
         if keep_out is not None:
             keep = keep_out["stage"]
-            if keep not in {self.stage_of(b) for b in plan.blocks}:
+            if keep not in {stage_of(b) for b in plan.blocks}:
                 raise ValueError(f"keep: no stage {keep!r} in this encoder")
-        # BatchNorm by linearity for conv3 -> bn3 (csrc/linbn.hip) needs two moments of conv3's input y2 per view: sum(y2),
-        # which bn2's apply pass adds up on the side (per-block partial rows), and the Gram matrix y2^T y2, one launch of the
-        # weight-gradient kernel on y2 alone (plain-store split-K slabs); sm3_linbn_moments adds both up in a fixed order,
-        # so the forward pass stays bit-reproducible.
-        Vt = self._V if train else 1
-        lin_ok = [self.linbn and train and save is not None and "c3" in b and b["c3"].Co % 128 == 0 and b["c3"].Ci % 64 == 0
-                  for b in plan.blocks]
-        for bi, (blk, lin) in enumerate(zip(plan.blocks, lin_ok)):
-            br = [] if save is not None else None
-            if plan.basic:
-                # BasicBlock (reference resnet.py:91-106): conv1 -> bn1 -> relu -> conv2 -> bn2 (+identity) -> relu.  Both
-                # convolutions are 3x3, so none of the by-linearity forms (1x1 only) applies; a downsample branch stops after
-                # its statistics and is normalised inside the join, as in the two-pass Bottleneck join.  Saved units:
-                # [conv1, (downsample,) conv2] -- the join is last, as in a Bottleneck.
-                y1, h1, w1 = self.conv_bn(blk["c1"], blk["b1"], cur, N, h, w, True, None, train, br)
-                ra = pend = None
-                if "cd" in blk and lazy:
-                    ra = (self._work("scale_d", 2 * 2048), self._work("shift_d", 2 * 2048))
-                    pend = [] if (train and self.stat_sync is not None) else None
-                    idn, _, _ = self.conv_bn(blk["cd"], blk["bd"], cur, N, h, w, False, None, train, br, apply=False,
-                                             scale_shift=ra, pending=pend)
-                elif "cd" in blk:
-                    idn, _, _ = self.conv_bn(blk["cd"], blk["bd"], cur, N, h, w, False, None, train, br)
-                else:
-                    idn = cur  # layer1: the max-pool output, or the previous block's output
-                y2, h2, w2 = self.conv_bn(blk["c2"], blk["b2"], y1, N, h1, w1, True, idn, train, br, res_affine=ra,
-                                          pending=pend)
-                del y1, idn
-                block_recs.append(br)
-                cur, h, w = y2, h2, w2
-                if keep is not None and self.stage_of(blk) == keep:
-                    kept = (cur, h, w)
-                if taps is not None:
-                    taps["x"].append(cur.clone())
-                continue
-            # conv1 -> bn1 -> relu -> conv2 (resnet.py:144-150)
-            y1, h1, w1 = self.conv_bn(blk["c1"], blk["b1"], cur, N, h, w, True, None, train, br)
-            pp = blk["c3"].Ci
-            cs = crow = None
-            if lin:
-                d2 = blk["c2"].fwd_desc(self.dtype, N, h1, w1)
-                crow = ops.bn_act_colsum_rows(self.dtype, N * d2.Ho * d2.Wo // Vt, pp)
-                cs = self._work("linbn_cs", Vt * crow * pp)
-            y2, h2, w2 = self.conv_bn(blk["c2"], blk["b2"], y1, N, h1, w1, True, None, train, br, colsum=cs)
-            if lin:
-                slabs, cap = self._slab_buf(pp * pp, Vt)
-                ns = ops.conv_wgrad_slabs(self._lin_conv_desc(self.dtype, N, h2, w2, pp, pp), y2, y2, slabs, views=Vt, cap=cap)
-                br[1].gram = torch.empty(Vt * pp * pp, dtype=torch.float32, device=dev0)
-                br[1].colsum = torch.empty(Vt * pp, dtype=torch.float64, device=dev0)
-                ops.linbn_moments(slabs, ns, pp * pp, br[1].gram, views=Vt, colsum=cs, colsum_rows=crow,
-                                  s_out=br[1].colsum, p=pp)
-            ra = None
-            pend = None
-            # the join by linearity needs what its backward needs (conv3_backward_linbn, lin_d)
-            join_lin = (lin and "cd" in blk and self.linbn_fwd and self.linbn_ds and self.linbn_join and self.fuse_bn_bwd
-                        and blk["cd"].Ci % 64 == 0 and
-                        (blk["cd"].stride == 1 or (bi > 0 and blk["cd"].stride == 2 and
-                                                   (Vt == 1 or (N * h * w) % 256 == 0))))
-            if join_lin:
-                y3, h3, w3 = self.join_fused(blk, br[1], y2, cur, N, h, w, h2, w2, br)
-                block_recs.append(br)
-                cur, h, w = y3, h3, w3
-                if keep is not None and self.stage_of(blk) == keep:
-                    kept = (cur, h, w)
-                if taps is not None:
-                    taps["x"].append(cur.clone())
-                continue
-            if "cd" in blk and lazy:
-                # downsample branch: convolution + statistics only; its BatchNorm is applied inside the join below
-                # (data parallel: its statistics travel in conv3's all-reduce)
-                ra = (self._work("scale_d", 2 * 2048), self._work("shift_d", 2 * 2048))
-                pend = [] if (train and self.stat_sync is not None) else None
-                idn, _, _ = self.conv_bn(blk["cd"], blk["bd"], cur, N, h, w, False, None, train, br, apply=False,
-                                         scale_shift=ra, pending=pend)
-            elif "cd" in blk:
-                idn, _, _ = self.conv_bn(blk["cd"], blk["bd"], cur, N, h, w, False, None, train, br)
-            else:
-                idn = cur
-            if lin and "cd" not in blk and self.linbn_fwd:
-                # conv3 -> bn3 -> (+identity) -> ReLU in ONE launch: bn3's batch statistics come from the moments of y2
-                y3, h3, w3 = self.conv3_bn3_fused(blk["c3"], blk["b3"], br[1], y2, idn, N, h2, w2, br)
-            else:
-                y3, h3, w3 = self.conv_bn(blk["c3"], blk["b3"], y2, N, h2, w2, True, idn, train, br, res_affine=ra,
-                                          pending=pend)
-                if lin:
-                    br[-1].linbn = True  # backward of conv3 -> bn3 by linearity; needs br[1].colsum / .gram (moments of y2)
+        block_forward = self._basic_forward if plan.basic else self._bottleneck_forward
+        for bi, blk in enumerate(plan.blocks):
+            form = block_form(blk, bi, self, train, self.dtype, V, N, h, w) if saving else TWO_PASS
+            cur, h, w, br = block_forward(blk, form, cur, N, h, w, train, saving)
             block_recs.append(br)
-            cur, h, w = y3, h3, w3
-            if keep is not None and self.stage_of(blk) == keep:
+            if keep is not None and stage_of(blk) == keep:
                 kept = (cur, h, w)
             if taps is not None:
                 taps["x"].append(cur.clone())
         ops.avgpool_fwd(self.dtype, cur, feat_f32, feat_t, N, h * w, plan.out_dim)
         if keep_out is not None:
             keep_out["out"] = kept
-        if save is not None:
-            save.append({"plan": plan, "stem": recs[0], "stem_hw": (Ho, Wo), "pool_hw": (Hp, Wp), "argmax": amax,
-                         "blocks": block_recs, "N": N, "last_hw": (h, w), "V": self._V, "img_hw": (H, W)})
+        if saving:
+            save.append(EncoderCtx(plan=plan, N=N, img_hw=(H, W), stem=rs, stem_hw=(Ho, Wo), argmax=amax,
+                                   blocks=block_recs, last_hw=(h, w)))
+
+    def _identity_branch(self, blk, cur, N, h, w, train, save):
+        """What a block's join adds to its last BatchNorm -> (idn, res_affine, pending, the downsample unit's Rec or None).
+        No downsample unit: the block input.  Train mode, or records kept: the downsample convolution and its statistics
+        only -- idn is its pre-BatchNorm output, normalised inside the join (conv_bn's res_affine; data parallel: its
+        statistics travel in the join's all-reduce, conv_bn's pending).  Inference: the whole unit in one launch."""
+        if "cd" not in blk:
+            return cur, None, None, None
+        if not (train or save):
+            return self.conv_bn(blk["cd"], blk["bd"], cur, N, h, w, False, None, train)[0], None, None, None
+        ra = (self._work("scale_d", 2 * 2048), self._work("shift_d", 2 * 2048))
+        pend = [] if (train and self.stat_sync is not None) else None
+        idn, _, _, rd = self.conv_bn(blk["cd"], blk["bd"], cur, N, h, w, False, None, train, save, apply=False,
+                                     scale_shift=ra, pending=pend)
+        return idn, ra, pend, rd
+
+    def _basic_forward(self, blk, form, cur, N, h, w, train, save):
+        """BasicBlock (reference resnet.py:91-106): conv1 -> bn1 -> relu -> conv2 -> bn2 (+identity) -> relu.  Both
+        convolutions are 3x3, so none of the by-linearity forms (1x1 only) applies; a downsample branch stops after its
+        statistics and is normalised inside the join, as in the two-pass Bottleneck join.
+        Returns (block output, h, w, BlockRec if save)."""
+        y1, h1, w1, r1 = self.conv_bn(blk["c1"], blk["b1"], cur, N, h, w, True, None, train, save)
+        idn, ra, pend, rd = self._identity_branch(blk, cur, N, h, w, train, save)
+        y2, h2, w2, r2 = self.conv_bn(blk["c2"], blk["b2"], y1, N, h1, w1, True, idn, train, save, res_affine=ra,
+                                      pending=pend)
+        return y2, h2, w2, (BlockRec(form, r1, r2, rd=rd) if save else None)
+
+    def _bottleneck_forward(self, blk, form, cur, N, h, w, train, save):
+        """Bottleneck (resnet.py:144-172) in the form `form` -> (block output, h, w, BlockRec if save).
+        BatchNorm by linearity for conv3 -> bn3 (csrc/linbn.hip) needs two moments of conv3's input y2 per view: sum(y2),
+        which bn2's apply pass adds up on the side (per-block partial rows), and the Gram matrix y2^T y2, one launch of the
+        weight-gradient kernel on y2 alone (plain-store split-K slabs); sm3_linbn_moments adds both up in a fixed order,
+        so the forward pass stays bit-reproducible."""
+        V = self._V
+        # conv1 -> bn1 -> relu -> conv2 (resnet.py:144-150)
+        y1, h1, w1, r1 = self.conv_bn(blk["c1"], blk["b1"], cur, N, h, w, True, None, train, save)
+        pp = blk["c3"].Ci
+        cs = crow = None
+        if form.lin:
+            d2 = blk["c2"].fwd_desc(self.dtype, N, h1, w1)
+            crow = ops.bn_act_colsum_rows(self.dtype, N * d2.Ho * d2.Wo // V, pp)
+            cs = self._work("linbn_cs", V * crow * pp)
+        y2, h2, w2, r2 = self.conv_bn(blk["c2"], blk["b2"], y1, N, h1, w1, True, None, train, save, colsum=cs)
+        if form.lin:
+            slabs, cap = self._slab_buf(pp * pp, V)
+            ns = ops.conv_wgrad_slabs(self._lin_conv_desc(self.dtype, N, h2, w2, pp, pp), y2, y2, slabs, views=V, cap=cap)
+            r2.gram = torch.empty(V * pp * pp, dtype=torch.float32, device=y2.device)
+            r2.colsum = torch.empty(V * pp, dtype=torch.float64, device=y2.device)
+            ops.linbn_moments(slabs, ns, pp * pp, r2.gram, views=V, colsum=cs, colsum_rows=crow, s_out=r2.colsum, p=pp)
+        if form.join_fused:
+            y3, h3, w3, rd, r3 = self.join_fused(blk, r2, y2, cur, N, h, w, h2, w2)
+        else:
+            idn, ra, pend, rd = self._identity_branch(blk, cur, N, h, w, train, save)
+            if form.conv3_fused:
+                # conv3 -> bn3 -> (+identity) -> ReLU in ONE launch: bn3's batch statistics come from the moments of y2
+                y3, h3, w3, r3 = self.conv3_bn3_fused(blk["c3"], blk["b3"], r2, y2, idn, N, h2, w2)
+            else:
+                y3, h3, w3, r3 = self.conv_bn(blk["c3"], blk["b3"], y2, N, h2, w2, True, idn, train, save, res_affine=ra,
+                                              pending=pend)
+                if form.lin:
+                    r3.linbn = True  # backward of conv3 -> bn3 by linearity: no pass over its pre-BatchNorm output
+        return y3, h3, w3, (BlockRec(form, r1, r2, r3, rd) if save else None)
 
     def encoder_backward(self, ctx, dfeat, last_view=True, taps=None, dx_out=None, params=True, stop_at=None):
         """dfeat: [N,2048] `dtype` gradient of the pooled features.  On the last view of a step each stage's
@@ -1305,132 +1065,38 @@ class SM3Engine:
         skipped.  The gradient is taken with respect to the post-ReLU output itself (not masked by its ReLU): the first block
         of the next stage computes its data gradient without the previous block's BatchNorm-backward phase 1 in the epilogue
         (the unfused form of that boundary).  Use with params=False."""
-        prev = self.__dict__.get("_data_only", False)
-        self._data_only = prev or not params
-        try:
+        with self._params_backward(params):
             return self._encoder_backward(ctx, dfeat, last_view, taps, dx_out, stop_at)
-        finally:
-            self._data_only = prev
 
     def _stop_block(self, ctx, stop_at):
         """Index of the first block after stage `stop_at` (whose input gradient is that stage's output gradient)."""
-        blocks = ctx["plan"].blocks
-        names = [self.stage_of(b) for b in blocks]
+        names = [stage_of(b) for b in ctx.plan.blocks]
         if stop_at not in names or names[-1] == stop_at:
             raise ValueError(f"stop_at: {stop_at!r} is not a stage below the last one of this encoder")
-        if not ctx["stem"].frozen_stats:
+        if not ctx.stem.frozen_stats:
             raise NotImplementedError("stop_at: eval-mode (frozen-statistics) contexts only")
         return max(i for i, n in enumerate(names) if n == stop_at) + 1
 
     def _encoder_backward(self, ctx, dfeat, last_view, taps, dx_out, stop_at=None):
-        plan, N = ctx["plan"], ctx["N"]
+        plan, N = ctx.plan, ctx.N
         stop_bi = self._stop_block(ctx, stop_at) if stop_at is not None else -1
-        h, w = ctx["last_hw"]
+        h, w = ctx.last_hw
         dcur = torch.empty(N * h * w, plan.out_dim, dtype=self.tdt, device=dfeat.device)
         ops.avgpool_bwd(self.dtype, dfeat, dcur, N, h * w, plan.out_dim)
         fr = None  # rows of fused BN-backward partials that came with dcur
         if taps is not None:
             taps["g"] = [None] * (len(plan.blocks) + 1)
             taps["g_pre_relu"] = [False] * (len(plan.blocks) + 1)
+        block_backward = self._basic_backward if plan.basic else self._bottleneck_backward
         for bi in range(len(plan.blocks) - 1, -1, -1):
-            blk, br = plan.blocks[bi], ctx["blocks"][bi]
+            blk = plan.blocks[bi]
             unfused_in = bi == stop_bi  # the gradient of this block's input is returned: no previous-block epilogue
             if taps is not None:  # before this block's first kernel, which masks dcur in place when fr is None
                 taps["g"][bi + 1], taps["g_pre_relu"][bi + 1] = dcur.clone(), fr is not None
-            if plan.basic:
-                # BasicBlock: the join's BatchNorm(s), conv2 with bn1's phase 1 in its epilogue, bn1; conv1's data gradient
-                # below takes the identity gradient (or the downsample's compact one) as its addend
-                if "cd" in blk:
-                    r1, rd, r2 = br
-                    dx2, dxd = self.bn_backward_join(r2, rd, dcur, fused_rows=fr)
-                    dz = None
-                else:
-                    (r1, r2), rd = br, None
-                    dx2, dz = self.bn_backward(r2, dcur, keep_dz=True, fused_rows=fr)
-                dy1, fr1 = self.conv_backward(r2, dx2, fuse=r1)
-                del dx2
-            else:
-                if "cd" in blk:
-                    r1, r2, rd, r3 = br
-                else:
-                    (r1, r2, r3), rd = br, None
-                if r3.linbn:
-                    # conv3 -> bn3 by linearity: dz (dcur, masked) feeds the weight- and data-gradient GEMMs as it is
-                    if fr is None:  # last block: dcur is the un-masked gradient from the pooling layer
-                        C3, V3 = r3.cu.Co, r3.V
-                        rows3 = r3.N * r3.Ho * r3.Wo // V3
-                        prow = ops.bn_bwd_partial_rows(rows3, C3)
-                        bpart = self._work("partials", V3 * prow * 2 * C3)
-                        ops.bn_bwd_reduce(self.dtype, dcur, None, r3.xo, r3.mean, r3.invstd, dcur, rows3, C3, bpart,
-                                          mask=r3.mask, views=V3)
-                    else:
-                        prow, bpart = fr, self._ws[(self._lane, "fz_partials")]
-                    prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 and not unfused_in else None
-                    lin_d = rd is not None and (rd.linbn or (
-                        self.linbn_ds and rd.cu.Ci % 64 == 0 and not rd.frozen_stats and
-                        (rd.cu.stride == 1 or (prev_r3 is not None and self.fuse_bn_bwd and rd.cu.stride == 2 and
-                                               (prev_r3.V == 1 or (r1.N * r1.H * r1.W) % 256 == 0)))))
-                    dy2, fr2, dxd = self.conv3_backward_linbn(r3, r2, dcur, bpart, prow, rd=rd, lin_d=lin_d)
-                    dz = None if rd is not None else dcur
-                else:
-                    if rd is not None:
-                        dx3, dxd = self.bn_backward_join(r3, rd, dcur, fused_rows=fr)
-                        dz = None
-                    else:
-                        dx3, dz = self.bn_backward(r3, dcur, keep_dz=True, fused_rows=fr)
-                    dy2, fr2 = self.conv_backward(r3, dx3, fuse=r2)
-                    del dx3
-                dx2, _ = self.bn_backward(r2, dy2, keep_dz=False, fused_rows=fr2)
-                dy1, fr1 = self.conv_backward(r2, dx2, fuse=r1)
-                del dx2, dy2
-            dx1, _ = self.bn_backward(r1, dy1, keep_dz=False, fused_rows=fr1)
-            if rd is not None and isinstance(dxd, dict):
-                # the downsample unit went by linearity: its data gradient is the two-segment product of dz (= dcur) and the
-                # compact block input, joined with conv1's data gradient as the two-pass form's is
-                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 and not unfused_in else None
-                cd = rd.cu
-                Vd = r3.V
-                Cd, Cin = cd.Co, cd.Ci
-                dd = cd.compact_dgrad_desc(self.dtype, rd.N, rd.Ho, rd.Wo)
-                if cd.stride == 2:
-                    dsp = torch.empty(rd.N * rd.Ho * rd.Wo, Cin, dtype=self.tdt, device=dcur.device)
-                    ops.conv_gemm_seg(dd, dcur, dxd["wa"], dxd["x1"], dxd["hn"], dxd["const"], dsp, None, views=Vd,
-                                      w_view_stride=Cin * Cd, w1_view_stride=Cin * Cin)
-                    din, fr = self.conv_backward(r1, dx1, addend=dsp, fuse=prev_r3, addend_sparse=(rd.Ho, rd.Wo))
-                else:
-                    din, _ = self.conv_backward(r1, dx1)
-                    ops.conv_gemm_seg(dd, dcur, dxd["wa"], dxd["x1"], dxd["hn"], dxd["const"], din, din, views=Vd,
-                                      w_view_stride=Cin * Cd, w1_view_stride=Cin * Cin)
-                    fr = None
-            elif rd is not None:
-                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 and not unfused_in else None
-                cd = rd.cu
-                V = prev_r3.V if prev_r3 is not None else 1
-                if (prev_r3 is not None and self.fuse_bn_bwd and cd.stride == 2
-                        and (V == 1 or all((dd.N * dd.Ho * dd.Wo) % 256 == 0
-                                           for dd in r1.cu.dgrad_descs(self.dtype, r1.N, r1.H, r1.W)[0]))):
-                    # Join of the two data gradients of a stride-2 downsample block WITHOUT a second pass over the
-                    # block-input gradient: the downsample convolution's data gradient is computed first, compact (it
-                    # only exists at the even pixels), and conv1's data gradient takes it as a sparse addend -- so that
-                    # launch sees the complete gradient of the previous block's output and runs that block's
-                    # BatchNorm-backward phase 1 in its epilogue, like every other block boundary.  A BasicBlock's conv1
-                    # is the 3x3 / stride-2 one: its data gradient is four parity-class launches, and the compact addend
-                    # goes to the (0, 0) class, whose rows are exactly the downsample's pixels.
-                    self._wgrad(cd, rd, dxd)
-                    hs, ws = rd.Ho, rd.Wo
-                    dd = cd.compact_dgrad_desc(self.dtype, rd.N, hs, ws)
-                    dsp = torch.empty(rd.N * hs * ws, cd.Ci, dtype=self.tdt, device=dxd.device)
-                    ops.conv_gemm(dd, dxd, cd.w_dgrad, dsp, None, None)
-                    din, fr = self.conv_backward(r1, dx1, addend=dsp, fuse=prev_r3, addend_sparse=(hs, ws))
-                else:
-                    din, _ = self.conv_backward(r1, dx1)
-                    self.conv_backward(rd, dxd, into=din)
-                    fr = None
-            else:
-                # din is the gradient of the previous block's output = of its bn3 (+residual, ReLU) unit
-                prev_r3 = ctx["blocks"][bi - 1][-1] if bi > 0 and not unfused_in else None
-                din, fr = self.conv_backward(r1, dx1, addend=dz, fuse=prev_r3)
-            dcur = din
+            # the unit whose output this block's input gradient is the gradient of: the previous block's join, whose
+            # BatchNorm-backward phase 1 then runs in the epilogue of this block's last data-gradient launch
+            prev = ctx.blocks[bi - 1].join if bi > 0 and not unfused_in else None
+            dcur, fr = block_backward(ctx.blocks[bi], dcur, fr, prev)
             if unfused_in:
                 return dcur
             if last_view and "cd" in blk and bi > 0:  # first block of a stage: the stage is complete
@@ -1439,39 +1105,119 @@ class SM3Engine:
         if taps is not None:
             taps["g"][0] = dcur.clone()  # the gradient of the max-pool output (not masked: maxpool_bn_bwd applies the mask)
         # maxpool -> stem BN/ReLU -> stem weight gradient (and, when asked for, the image gradient)
-        Ho, Wo = ctx["stem_hw"]
-        rs = ctx["stem"]
+        Ho, Wo = ctx.stem_hw
+        rs = ctx.stem
         # maxpool gradient gather + recomputed ReLU mask + BatchNorm-backward phase 1 in one pass
         dz = torch.empty(N * Ho * Wo, 64, dtype=self.tdt, device=dfeat.device)
         prow = ops.maxpool_bn_bwd_partial_rows(N, Ho, Wo, rs.V)
         part = self._work("fz_partials", rs.V * prow * 2 * 64)
-        ops.maxpool_bn_bwd(self.dtype, ctx["argmax"], dcur, rs.xo, rs.scale, rs.shift, rs.mean, rs.invstd, dz, part,
+        ops.maxpool_bn_bwd(self.dtype, ctx.argmax, dcur, rs.xo, rs.scale, rs.shift, rs.mean, rs.invstd, dz, part,
                            N, Ho, Wo, 64, views=rs.V)
         # BatchNorm-backward apply inside the stem weight gradient's operand load: d(conv1 output) never reaches HBM
         lsums, gsums, count = self._bn_backward_sums(rs, part, prow)
-        bn = rs.bu.name
+        gamma = self._bn_affine(rs.bu)[0]
         if not self._data_only:
+            dgamma, dbeta = self._bn_affine(rs.bu, grad=True)
             wg = ops.stem_wgrad_bn16 if isinstance(rs.x_in, ops.StemImage) else ops.stem_wgrad_bn
-            wg(self.dtype, rs.x_in, dz, rs.xo, rs.mean, rs.invstd, self._p(bn + ".weight"), gsums, count,
-               lsums, self._g(bn + ".weight"), self._g(bn + ".bias"), self._g(rs.cu.name + ".weight"), views=rs.V,
+            wg(self.dtype, rs.x_in, dz, rs.xo, rs.mean, rs.invstd, gamma, gsums, count, lsums, dgamma, dbeta,
+               self._g(rs.cu.name + ".weight"), views=rs.V,
                slabs=self._work("stem_slabs", ops.STEM_WGRAD_SLABS * 64 * 147) if self.det_wgrad else None)
         if dx_out is not None:
             # the same BatchNorm-backward apply, on the fly, then the transposed 7x7 / stride-2 convolution in gather form;
             # the gradient passes straight through the 16-bit rounding of the images (StemImage), as a cast does
-            ops.stem_dgrad_bn(self.dtype, dz, rs.xo, rs.mean, rs.invstd, self._p(bn + ".weight"), gsums, count,
+            ops.stem_dgrad_bn(self.dtype, dz, rs.xo, rs.mean, rs.invstd, gamma, gsums, count,
                               self._p(rs.cu.name + ".weight"), dx_out, views=rs.V)
         if last_view:
             self._notify(plan.prefix + "conv1", plan.prefix + "layer1.")
 
+    def _basic_backward(self, br, dcur, fr, prev):
+        """BasicBlock: the join's BatchNorm(s), conv2 with bn1's phase 1 in its epilogue; then _block_input_backward."""
+        dxd = dz = None
+        if br.rd is not None:
+            dx2, dxd = self.bn_backward_join(br.r2, br.rd, dcur, fused_rows=fr)
+        else:
+            dx2, dz = self.bn_backward(br.r2, dcur, keep_dz=True, fused_rows=fr)
+        dy1, fr1 = self.conv_backward(br.r2, dx2, fuse=br.r1)
+        del dx2
+        return self._block_input_backward(br, dy1, fr1, dcur, dz, dxd, prev)
+
+    def _bottleneck_backward(self, br, dcur, fr, prev):
+        """Bottleneck: the join and conv3 -> bn3 (by linearity or in two passes), conv2 -> bn2; then _block_input_backward."""
+        r1, r2, r3, rd = br.r1, br.r2, br.r3, br.rd
+        dxd = dz = None
+        if br.form.lin:
+            # conv3 -> bn3 by linearity: dz (dcur, masked) feeds the weight- and data-gradient GEMMs as it is; phase 1 has
+            # run already except in the last block, whose dcur is the un-masked gradient from the pooling layer
+            prow, bpart = self._phase1(r3, dcur, fr)
+            dy2, fr2, dxd = self.conv3_backward_linbn(br, dcur, bpart, prow)
+            if rd is None:
+                dz = dcur
+        else:
+            if rd is not None:
+                dx3, dxd = self.bn_backward_join(r3, rd, dcur, fused_rows=fr)
+            else:
+                dx3, dz = self.bn_backward(r3, dcur, keep_dz=True, fused_rows=fr)
+            dy2, fr2 = self.conv_backward(r3, dx3, fuse=r2)
+            del dx3
+        dx2, _ = self.bn_backward(r2, dy2, keep_dz=False, fused_rows=fr2)
+        dy1, fr1 = self.conv_backward(r2, dx2, fuse=r1)
+        del dx2, dy2
+        return self._block_input_backward(br, dy1, fr1, dcur, dz, dxd, prev)
+
+    def _block_input_backward(self, br, dy1, fr1, dcur, dz, dxd, prev):
+        """The head of a block, backward: bn1, then conv1's data gradient joined with the gradient that reaches the block
+        input through the identity (dz: the masked gradient of the block output) or through the downsample unit br.rd
+        (dxd: what the join's backward left for it; dcur: the masked gradient of the block output).
+        prev: the previous block's join, whose BatchNorm-backward phase 1 goes into the epilogue of the launch that completes
+        the block-input gradient; None (block 0, or the gradient is returned to the caller): no epilogue.
+        Returns (gradient of the block input, its rows of fused partials or None)."""
+        r1, rd = br.r1, br.rd
+        dx1, _ = self.bn_backward(r1, dy1, keep_dz=False, fused_rows=fr1)
+        if rd is None:
+            # din is the gradient of the previous block's output = of its bn3 (+residual, ReLU) unit
+            return self.conv_backward(r1, dx1, addend=dz, fuse=prev)
+        cd = rd.cu
+        if br.form.lin_d:
+            # the downsample unit went by linearity: its data gradient is the two-segment product of dz (= dcur) and the
+            # compact block input, joined with conv1's data gradient as the two-pass form's is
+            Cd, Cin = cd.Co, cd.Ci
+            dd = cd.compact_dgrad_desc(self.dtype, rd.N, rd.Ho, rd.Wo)
+            if cd.stride == 2:
+                dsp = torch.empty(rd.N * rd.Ho * rd.Wo, Cin, dtype=self.tdt, device=dcur.device)
+                ops.conv_gemm_seg(dd, dcur, dxd["wa"], dxd["x1"], dxd["hn"], dxd["const"], dsp, None, views=rd.V,
+                                  w_view_stride=Cin * Cd, w1_view_stride=Cin * Cin)
+                return self.conv_backward(r1, dx1, addend=dsp, fuse=prev, addend_sparse=(rd.Ho, rd.Wo))
+            din, _ = self.conv_backward(r1, dx1)
+            ops.conv_gemm_seg(dd, dcur, dxd["wa"], dxd["x1"], dxd["hn"], dxd["const"], din, din, views=rd.V,
+                              w_view_stride=Cin * Cd, w1_view_stride=Cin * Cin)
+            return din, None
+        if br.form.sparse_join and prev is not None:
+            # Join of the two data gradients of a stride-2 downsample block WITHOUT a second pass over the
+            # block-input gradient: the downsample convolution's data gradient is computed first, compact (it
+            # only exists at the even pixels), and conv1's data gradient takes it as a sparse addend -- so that
+            # launch sees the complete gradient of the previous block's output and runs that block's
+            # BatchNorm-backward phase 1 in its epilogue, like every other block boundary.  A BasicBlock's conv1
+            # is the 3x3 / stride-2 one: its data gradient is four parity-class launches, and the compact addend
+            # goes to the (0, 0) class, whose rows are exactly the downsample's pixels.
+            self._wgrad(cd, rd, dxd)
+            hs, ws = rd.Ho, rd.Wo
+            dd = cd.compact_dgrad_desc(self.dtype, rd.N, hs, ws)
+            dsp = torch.empty(rd.N * hs * ws, cd.Ci, dtype=self.tdt, device=dxd.device)
+            ops.conv_gemm(dd, dxd, cd.w_dgrad, dsp, None, None)
+            return self.conv_backward(r1, dx1, addend=dsp, fuse=prev, addend_sparse=(hs, ws))
+        din, _ = self.conv_backward(r1, dx1)
+        self.conv_backward(rd, dxd, into=din)
+        return din, None
+
     # ---- projector -----------------------------------------------------------------------
     def projector_forward(self, plan, x_t, M, train, z_out, save=None):
         """x_t [M,2048] `dtype` -> z_out [M,proj_dim] fp32 (view into the caller's [2B,proj] buffer)."""
-        recs = [] if save is not None else None
-        h, _, _ = self.conv_bn(plan.l0, plan.b1, x_t, M, 1, 1, True, None, train, recs)
-        h, _, _ = self.conv_bn(plan.l3, plan.b4, h, M, 1, 1, True, None, train, recs)
-        self.conv_bn(plan.l6, plan.b7, h, M, 1, 1, False, None, train, recs, out_f32=True, y_out=z_out)
-        if save is not None:
-            save.append(recs)
+        saving = save is not None
+        h, _, _, r0 = self.conv_bn(plan.l0, plan.b1, x_t, M, 1, 1, True, None, train, saving)
+        h, _, _, r3 = self.conv_bn(plan.l3, plan.b4, h, M, 1, 1, True, None, train, saving)
+        r6 = self.conv_bn(plan.l6, plan.b7, h, M, 1, 1, False, None, train, saving, out_f32=True, y_out=z_out)[3]
+        if saving:
+            save.append((r0, r3, r6))
 
     def projector_backward(self, recs, dz, addend=None, into=None):
         """dz [M,proj_dim] `dtype` -> gradient w.r.t. the projector input [M,2048] (+addend)."""
@@ -1506,8 +1252,7 @@ class SM3Engine:
         # Cross-modal projectors (simclr.py:290-322): cross_proj[0] only ever sees dermoscopy features and cross_proj[1]
         # clinical ones, so each runs at the end of its modality's lane, hidden behind the other lane's encoder, instead of
         # on the main stream after the join (4 projector passes = ~50 small dependent launches in series).
-        lane_cross = (self.cross is not None and streams is not None and set(self.branches) == {"derm", "clinic"}
-                      and self.lane_cross)
+        lane_cross = self._cross_in_lanes(streams)
         pairs = self.cross_pairs(style) if self.cross is not None else []
         zc = [self._share(torch.empty(2 * B, self.module.proj_dim, dtype=torch.float32, device=dev), streams) for _ in pairs] \
             if lane_cross else []
@@ -1557,7 +1302,7 @@ class SM3Engine:
             if want_grad:
                 saved[key] = {"enc": ctxs, "proj": precs[0] if proj is not None else None}
         self._join(streams)
-        for k in list(self.__dict__.get("_lane_prep", {})):
+        for k in list(self._lane_prep):
             self.prep_lane(k)  # (a branch whose lane never ran)
         cross_saved = []
         if lane_cross:
@@ -1597,8 +1342,13 @@ class SM3Engine:
                 saved["meta"] = pm[0]
         return zs, feats, saved
 
+    def _cross_in_lanes(self, streams):
+        """Whether the cross-modal projector passes run inside the two modality lanes (forward and its mirror, backward)."""
+        return (self.cross is not None and streams is not None and set(self.branches) == {"derm", "clinic"}
+                and self.lane_cross)
+
     def _notify(self, plan_prefix_first, plan_prefix_last):
-        if self.grad_ready is not None and not self.__dict__.get("_data_only"):
+        if self.grad_ready is not None and not self._data_only:
             self.grad_ready(plan_prefix_first, plan_prefix_last)
 
     def backward(self, saved, dz, dfeat=None, want_dx=None, params=True):
@@ -1608,12 +1358,8 @@ class SM3Engine:
         want_dx: optional dict branch -> (view 0?, view 1?): the image gradients to compute; returns dict branch ->
         [dx_view0, dx_view1] (fp32 NCHW, None where not asked for).  A pair batch (both views in one encoder pass) gives
         one [2B, 3, H, W] gradient, split into its views.  params=False: data-only (see encoder_backward)."""
-        prev = self.__dict__.get("_data_only", False)
-        self._data_only = prev or not params
-        try:
+        with self._params_backward(params):
             return self._backward(saved, dz, dfeat, want_dx)
-        finally:
-            self._data_only = prev
 
     def _backward(self, saved, dz, dfeat, want_dx):
         B = saved["B"]
@@ -1623,9 +1369,8 @@ class SM3Engine:
         for t in dz.values():
             self._share(t, streams)
         # mirror of forward(): each cross-modal projector's backward inside its modality's lane (no join, no main-stream pass)
-        lane_cross = (self.cross is not None and streams is not None and set(self.branches) == {"derm", "clinic"}
-                      and self.lane_cross and bool(saved.get("cross")) and all(f"cross{ci}" in dz
-                                                                             for ci in range(len(saved["cross"]))))
+        lane_cross = (self._cross_in_lanes(streams) and bool(saved.get("cross"))
+                      and all(f"cross{ci}" in dz for ci in range(len(saved["cross"]))))
         for key, (plan, proj) in self.branches.items():
             extra = dfeat.get(key) if dfeat is not None else None
             self._share(extra, streams)
@@ -1671,8 +1416,8 @@ class SM3Engine:
                     ec = saved[key]["enc"][0]
                     dxo = None
                     if any(want):
-                        H, W = ec["img_hw"]
-                        dxo = self._share(torch.empty(ec["N"], 3, H, W, dtype=torch.float32, device=dev), streams)
+                        H, W = ec.img_hw
+                        dxo = self._share(torch.empty(ec.N, 3, H, W, dtype=torch.float32, device=dev), streams)
                     self.encoder_backward(ec, dfe[key], last_view=True, dx_out=dxo)
                     saved[key]["enc"][0] = None
                 if dxo is not None:  # split the pair batch back into its views
@@ -1683,8 +1428,8 @@ class SM3Engine:
                     ec = saved[key]["enc"][v]
                     dxo = None
                     if want[v]:
-                        H, W = ec["img_hw"]
-                        dxo = self._share(torch.empty(ec["N"], 3, H, W, dtype=torch.float32, device=dev), streams)
+                        H, W = ec.img_hw
+                        dxo = self._share(torch.empty(ec.N, 3, H, W, dtype=torch.float32, device=dev), streams)
                         dxs[key][v] = dxo
                     self.encoder_backward(ec, dfe[key][v * B:(v + 1) * B], last_view=(v == 0), dx_out=dxo)
                     saved[key]["enc"][v] = None  # free the view's activations as soon as it is done

@@ -55,7 +55,7 @@ def _step_bytes(saved_bytes, E, T, perturbed):
 def _saved_bytes(eng, x):
     """What one image's saved records hold: one forward of x that keeps them, dropped at once.  Only when the chunk is planned,
     and once per engine, arithmetic mode and image size (the figure is kept on the engine)."""
-    known = eng.__dict__.setdefault("_faith_saved_bytes", {})
+    known = eng._faith_saved_bytes
     key = (eng.dtype, tuple(x.shape[1:]))
     if key not in known:
         known[key] = forward_measured(eng, x)[1]

@@ -70,7 +70,7 @@ class SM3Trainer:
             # in front of that lane's next (latency-critical) BatchNorm statistics all-reduce.
             lanes = list(eng.branches) + [k + "#1" for k in eng.branches] + ["main", "grads"]
             self._groups = {k: dist.new_group() for k in lanes}
-        if self.dp and self.sync_bn and eng.__dict__.get("_explicit_sync") is None:
+        if self.dp and self.sync_bn and eng._explicit_sync is None:
             eng.world_size = self.world
             if os.environ.get("SM3_SYNCBN_P2P", "0") == "1":
                 # opt-in: the statistics exchange as one kernel on the lane's own stream through hipIpc-mapped mailboxes
@@ -82,7 +82,7 @@ class SM3Trainer:
                 eng.stat_sync = lambda t: self._p2p(eng._lane, t)
             else:
                 eng.stat_sync = lambda t: dist.all_reduce(t, group=self._groups[eng._lane])
-            eng.__dict__["_explicit_sync"] = True
+            eng._explicit_sync = True
         return eng
 
     def _bucket_ready(self, eng, first, last):
@@ -218,7 +218,7 @@ class SM3Trainer:
         if p2p is not None:
             eng = sm3_engine_for(self.model, self.kind)
             eng.stat_sync = None
-            eng.__dict__["_explicit_sync"] = None
+            eng._explicit_sync = None
             p2p.close(barrier=barrier)
 
     def __del__(self):
@@ -244,12 +244,12 @@ class SM3Trainer:
             if self.flat_target is None or self.flat_target.numel() != st.total:
                 self.flat_target = st.flat_p.clone()
             online, st.flat_p = st.flat_p, self.flat_target
-            eng.__dict__["_no_stat_update"] = True
+            eng._no_stat_update = True
             try:
                 zt, _f, _s = eng.forward(views, self.style, True, False)
             finally:
                 st.flat_p = online
-                eng.__dict__["_no_stat_update"] = False
+                eng._no_stat_update = False
         if metadata is not None and (self.style != 0 or self.target_momentum is not None):
             raise NotImplementedError("the metadata branch is defined for style 0 without a momentum target")
         zs, _feats, saved = eng.forward(views, self.style, True, True, metadata=metadata)

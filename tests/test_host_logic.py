@@ -144,6 +144,39 @@ def test_engine_dry_run_sequences_and_bucket_schedule(model, linbn):
     assert all(v == 1 for v in covered.values()), [k for k, v in covered.items() if v != 1][:5]
 
 
+@pytest.mark.parametrize("switch, banks_post, banks_and_post, seg_act, bn_act_fused", [
+    ("SM3_LINBN_FWD", 80, 0, 0, 0),      # no forward half by linearity: neither the fused conv3 nor the fused join
+    ("SM3_LINBN_DS", 64, 0, 0, 48),      # downsample units in two passes: 16 fewer by linearity, and no fused join
+    ("SM3_LINBN_JOIN", 80, 0, 0, 48),    # the fused join alone is off
+    ("SM3_LINBN_MERGE", 0, 80, 16, 48),  # banks and finish as two launches per unit
+    ("SM3_LANE_CROSS", 80, 0, 16, 48),   # no lanes on the CPU: the default step
+])
+def test_engine_dry_run_with_a_form_switch_off(monkeypatch, switch, banks_post, banks_and_post, seg_act, bn_act_fused):
+    """The two dry-run steps of test_engine_dry_run_sequences_and_bucket_schedule with one of the engine's A/B switches off
+    (B = 2, 32 x 32, bf16): the step completes, the first step's schedule check passes (every parameter's gradient announced
+    exactly once), and the second step's launch counts tell the block forms apart.  Counts with every switch on: 80 / 0 / 16 /
+    48.  The engine reads its switches when it is built, so each case builds its own model (and with it its own engine)."""
+    from sm3hip.trainer import SM3Trainer
+    from src.models.simclr import SimCLRSkinV32
+    monkeypatch.setenv(switch, "0")
+    torch.manual_seed(0)
+    fresh = SimCLRSkinV32("resnet50", None, 128, 0.1)
+    with installed() as fake:
+        fresh.sm3_dtype = torch.bfloat16
+        tr = SM3Trainer(fresh, lr=1e-3, data_parallel=False)
+        x = [torch.randn(2, 3, 32, 32) for _ in range(4)]
+        tr.step(x[:2], x[2:])
+        assert tr._sched_ok is not None
+        del fake.calls[:]
+        tr.step(x[:2], x[2:])
+        calls = Counter(fake.calls)
+    assert tr.step_count == 2
+    assert calls["sm3_bn_finalize"] == 230
+    assert calls["sm3_linbn_banks_post"] == banks_post
+    assert calls["sm3_linbn_banks"] == banks_and_post and calls["sm3_linbn_post"] == banks_and_post
+    assert calls["sm3_conv_seg_act"] == seg_act and calls["sm3_conv_bn_act_fused"] == bn_act_fused
+
+
 def test_a_bucket_schedule_with_a_hole_raises_before_any_update(model):
     """a gradient-ready schedule that does not cover every parameter must fail on the verification step, i.e.
     BEFORE a single AdamW launch has modified the weights (it used to be detected after the bucket-wise updates)."""
