@@ -770,6 +770,35 @@ int sm3_faith_compose(const float* x, const float* base, int base_n, const int* 
                       int64_t rank_stride_t, float* out, int N, int T, int HW, int k0, int c, int steps, int invert,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * RISE black-box saliency maps (Petsiuk et al., BMVC 2018; csrc/rise.hip; ABI 9, additive).  An image [3][H][W] f32, H * W a
+ * multiple of 4 and at most 2^24; a grid of s x s cells, 1 <= s <= min(H, W, 30); cells ch = ceil(H / s), cw = ceil(W / s);
+ * corner grid G x G bits, G = s + 2.  Mask i of modality m at pixel (y, x), with Y = y + oy, X = x + ox, gy = Y / ch, ry = Y % ch,
+ * gx = X / cw, rx = X % cw:
+ *   A = (ch - ry) (cw - rx) g[gy][gx] + (ch - ry) rx g[gy][gx + 1] + ry (cw - rx) g[gy + 1][gx] + ry rx g[gy + 1][gx + 1],
+ *   mask = (float)A / (float)(ch * cw): one correctly rounded f32 division.  Masks are regenerated from table rows, never stored.
+ * sm3_rise_table: table [c][36] uint32, row j for mask i = i0 + j: words 0 .. 31 the grid bits (bit gy * G + gx of the row,
+ *   little-endian in the words), word 32 oy, word 33 ox, words 34 and 35 zero.  Philox4x32-10 (as sm3_attr_noise), key = (seed
+ *   low word, seed high word), counter (q, i, modality, 1): bit 4q + l = (word l of call q) < thr, thr = floor(p * 2^32) in
+ *   float64; call ceil(G * G / 4): oy = (w0 * ch) >> 32, ox = (w1 * cw) >> 32 in 64-bit integers.  0 < p < 1 with thr > 0,
+ *   modality 0 or 1, 0 <= i0, i0 + c <= 2^20.  A row depends on (seed, modality, i, H, W, s, p) alone.
+ * sm3_rise_compose: out [c][N][3][HW] = base + mask_j * (x - base) as fadd(base, fmul(mask, fsub(x, base))), three separately
+ *   rounded f32 operations, the three channels of a pixel with the pixel's mask value; table: the rows of the c masks; x
+ *   [N][3][HW], base [base_n][3][HW] with base_n = 1 (shared) or N; N <= 65535, c <= 524 280 (groups of 8 masks on one grid
+ *   axis of 65 535).
+ * sm3_rise_accumulate: maps[n][t][p] (at maps[n * stride_n + t * stride_t + p], strides in elements, multiples of 4) =
+ *   acc / d, acc = (((0 + w[0][r] * mask_0[p]) + w[1][r] * mask_1[p]) + ...) over all M masks in ascending order, every product
+ *   and sum rounded on its own, r = n * T + t, weights [M][N * T] f32, table [M][36], d = (float)((double)M * p).  A thread owns 4
+ *   pixels x 8 rows.  1 <= M <= 2^20.
+ * Every pointer 16-byte aligned (weights: 4), SM3_EALIGN otherwise; sizes are checked on the host (SM3_EINVAL) before anything
+ * is launched.  No atomics: equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_rise_table(uint32_t* table, int i0, int c, int modality, int H, int W, int s, double p, uint64_t seed, void* stream);
+int sm3_rise_compose(const float* x, const float* base, int base_n, const uint32_t* table, float* out, int N, int H, int W, int s,
+                     int c, void* stream);
+int sm3_rise_accumulate(const uint32_t* table, const float* weights, float* maps, int64_t stride_n, int64_t stride_t, int N, int T,
+                        int M, int H, int W, int s, double p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,11 +21,11 @@
 // No atomics: every output is written once by a fixed order of operations on its own inputs.
 #include <math.h>
 
-#include "common.h"
+#include "exact_f32.h"
 
 // Contraction off for the file: every product and sum below is rounded on its own (the numpy restatements in the tests
 // depend on it).  The toolchain's fadd / fmul are plain + and * compiled under the default contraction, which the
-// backend still fuses after inlining, so the three operations are written here.
+// backend still fuses after inlining, so the three operations are written in exact_f32.h (shared with rise.hip).
 #pragma clang fp contract(off)
 
 namespace {
@@ -33,14 +33,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int64_t kMax31 = 0x7fffffffLL;
-
-__device__ __forceinline__ float fadd(float a, float b) { return a + b; }
-__device__ __forceinline__ float fsub(float a, float b) { return a - b; }
-__device__ __forceinline__ float fmul(float a, float b) { return a * b; }
-
-__device__ __forceinline__ float blend(float x, float b, float alpha) {
-    return fadd(b, fmul(alpha, fsub(x, b)));
-}
 
 __global__ void __launch_bounds__(kThreads) attr_path_kernel(const float4* __restrict__ x, const float4* __restrict__ base,
                                                              int base_n, float4* __restrict__ out, int64_t NE4, int64_t E4,
@@ -53,18 +45,6 @@ __global__ void __launch_bounds__(kThreads) attr_path_kernel(const float4* __res
     const float4 v = x[r];
     const float4 b = base[base_n == 1 ? r % E4 : r];
     out[i] = make_float4(blend(v.x, b.x, alpha), blend(v.y, b.y, alpha), blend(v.z, b.z, alpha), blend(v.w, b.w, alpha));
-}
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t w[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-    w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
 }
 
 __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& z0, float& z1) {

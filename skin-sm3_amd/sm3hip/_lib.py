@@ -179,6 +179,9 @@ SIGNATURES = {
     "sm3_faith_rank_workspace": [_I, _I],
     "sm3_faith_rank": [_P, _P, _I, _I, _P, _L, _P],
     "sm3_faith_compose": [_P, _P, _I, _P, _L, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "sm3_rise_table": [_P, _I, _I, _I, _I, _I, _I, _D, C.c_uint64, _P],
+    "sm3_rise_compose": [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sm3_rise_accumulate": [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _D, _P],
 }
 
 _lib = None

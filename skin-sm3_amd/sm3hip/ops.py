@@ -1408,6 +1408,61 @@ def faith_compose(x, base, ranks, out, k0, steps, invert):
               "sm3_faith_compose")
 
 
+RISE_ROW_WORDS = 36  # a mask's table row: 32 words of grid bits, oy, ox, two words of padding
+
+
+def _rise_table(table, name):
+    """The number of rows of a mask table [c, 36] int32."""
+    _chk(table, torch.int32, name)
+    if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] != RISE_ROW_WORDS:
+        raise ValueError(f"{name} must be int32 [masks, {RISE_ROW_WORDS}]")
+    return table.shape[0]
+
+
+def rise_table(table, i0, modality, H, W, cells, p, seed):
+    """The table rows of RISE masks i0 .. i0 + c - 1 of one modality (sm3_rise_table): table [c, 36] int32 -- the (cells + 2)^2
+    grid bits, then the shift (oy, ox).  A function of (seed, modality, mask, H, W, cells, p) alone."""
+    c = _rise_table(table, "table")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("rise_table: seed must fit 64 bits")
+    check(_lib.load().sm3_rise_table(_ptr(table), int(i0), c, int(modality), int(H), int(W), int(cells), float(p), seed,
+                                     _stream()), "sm3_rise_table")
+
+
+def rise_compose(x, base, table, out, cells):
+    """One modality's masked inputs (sm3_rise_compose): out [c, N, 3, H, W] fp32 = base + mask_j * (x - base) for the c masks of
+    table [c, 36]; x [N, 3, H, W], base [1 | N, 3, H, W]."""
+    N, E = _attr_rows(x, "x")
+    _chk(base, torch.float32, "base"); _chk(out, torch.float32, "out")
+    c = _rise_table(table, "table")
+    if x.dim() != 4 or x.shape[1] != 3 or out.dim() != 5:
+        raise ValueError("rise_compose: x [N, 3, H, W], out [c, N, 3, H, W]")
+    H, W = x.shape[2:]
+    if tuple(out.shape) != (c, N, 3, H, W) or base.numel() not in (E, N * E):
+        raise ValueError("rise_compose: x [N, 3, H, W], base [1 | N, 3, H, W], table [c, 36] and out [c, N, 3, H, W] do not match")
+    with _prof("rise_compose", 3.0 * out.numel(), 4.0 * (x.numel() + base.numel() + out.numel())):
+        check(_lib.load().sm3_rise_compose(_ptr(x), _ptr(base), base.numel() // E, _ptr(table), _ptr(out), N, H, W, int(cells), c,
+                                           _stream()), "sm3_rise_compose")
+
+
+def rise_accumulate(table, weights, maps, cells, p):
+    """maps [N, T, H, W] fp32 (a view whose pixels are contiguous: one modality of [N, T, 2, H, W]) = the sum over the M masks of
+    table [M, 36], in ascending order, of weights[i, n * T + t] * mask_i, every product and sum rounded on its own, divided by
+    (float)(M * p) (sm3_rise_accumulate).  weights [M, N * T] fp32."""
+    M = _rise_table(table, "table")
+    _chk(weights, torch.float32, "weights")
+    if maps.dim() != 4 or not maps.is_cuda or maps.dtype != torch.float32:
+        raise ValueError("rise_accumulate: maps must be fp32 [N, T, H, W] on the GPU (the SM3 HIP path has no CPU fallback)")
+    N, T, H, W = maps.shape
+    if maps.stride(3) != 1 or maps.stride(2) != W:
+        raise ValueError("rise_accumulate: the pixels of maps must be contiguous")
+    if tuple(weights.shape) != (M, N * T):
+        raise ValueError(f"rise_accumulate: weights must be [{M}, {N * T}] for table [{M}, 36] and maps {tuple(maps.shape)}")
+    with _prof("rise_accumulate", 2.0 * M * maps.numel(), 4.0 * (weights.numel() + maps.numel())):
+        check(_lib.load().sm3_rise_accumulate(_ptr(table), _ptr(weights), _ptr(maps), maps.stride(0), maps.stride(1), N, T, M, H,
+                                              W, int(cells), float(p), _stream()), "sm3_rise_accumulate")
+
+
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):
     """Stem weight gradient with bn1's backward apply fused into the operand load (sm3_stem_wgrad_bn; bf16 / fp16 / exact f32).
     slabs: fp32 workspace of STEM_WGRAD_SLABS * 64 * 147 floats -> fixed-order sum instead of float atomics."""

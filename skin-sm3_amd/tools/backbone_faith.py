@@ -5,10 +5,15 @@ predictions fall when the pixels a map calls important are taken away, and rise 
         --mean 0.7833 0.6712 0.6026 --std 0.2139 0.2472 0.2571 -b 8 -j 4 --img-sz 224 224 \
         --linear-path logs/eval/best_linear.pth --log-path logs/eval/faith --method ig --steps 32 --curve-steps 32 --max-cases 64
 
-Takes tools/backbone_cam.py's and tools/backbone_attr.py's command lines with --method cam|ig|smoothgrad|random (and that
-method's own flags: --cam-layer; --steps / --samples / --sigma / --squared / --attr-seed), --curve-steps, --curve-mode
+    python tools/backbone_faith.py ... --method rise --rise-masks 4000 --rise-cells 7 --rise-p 0.5 --curve-steps 32
+
+Takes tools/backbone_cam.py's and tools/backbone_attr.py's command lines with --method cam|ig|smoothgrad|random|rise (and that
+method's own flags: --cam-layer; --steps / --samples / --sigma / --squared / --attr-seed; --rise-masks / --rise-cells /
+--rise-p), --curve-steps, --curve-mode
 both|deletion|insertion, --modality joint|derm|clinic and --chunk (curve steps per encoder forward).  random ranks a uniform
-random map seeded by --attr-seed: the control a faithfulness table needs.  The maps are computed with the chosen method on the
+random map seeded by --attr-seed: the control a faithfulness table needs.  rise makes the black-box maps of sm3hip/rise.py
+(masks seeded by --attr-seed, the curves' baseline and --modality, the planned chunk) and also writes them: maps [n, 8, 2, H, W]
+fp16.  The maps are computed with the chosen method on the
 engine, then ranked and scored; the baseline is zero in normalised space (the dataset-mean image).  faith.pt goes to --log-path:
 deletion / insertion [n, 8, curve-steps + 1] fp64, deletion_auc / insertion_auc [n, 8] fp64, logits and baseline_logits (8
 tensors [n, classes]), targets [n, 8], target_class [n, 8], indices [n], method, labels.  A low deletion AUC and a high insertion
@@ -28,7 +33,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import explain_cli as cli  # noqa: E402
-from sm3hip import attr, cam, faith  # noqa: E402
+from sm3hip import attr, cam, faith, rise  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES  # noqa: E402
 
 
@@ -46,6 +51,9 @@ def make_maps(model, derm, clinic, args, gen):
         out = cam.grad_cam(model, derm, clinic, layer=args.cam_layer, target=args.target)
     elif args.method == "ig":
         out = attr.integrated_gradients(model, derm, clinic, target=args.target, steps=args.steps)
+    elif args.method == "rise":
+        out = rise.rise(model, derm, clinic, target=args.target, masks=args.rise_masks, cells=args.rise_cells, p=args.rise_p,
+                        seed=args.attr_seed, modality=args.modality)
     else:
         out = attr.smooth_grad(model, derm, clinic, target=args.target, samples=args.samples, sigma=args.sigma,
                                squared=args.squared, seed=args.attr_seed)
@@ -65,6 +73,8 @@ def run(args, parser, tool, mlc):
         curves = [n for n in ("deletion", "insertion") if args.curve_mode in ("both", n)]
         got = {k: out[k] for k in curves + [n + "_auc" for n in curves]}
         got.update(targets=lab, target_class=out["target_class"], logits=out["logits"], baseline_logits=out["baseline_logits"])
+        if args.method == "rise":
+            got["maps"] = maps.half()
         return got
 
     saved, stat = cli.explain(args, parser, tool, mlc, per_batch, "faith.pt",

@@ -13,9 +13,11 @@ from sm3hip.attr import METHODS as ATTR_METHODS
 from sm3hip.cam import STAGES, TARGETS
 from sm3hip.faith import MODALITIES, MODES
 from sm3hip.metrics import CLASSES_NAME
+from sm3hip.rise import MAX_CELLS, MAX_MASKS, threshold
 from src.models.baseline import Baseline
 
-FAITH_METHODS = ("cam", "ig", "smoothgrad", "random")
+ATTR_TOOL_METHODS = ATTR_METHODS + ("rise",)  # the attribution tools also make the black-box maps of sm3hip/rise.py
+FAITH_METHODS = ("cam", "ig", "smoothgrad", "random", "rise")
 
 
 # ---- parsers ----------------------------------------------------------------------------------------------------------------
@@ -51,9 +53,9 @@ def add_cases_args(p, verb="map"):
     return p
 
 
-def add_attr_args(p, method_help="ig (Integrated Gradients) or smoothgrad",
-                  chunk_help="path points / samples per encoder forward (default: from the free device memory); any value gives "
-                             "the same bits"):
+def add_attr_args(p, method_help="ig (Integrated Gradients), smoothgrad or rise (black-box: random masks, forward only)",
+                  chunk_help="path points / samples / masks per encoder forward (default: from the free device memory); any value "
+                             "gives the same bits"):
     """The flags the two attribution tools share (the place --cam-layer takes in the Grad-CAM tools)."""
     add_target_arg(p)
     p.add_argument("--method", default="ig", help=method_help)
@@ -61,27 +63,44 @@ def add_attr_args(p, method_help="ig (Integrated Gradients) or smoothgrad",
     p.add_argument("--samples", default=16, type=int, help="smoothgrad: noisy copies per image")
     p.add_argument("--sigma", default=0.15, type=float, help="smoothgrad: noise level relative to each image's max - min")
     p.add_argument("--squared", action="store_true", help="smoothgrad: average the squared gradients")
-    p.add_argument("--attr-seed", default=0, type=int, help="smoothgrad: seed of the noise")
+    p.add_argument("--attr-seed", default=0, type=int, help="smoothgrad: seed of the noise; rise: seed of the masks")
+    p.add_argument("--rise-masks", default=4000, type=int, help="rise: random masks per image pair")
+    p.add_argument("--rise-cells", default=7, type=int, help="rise: cells of the binary grid a mask is upsampled from, per side")
+    p.add_argument("--rise-p", default=0.5, type=float, help="rise: probability that a grid corner keeps the image")
     p.add_argument("--chunk", default=None, type=int, help=chunk_help)
     return add_cases_args(p, "attribute")
 
 
-def check_attr_args(args, tool):
-    """Refusals that need no device."""
-    if args.method not in ATTR_METHODS:
-        raise SystemExit(f"{tool}: --method {args.method} is not available (one of {', '.join(ATTR_METHODS)})")
+def check_rise_args(args, tool, size):
+    """The refusals of --method rise that need no device.  size: (H, W) of the images."""
+    if not 1 <= args.rise_masks <= MAX_MASKS:
+        raise SystemExit(f"{tool}: --rise-masks must be between 1 and {MAX_MASKS}")
+    if not 1 <= args.rise_cells <= min(MAX_CELLS, *size):
+        raise SystemExit(f"{tool}: --rise-cells must be between 1 and min(H, W, {MAX_CELLS}) = {min(MAX_CELLS, *size)}")
+    if not 0 < args.rise_p < 1 or threshold(args.rise_p) == 0:
+        raise SystemExit(f"{tool}: --rise-p must lie strictly between 0 and 1")
+    if (size[0] * size[1]) % 4:
+        raise SystemExit(f"{tool}: the image's H * W ({size[0]} x {size[1]}) must be a multiple of 4")
+
+
+def check_attr_args(args, tool, size):
+    """Refusals that need no device.  size: (H, W) of the images (what --method rise asks of them)."""
+    if args.method not in ATTR_TOOL_METHODS:
+        raise SystemExit(f"{tool}: --method {args.method} is not available (one of {', '.join(ATTR_TOOL_METHODS)})")
     if args.max_cases < 1:
         raise SystemExit(f"{tool}: --max-cases must be at least 1")
-    n = args.steps if args.method == "ig" else args.samples
-    name = "--steps" if args.method == "ig" else "--samples"
+    n, name = {"ig": (args.steps, "--steps"), "smoothgrad": (args.samples, "--samples"),
+               "rise": (args.rise_masks, "--rise-masks")}[args.method]
+    if args.method == "rise":
+        check_rise_args(args, tool, size)
     if n < 1:
         raise SystemExit(f"{tool}: {name} must be at least 1")
     if args.chunk is not None and not 1 <= args.chunk <= n:
         raise SystemExit(f"{tool}: --chunk must be between 1 and {name} ({n})")
     if args.sigma < 0:
         raise SystemExit(f"{tool}: --sigma must be non-negative")
-    if args.attr_seed < 0:
-        raise SystemExit(f"{tool}: --attr-seed must be non-negative")
+    if not 0 <= args.attr_seed < 2 ** 64:
+        raise SystemExit(f"{tool}: --attr-seed must be non-negative and below 2^64")
 
 
 def add_faith_args(p):
@@ -122,8 +141,10 @@ def check_faith_args(args, tool, size):
         raise SystemExit(f"{tool}: --samples must be at least 1")
     if args.method == "smoothgrad" and args.sigma < 0:
         raise SystemExit(f"{tool}: --sigma must be non-negative")
-    if args.attr_seed < 0:
-        raise SystemExit(f"{tool}: --attr-seed must be non-negative")
+    if args.method == "rise":
+        check_rise_args(args, tool, size)
+    if not 0 <= args.attr_seed < 2 ** 64:
+        raise SystemExit(f"{tool}: --attr-seed must be non-negative and below 2^64")
 
 
 # ---- the two subjects -------------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ MI355X (sm3hip/faith.py).
         --log-path logs/mlc_eval/faith --method cam --cam-layer layer4 --curve-steps 32 --split test --max-cases 64
 
 Takes tools/mlc_cam.py's and tools/mlc_attr.py's command lines (mlc_eval's model and data flags, --checkpoint, --target, --split,
---max-cases) with the flags of tools/backbone_faith.py (--method cam|ig|smoothgrad|random and that method's own flags,
+--max-cases) with the flags of tools/backbone_faith.py (--method cam|ig|smoothgrad|random|rise and that method's own flags,
 --curve-steps, --curve-mode, --modality, --chunk).  The heads run in eval semantics.  faith.pt goes to --log-path with the fields
 backbone_faith writes.
 """
