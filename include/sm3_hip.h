@@ -799,6 +799,33 @@ int sm3_rise_compose(const float* x, const float* base, int base_n, const uint32
 int sm3_rise_accumulate(const uint32_t* table, const float* weights, float* maps, int64_t stride_n, int64_t stride_t, int N, int T,
                         int M, int H, int W, int s, double p, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Evaluation report: the integer counts behind AUROC, Recall, Spec and Prec of every (label, class) column, for the point
+ * estimate and for case-resampling bootstrap replicates (csrc/report.hip, sm3hip/report.py; ABI 9, additive).
+ * N cases, T labels, K columns; colmap [K][2] int32 = (label t, class c) of column k;
+ * targets, yhat [N][T] int32 (class indices below 256; yhat = the predicted class, lowest index of the row maximum);
+ * per column the score softmax(logits_t.double())[:, c] sorted ascending and stably ONCE: order [K][N] int32 = the case at sorted
+ * position j, gs / ge [K][N] int32 = first and one-past-last sorted position of j's tie group (ties by == on the fp64 scores).
+ * With integer case multiplicities m[n] >= 0, sum m = N:
+ *   P = sum m[y == c], Q = N - P, S[j] = sum of m over the negative cases at sorted positions < j,
+ *   A2 = sum over positive j of m_j * (S[gs[j]] + S[ge[j]])   (twice the negatives strictly below, plus the tied negatives),
+ *   TP = sum m[y == c & yhat == c], FP = sum m[y != c & yhat == c], FN = sum m[y == c & yhat != c]   (TN = N - TP - FP - FN),
+ * so that AUC = A2 / (2 P Q), Recall = TP / (TP + FN), Spec = TN / (TN + FP), Prec = TP / (TP + FP), one fp64 division each on
+ * the host, 0 when the denominator is 0.
+ * sm3_report_counts: out [c][K][6] int64 = (A2, P, Q, TP, FP, FN) for replicates r = r0 .. r0 + c - 1, one workgroup per
+ *   (replicate, label); a column whose label is outside [0, T) is left unwritten.
+ *   point != 0: m = 1 everywhere, c must be 1, no random words.  Otherwise draw d, 0 <= d < N, hits case (w * N) >> 32 in 64-bit
+ *   integers, w = word d % 4 of Philox4x32-10 (as sm3_attr_noise), key = (seed low word, seed high word), counter (d / 4, r, 0, 2)
+ *   -- the last word keeps the stream apart from SmoothGrad's 0 and RISE's 1 -- and m_r[i] = the number of draws that hit case
+ *   i, shared by all columns.  A replicate is a function of (seed, r, N) alone.  1 <= N <= sm3_report_max_cases() (8192: m and S
+ *   live in LDS), 1 <= T <= 64, 1 <= K <= 64, c >= 1, 0 <= r0, r0 + c <= 2^32; SM3_EINVAL otherwise, before anything is
+ *   launched.  Entries of order are clamped to N - 1 and of gs / ge to N: no input can make an access leave its array.
+ *   Integer sums only, no float anywhere: equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_report_max_cases(void);
+int sm3_report_counts(const int* order, const int* gs, const int* ge, const int* targets, const int* yhat, const int* colmap,
+                      int64_t* out, int N, int T, int K, uint64_t seed, int64_t r0, int c, int point, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1463,6 +1463,35 @@ def rise_accumulate(table, weights, maps, cells, p):
                                               W, int(cells), float(p), _stream()), "sm3_rise_accumulate")
 
 
+REPORT_MAX_CASES = 8192  # sm3_report_max_cases(): the multiplicities and the prefix sums of a replicate live in LDS
+
+
+def report_counts(order, gs, ge, targets, yhat, colmap, out, seed, r0, point=False):
+    """out [c, K, 6] int64 = (A2, P, Q, TP, FP, FN) of the K columns for bootstrap replicates r0 .. r0 + c - 1, or for the point
+    estimate (point: c = 1, every case once) (sm3_report_counts).  order, gs, ge [K, N] int32: per column the cases in ascending
+    score order and the bounds of each position's tie group; targets, yhat [N, T] int32; colmap [K, 2] int32 = (label, class)."""
+    for t, n in ((order, "order"), (gs, "gs"), (ge, "ge"), (targets, "targets"), (yhat, "yhat"), (colmap, "colmap")):
+        _chk(t, torch.int32, n)
+    _chk(out, torch.int64, "out")
+    if order.dim() != 2 or targets.dim() != 2 or out.dim() != 3:
+        raise ValueError("report_counts: order [K, N], targets [N, T] and out [c, K, 6]")
+    K, N = order.shape
+    T = targets.shape[1]
+    c = out.shape[0]
+    if N > REPORT_MAX_CASES:
+        raise ValueError(f"report_counts: {N} cases, at most {REPORT_MAX_CASES} supported")
+    if tuple(gs.shape) != (K, N) or tuple(ge.shape) != (K, N) or tuple(targets.shape) != (N, T) or \
+            tuple(yhat.shape) != (N, T) or tuple(colmap.shape) != (K, 2) or tuple(out.shape) != (c, K, 6):
+        raise ValueError("report_counts: order, gs, ge [K, N], targets, yhat [N, T], colmap [K, 2] and out [c, K, 6] do not match")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("report_counts: seed must fit 64 bits")
+    if point and c != 1:
+        raise ValueError("report_counts: the point estimate is one table")
+    with _prof("report_counts", 0.0, 4.0 * 3 * K * N * c):
+        check(_lib.load().sm3_report_counts(_ptr(order), _ptr(gs), _ptr(ge), _ptr(targets), _ptr(yhat), _ptr(colmap), _ptr(out),
+                                            N, T, K, seed, int(r0), c, int(bool(point)), _stream()), "sm3_report_counts")
+
+
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):
     """Stem weight gradient with bn1's backward apply fused into the operand load (sm3_stem_wgrad_bn; bf16 / fp16 / exact f32).
     slabs: fp32 workspace of STEM_WGRAD_SLABS * 64 * 147 floats -> fixed-order sum instead of float atomics."""

@@ -5,7 +5,9 @@ tools/backbone_eval.py (train :65-142, validate :145-212, checkpoint key split :
         --finetune fc --pretrain-path logs/backbone/ckp_50.pth --epochs 2 --steps-per-epoch 10
 
 `--finetune fc`: encoders frozen and in eval mode (one fused conv+BN+ReLU kernel per layer), the 8 heads trained
-with AdamW on the weighted cross-entropy sum/8; AUROC "8 avg" (sm3hip.metrics.auc_avg) on the validation pass.
+with AdamW on the weighted cross-entropy sum/8; AUROC "8 avg" (sm3hip.metrics.auc_avg) on the validation pass, and with it the
+reference's Recall / Spec / Prec of the 8 labels (sm3hip.report).  The validation pass of the last epoch writes val_report.json
+and val_report.csv (the reference's table layout) to --log-path; --bootstrap B adds case-resampling intervals to them.
 Any other value fine-tunes everything through the autograd bridge.
 
 `--data-name SevenPCBaseDataset --data-path DIR`: derm7pt's train and test splits decoded once into the device image store
@@ -28,6 +30,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
+from sm3hip import report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.baseline import Baseline  # noqa: E402
 
@@ -42,6 +45,7 @@ def get_parser():
     # this build (synthetic data: an epoch is a number of steps)
     p.add_argument("--steps-per-epoch", default=8, type=int)
     p.add_argument("--val-steps", default=4, type=int)
+    report.add_flags(p)
     p.set_defaults(arch="resnet50", epochs=50, batch_size=128)
     return p
 
@@ -156,11 +160,14 @@ def main(argv=None):
         tr = run_epoch(args, evaluator, criterion, optimizer, args.steps_per_epoch, gen, dev, True, train_data(epoch))
         va = run_epoch(args, evaluator, criterion, None, args.val_steps, gen, dev, False, val_data(epoch))
         history.append((tr, va))
+        new, rep = report.validation_stats(va["preds"], va["targets"], args, epoch == args.epochs - 1, args.log_path)
+        va.update(new)
         if real:
             torch.save({"epoch": epoch + 1, "preds": [p.cpu() for p in va["preds"]], "targets": va["targets"].cpu(),
                         "AUC_AVG": va["AUC_AVG"]}, os.path.join(args.log_path, "val_predictions.pt"))
         print(f"epoch {epoch}: train loss {tr['loss']:.4f} AUC_AVG {tr['AUC_AVG']:.4f} {tr['pairs_per_s']:.0f} pairs/s | "
               f"val loss {va['loss']:.4f} AUC_AVG {va['AUC_AVG']:.4f} {va['pairs_per_s']:.0f} pairs/s", flush=True)
+        print(f"epoch {epoch}: val {report.stats_line(va, rep)}", flush=True)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG (backbone_eval.py:386,405-411)
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},

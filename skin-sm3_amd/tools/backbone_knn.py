@@ -10,7 +10,9 @@ Takes backbone_eval's command line (and its checkpoint loader and data helpers) 
 frozen and in eval mode (one fused conv + BN + ReLU kernel per layer); a case's feature is normalize(cat(derm_f, clinic_f))
 (sm3_normalize_rows), both splits through the validation chain (Resize -> Normalize of the whole image).  Per label the votes
 become fractions p = votes / sum(votes); AUC_AVG is sm3hip.metrics.auc_avg of log p (softmax(log p) = p) and top-1 is the
-first of the stable descending order, as KNNOnlineEvaluator.predict ranks.  knn_predictions.pt goes to --log-path.
+first of the stable descending order, as KNNOnlineEvaluator.predict ranks.  knn_predictions.pt goes to --log-path, and with it
+val_report.json / val_report.csv: Recall / Spec / Prec and every class's AUROC of the same log p (sm3hip.report; --bootstrap B
+adds case-resampling intervals).
 `--data-name synthetic`: --steps-per-epoch batches form the bank, --val-steps batches the queries; --random-features N B D
 replaces the encoders by N bank and B query rows of unit-norm random features of width D (the kNN stage alone, at bank sizes
 no encoder pass in a test reaches).
@@ -30,6 +32,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import backbone_eval  # noqa: E402
+from sm3hip import report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.baseline import Baseline  # noqa: E402
 
@@ -121,6 +124,8 @@ def main(argv=None):
     stat.update({"AUC_AVG": float(avg), "bank": bank.N, "queries": query_f.shape[0],
                  "pairs_per_s": (bank.N + query_f.shape[0]) / seconds})
     os.makedirs(args.log_path, exist_ok=True)
+    new, rep = report.validation_stats([p.log() for p in probs], query_t, args, True, args.log_path)
+    stat.update(new)
     saved = {"votes": [v.cpu() for v in votes], "targets": query_t.cpu(), "AUC_AVG": stat["AUC_AVG"],
              "AUC": [float(a) for a in per], "top1": top1, "k": args.knn_k, "temperature": args.knn_t, "bank_size": bank.N}
     if args.save_features:
@@ -129,6 +134,7 @@ def main(argv=None):
     print(f"knn k={args.knn_k} T={args.knn_t}: AUC_AVG {stat['AUC_AVG']:.4f} | top-1 "
           + " ".join(f"{n} {a:.3f}" for n, a in zip(CLASSES_NAME, top1))
           + f" | bank {bank.N} queries {query_f.shape[0]} | {stat['pairs_per_s']:.0f} pairs/s", flush=True)
+    print(f"knn k={args.knn_k} T={args.knn_t}: {report.stats_line(stat, rep)}", flush=True)
     return stat
 
 

@@ -1,7 +1,9 @@
 """Supervised fine-tuning / evaluation of the multi-label model on MI355X -- entry point mirroring the reference's
 tools/mlc_eval.py (Model :67-115 with BIASED prototypes, train :118-200, validate :203-280, freeze modes :374-388,
 run.sh:49-61): loads a tools/mlc_train.py checkpoint (strict=False: the bias-free DeepCluster prototypes are replaced),
-trains with the weighted cross-entropy sum / 8 against the real labels, reports AUROC "8 avg" (sm3hip.metrics).
+trains with the weighted cross-entropy sum / 8 against the real labels, reports AUROC "8 avg" (sm3hip.metrics) and, on the
+validation pass, the reference's Recall / Spec / Prec of the 8 labels (sm3hip.report); the last epoch's validation pass writes
+val_report.json / val_report.csv (--bootstrap B: with intervals) and, under real data, val_predictions.pt to --log-path.
 
     python tools/mlc_eval.py --data-name synthetic -a resnet50 -b 128 -lr 1e-3 --epochs 2 --mlc-proj v4 \
         --mlc-proj-dim 512 --num-heads 1 --sa-dim-ff 128 --sa-dropout 0.1 --finetune projector \
@@ -32,6 +34,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
+from sm3hip import report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.projector import build_mlc_projectors  # noqa: E402
 from src.models.simclr import SimCLRSkinV32  # noqa: E402
@@ -83,6 +86,7 @@ def get_parser():
     # this build (synthetic data: an epoch is a number of steps)
     p.add_argument("--steps-per-epoch", type=int, default=8)
     p.add_argument("--val-steps", type=int, default=4)
+    report.add_flags(p)
     p.set_defaults(arch="resnet50", batch_size=128, finetune="projector", pretrain_path="", log_path="./logs/mlc_eval")
     return p
 
@@ -109,7 +113,8 @@ def set_train_modes(evaluator, finetune):
         evaluator.mlc_sa.eval()
 
 
-def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, data=None):
+def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, data=None, keep=None):
+    """keep: a dict that receives the pass's "preds" (8 x [N, n_t]) and "targets" [N, 8]; the returned stat holds numbers only."""
     if train:  # the reference's mode matrix, tools/mlc_eval.py:124-138
         set_train_modes(evaluator, args.finetune)
     else:
@@ -142,6 +147,8 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, dat
     per, avg = auc_avg(preds, torch.cat(targets_all))
     stat = {f"AUC_{n}": float(v) for n, v in zip(CLASSES_NAME, per)}
     stat.update({"AUC_AVG": float(avg), "loss": total / steps, "pairs_per_s": pairs / (time.time() - t0)})
+    if keep is not None:
+        keep["preds"], keep["targets"] = preds, torch.cat(targets_all)
     return stat
 
 
@@ -209,10 +216,17 @@ def main(argv=None):
     best, history = -1.0, []
     for epoch in range(args.epochs):
         tr = run_epoch(args, evaluator, criterion, optimizer, args.steps_per_epoch, gen, dev, True, train_data(epoch))
-        va = run_epoch(args, evaluator, criterion, None, args.val_steps, gen, dev, False, val_data(epoch))
+        kept = {}
+        va = run_epoch(args, evaluator, criterion, None, args.val_steps, gen, dev, False, val_data(epoch), keep=kept)
         history.append((tr, va))
+        new, rep = report.validation_stats(kept["preds"], kept["targets"], args, epoch == args.epochs - 1, args.log_path)
+        va.update(new)
+        if real:  # backbone_eval's format
+            torch.save({"epoch": epoch + 1, "preds": [p.cpu() for p in kept["preds"]], "targets": kept["targets"].cpu(),
+                        "AUC_AVG": va["AUC_AVG"]}, os.path.join(args.log_path, "val_predictions.pt"))
         print(f"epoch {epoch}: train loss {tr['loss']:.4f} AUC_AVG {tr['AUC_AVG']:.4f} {tr['pairs_per_s']:.0f} pairs/s | "
               f"val loss {va['loss']:.4f} AUC_AVG {va['AUC_AVG']:.4f}", flush=True)
+        print(f"epoch {epoch}: val {report.stats_line(va, rep)}", flush=True)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},
