@@ -826,6 +826,34 @@ int sm3_report_max_cases(void);
 int sm3_report_counts(const int* order, const int* gs, const int* ge, const int* targets, const int* yhat, const int* colmap,
                       int64_t* out, int N, int T, int K, uint64_t seed, int64_t r0, int c, int point, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Calibration report: the integer bin tables behind ECE, MCE and the reliability diagram and the integer sums behind NLL and
+ * the Brier score, for the point estimate and for case-resampling bootstrap replicates (csrc/calib.hip,
+ * sm3hip/calibration.py; ABI 9, additive).
+ * N cases, S series, X plain sums, T labels, M bins.  A series s is q [S][N] int64 (a probability in Q32, rint(p * 2^32), 0 <= q
+ * <= 2^32) with the event ev [S][N] uint8 (0 / 1; any non-zero byte counts as 1); order [S][N] int32 = the case at sorted
+ * position j of the series' stable ascending sort by q (a permutation of the cases); slabel [S] int32 = the label of series s;
+ * xq [X][N] int64 = the per-case terms of plain sum x (each below 2^43, so that N of them stay below 2^56).
+ * With integer case multiplicities m[n] >= 0, sum m = N:
+ *   binning 0 (width): every copy of case n goes to bin min((q * M) >> 32, M - 1), in 64-bit integers;
+ *   binning 1 (mass):  the case at sorted position j owns the copy ranks [R_j, R_j + m_j), R_j = the sum of m over the
+ *                      positions < j; the copy at rank u goes to bin (u * M) / N (integer division), so a case whose ranks
+ *                      straddle a boundary is split copy by copy, and M > N leaves empty bins;
+ *   per series and bin: n_b = copies, E_b = sum of the copies' ev, Q_b = sum of the copies' q;  per plain sum: sum m[n] xq[x][n].
+ * sm3_calib_counts: bins [c][S][M][3] int64 = (n_b, E_b, Q_b) and sums [c][X] int64 for replicates r = r0 .. r0 + c - 1, one
+ *   workgroup per (replicate, label), which serves the series of its label and the plain sums x with x % T == label; a series
+ *   whose label is outside [0, T) is left unwritten.  point != 0: m = 1 everywhere, c must be 1, no random words.  Otherwise
+ *   m_r is the multiplicity vector of sm3_report_counts, exactly: draw d hits case (w * N) >> 32, w = word d % 4 of
+ *   Philox4x32-10, key = (seed low word, seed high word), counter (d / 4, r, 0, 2) -- with one seed, replicate r of both
+ *   reports resamples the same cases.  1 <= N <= sm3_report_max_cases(), 1 <= S, X, T <= 64, 1 <= M <= 64, binning 0 or 1,
+ *   c >= 1, 0 <= r0, r0 + c <= 2^32; SM3_EINVAL otherwise, before anything is launched.  Entries of order are clamped to
+ *   N - 1 and bin indices to M - 1: no input can make an access leave its array.  Integer sums only, no float anywhere: equal
+ *   inputs give equal bits.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_calib_counts(const int64_t* q, const uint8_t* ev, const int* order, const int* slabel, const int64_t* xq, int64_t* bins,
+                     int64_t* sums, int N, int S, int X, int T, int M, int binning, uint64_t seed, int64_t r0, int c, int point,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,7 @@ SIGNATURES = {
     "sm3_rise_accumulate": [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _D, _P],
     "sm3_report_max_cases": [],
     "sm3_report_counts": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
+    "sm3_calib_counts": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
 }
 
 _lib = None

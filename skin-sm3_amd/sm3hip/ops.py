@@ -1492,6 +1492,42 @@ def report_counts(order, gs, ge, targets, yhat, colmap, out, seed, r0, point=Fal
                                             N, T, K, seed, int(r0), c, int(bool(point)), _stream()), "sm3_report_counts")
 
 
+CALIB_MAX_BINS = 64
+CALIB_BINNINGS = ("width", "mass")
+
+
+def calib_counts(q, ev, order, slabel, xq, bins, sums, labels, binning, seed, r0, point=False):
+    """bins [c, S, M, 3] int64 = (n_b, E_b, Q_b) of the S series and sums [c, X] int64 of the X plain sums for bootstrap replicates
+    r0 .. r0 + c - 1, or for the point estimate (point: c = 1, every case once) (sm3_calib_counts).  q [S, N] int64 (Q32), ev
+    [S, N] uint8, order [S, N] int32 (each series' cases in ascending q, stable), slabel [S] int32 = the label of a series, xq
+    [X, N] int64; labels: T, the number of labels (plain sum x is served with label x % T); binning: "width" or "mass"."""
+    for t, n in ((q, "q"), (xq, "xq"), (bins, "bins"), (sums, "sums")):
+        _chk(t, torch.int64, n)
+    _chk(ev, torch.uint8, "ev"); _chk(order, torch.int32, "order"); _chk(slabel, torch.int32, "slabel")
+    if q.dim() != 2 or xq.dim() != 2 or bins.dim() != 4 or sums.dim() != 2:
+        raise ValueError("calib_counts: q [S, N], xq [X, N], bins [c, S, M, 3] and sums [c, X]")
+    S, N = q.shape
+    X = xq.shape[0]
+    c, M = bins.shape[0], bins.shape[2]
+    if not 1 <= N <= REPORT_MAX_CASES:
+        raise ValueError(f"calib_counts: {N} cases, 1 to {REPORT_MAX_CASES} are supported")
+    if not 1 <= M <= CALIB_MAX_BINS:
+        raise ValueError(f"calib_counts: {M} bins, 1 to {CALIB_MAX_BINS} are supported")
+    if tuple(ev.shape) != (S, N) or tuple(order.shape) != (S, N) or tuple(slabel.shape) != (S,) or tuple(xq.shape) != (X, N) or \
+            tuple(bins.shape) != (c, S, M, 3) or tuple(sums.shape) != (c, X):
+        raise ValueError("calib_counts: q, ev, order [S, N], slabel [S], xq [X, N], bins [c, S, M, 3] and sums [c, X] do not match")
+    if binning not in CALIB_BINNINGS:
+        raise ValueError(f"calib_counts: binning must be one of {CALIB_BINNINGS}, got {binning!r}")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("calib_counts: seed must fit 64 bits")
+    if point and c != 1:
+        raise ValueError("calib_counts: the point estimate is one table")
+    with _prof("calib_counts", 0.0, (8.0 + 4 + 1) * S * N * c):
+        check(_lib.load().sm3_calib_counts(_ptr(q), _ptr(ev), _ptr(order), _ptr(slabel), _ptr(xq), _ptr(bins), _ptr(sums), N, S, X,
+                                           int(labels), M, CALIB_BINNINGS.index(binning), seed, int(r0), c, int(bool(point)),
+                                           _stream()), "sm3_calib_counts")
+
+
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):
     """Stem weight gradient with bn1's backward apply fused into the operand load (sm3_stem_wgrad_bn; bf16 / fp16 / exact f32).
     slabs: fp32 workspace of STEM_WGRAD_SLABS * 64 * 147 floats -> fixed-order sum instead of float atomics."""

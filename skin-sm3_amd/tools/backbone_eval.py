@@ -8,6 +8,8 @@ tools/backbone_eval.py (train :65-142, validate :145-212, checkpoint key split :
 with AdamW on the weighted cross-entropy sum/8; AUROC "8 avg" (sm3hip.metrics.auc_avg) on the validation pass, and with it the
 reference's Recall / Spec / Prec of the 8 labels (sm3hip.report).  The validation pass of the last epoch writes val_report.json
 and val_report.csv (the reference's table layout) to --log-path; --bootstrap B adds case-resampling intervals to them.
+--calibration adds val_calibration.json / .csv of the same pass at T = 1 (sm3hip.calibration: NLL, Brier, ECE, MCE, class-wise ECE and
+the reliability diagram; --calib-bins M, --calib-binning width|mass; the same bootstrap replicates).
 Any other value fine-tunes everything through the autograd bridge.
 
 `--data-name SevenPCBaseDataset --data-path DIR`: derm7pt's train and test splits decoded once into the device image store
@@ -30,13 +32,14 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from sm3hip import report  # noqa: E402
+from sm3hip import calibration, report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.baseline import Baseline  # noqa: E402
 
 
-def get_parser():
-    """src/utils/misc.py:get_parser + tools/backbone_eval.py:434-440 of the reference, then this build's own flags."""
+def get_parser(calibration_flags=True):
+    """src/utils/misc.py:get_parser + tools/backbone_eval.py:434-440 of the reference, then this build's own flags
+    (calibration_flags=False: without --calibration and its two settings, for backbone_knn, whose votes are not logits)."""
     from src.utils.misc import get_parser as base_parser
     p = base_parser("SM3 linear probe / fine-tune (MI355X)")
     p.add_argument("--arch-weights", type=str, default=None)
@@ -46,6 +49,8 @@ def get_parser():
     p.add_argument("--steps-per-epoch", default=8, type=int)
     p.add_argument("--val-steps", default=4, type=int)
     report.add_flags(p)
+    if calibration_flags:
+        calibration.add_flags(p)
     p.set_defaults(arch="resnet50", epochs=50, batch_size=128)
     return p
 
@@ -121,6 +126,7 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, dat
 def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
+    calibration.check_flags(args)
     from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
     require_baseline_arch(args.arch, "backbone_eval")
     real = require_data(args, "backbone_eval")
@@ -168,6 +174,9 @@ def main(argv=None):
         print(f"epoch {epoch}: train loss {tr['loss']:.4f} AUC_AVG {tr['AUC_AVG']:.4f} {tr['pairs_per_s']:.0f} pairs/s | "
               f"val loss {va['loss']:.4f} AUC_AVG {va['AUC_AVG']:.4f} {va['pairs_per_s']:.0f} pairs/s", flush=True)
         print(f"epoch {epoch}: val {report.stats_line(va, rep)}", flush=True)
+        if args.calibration and epoch == args.epochs - 1:  # val_calibration.json / .csv next to val_report.*
+            cal = calibration.validation_calibration(va["preds"], va["targets"], args, args.log_path)
+            print(f"epoch {epoch}: val {calibration.stats_line(cal)}", flush=True)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG (backbone_eval.py:386,405-411)
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},

@@ -10,6 +10,16 @@ log of the vote fraction).  Prints the table, writes <name>_report.json and <nam
 next to PRED.pt or under --out.  With --against OTHER.pt both files must hold the same cases (equal targets); the replicates
 are a function of the seed, so replicate r resamples the same cases in both and the difference PRED - OTHER is paired:
 its interval and the fraction of replicates with a difference <= 0 are printed and written to <name>_compare.json.
+
+    python tools/eval_report.py logs/linear/val_predictions.pt --bootstrap 2000 --calibration --calib-binning mass
+    python tools/eval_report.py logs/linear/test_predictions.pt --bootstrap 2000 --fit-on logs/linear/val_predictions.pt
+
+--calibration adds the calibration report (sm3hip/calibration.py: NLL, Brier, ECE and MCE of the top label, class-wise ECE, the
+reliability diagram; --calib-bins M, --calib-binning width|mass) with the SAME bootstrap replicates, written to
+<name>_calibration.json / .csv.  --fit-on OTHER.pt (implies --calibration) fits one temperature per label on OTHER.pt, for
+example the validation split's predictions, and reports PRED.pt both at T = 1 and at the fitted temperatures
+(<name>_calibration_fitted.json / .csv), with the paired difference fitted - unscaled and its interval
+(<name>_calibration_compare.json).
 """
 import argparse
 import json
@@ -24,7 +34,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 
 import torch  # noqa: E402
 
-from sm3hip import report  # noqa: E402
+from sm3hip import calibration, report  # noqa: E402
 
 
 def get_parser():
@@ -34,6 +44,9 @@ def get_parser():
     p.add_argument("--out", default=None, help="directory of the JSON / CSV files (default: next to PRED.pt)")
     p.add_argument("--chunk", type=int, default=None, help="bootstrap replicates per launch (any value gives the same bits)")
     report.add_flags(p)
+    calibration.add_flags(p)
+    p.add_argument("--fit-on", metavar="OTHER.pt", default=None,
+                   help="fit the temperatures on this predictions file; report PRED.pt at T = 1 and at the fitted T (implies --calibration)")
     return p
 
 
@@ -50,8 +63,40 @@ def format_compare(cmp):
     return "\n".join(lines)
 
 
+def _dump(obj, path):
+    with open(path, "w") as f:
+        json.dump({k: (v.tolist() if isinstance(v, torch.Tensor) else v) for k, v in obj.items()}, f, indent=1)
+
+
+def calibrate(args, preds, targets, kw, out, stem, dev):
+    """The --calibration / --fit-on part: prints the tables, writes the files, returns what it computed."""
+    if targets.shape[0] > report.MAX_CASES:
+        print(calibration.stats_line(None), flush=True)
+        return {}
+    ckw = dict(kw, bins=args.calib_bins, binning=args.calib_binning)
+    cal = calibration.calibration_report(preds, targets, **ckw)
+    print(calibration.format_table(cal), flush=True)
+    calibration.save(cal, out, stem + "_calibration")
+    result = {"calibration": cal}
+    if args.fit_on:
+        fit = calibration.fit_temperature(*report.load_predictions(args.fit_on, dev))
+        print(f"temperatures fitted on {args.fit_on}: " + " ".join(
+            f"{n} {v:.4f}{' (clipped)' if c else ''}" for n, v, c in zip(calibration.CLASSES_NAME, fit["temperature"], fit["clipped"])),
+            flush=True)
+        fitted = calibration.calibration_report(preds, targets, temperature=fit["temperature"], **ckw)
+        print(calibration.format_table(fitted), flush=True)
+        calibration.save(fitted, out, stem + "_calibration_fitted")
+        cmp = calibration.compare(fitted, cal)
+        print("fitted - unscaled", flush=True)
+        print(calibration.format_compare(cmp), flush=True)
+        _dump(dict(cmp, fit=fit), os.path.join(out, stem + "_calibration_compare.json"))
+        result.update({"fit": fit, "calibration_fitted": fitted, "calibration_compare": cmp})
+    return result
+
+
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    calibration.check_flags(args)
     out = args.out or os.path.dirname(os.path.abspath(args.pred))
     stem = os.path.splitext(os.path.basename(args.pred))[0]
     kw = dict(bootstrap=args.bootstrap, confidence=args.confidence, seed=args.bootstrap_seed, chunk=args.chunk)
@@ -71,6 +116,8 @@ def main(argv=None):
         with open(os.path.join(out, stem + "_compare.json"), "w") as f:
             json.dump({k: (v.tolist() if isinstance(v, torch.Tensor) else v) for k, v in cmp.items()}, f, indent=1)
         result.update({"other": other, "compare": cmp})
+    if args.calibration or args.fit_on:
+        result.update(calibrate(args, preds, targets, kw, out, stem, dev))
     return result
 
 

@@ -4,6 +4,7 @@ run.sh:49-61): loads a tools/mlc_train.py checkpoint (strict=False: the bias-fre
 trains with the weighted cross-entropy sum / 8 against the real labels, reports AUROC "8 avg" (sm3hip.metrics) and, on the
 validation pass, the reference's Recall / Spec / Prec of the 8 labels (sm3hip.report); the last epoch's validation pass writes
 val_report.json / val_report.csv (--bootstrap B: with intervals) and, under real data, val_predictions.pt to --log-path.
+--calibration adds val_calibration.json / .csv of that pass at T = 1 (sm3hip.calibration; --calib-bins, --calib-binning).
 
     python tools/mlc_eval.py --data-name synthetic -a resnet50 -b 128 -lr 1e-3 --epochs 2 --mlc-proj v4 \
         --mlc-proj-dim 512 --num-heads 1 --sa-dim-ff 128 --sa-dropout 0.1 --finetune projector \
@@ -34,7 +35,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from sm3hip import report  # noqa: E402
+from sm3hip import calibration, report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.projector import build_mlc_projectors  # noqa: E402
 from src.models.simclr import SimCLRSkinV32  # noqa: E402
@@ -87,6 +88,7 @@ def get_parser():
     p.add_argument("--steps-per-epoch", type=int, default=8)
     p.add_argument("--val-steps", type=int, default=4)
     report.add_flags(p)
+    calibration.add_flags(p)
     p.set_defaults(arch="resnet50", batch_size=128, finetune="projector", pretrain_path="", log_path="./logs/mlc_eval")
     return p
 
@@ -155,6 +157,7 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, dat
 def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
+    calibration.check_flags(args)
     from src.utils.misc import ignored_line, require_data, require_mlc_arch, require_mlc_proj
     require_mlc_arch(args.arch, "mlc_eval")
     require_mlc_proj(args, "mlc_eval")
@@ -227,6 +230,9 @@ def main(argv=None):
         print(f"epoch {epoch}: train loss {tr['loss']:.4f} AUC_AVG {tr['AUC_AVG']:.4f} {tr['pairs_per_s']:.0f} pairs/s | "
               f"val loss {va['loss']:.4f} AUC_AVG {va['AUC_AVG']:.4f}", flush=True)
         print(f"epoch {epoch}: val {report.stats_line(va, rep)}", flush=True)
+        if args.calibration and epoch == args.epochs - 1:  # val_calibration.json / .csv next to val_report.*
+            cal = calibration.validation_calibration(kept["preds"], kept["targets"], args, args.log_path)
+            print(f"epoch {epoch}: val {calibration.stats_line(cal)}", flush=True)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},
