@@ -30,13 +30,18 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     const int64_t n4 = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // The float4 body and the scalar tail are two instances of this update.  Left to the compiler's FMA contraction they
+    // were fused differently, and the last n % 4 elements of a buffer got other bits than the same (p, g, m, v) anywhere
+    // else in it.  So the fusions are written out -- the ones the float4 body has always had -- and nothing else is
+    // contracted: the update is a function of (p, g, m, v) alone.
+    const float decay = fmaf(-lr, wd, 1.f), step_size = lr * inv_bc1;
     auto upd = [&](float& pp, float gg, float& mm, float& vv) {
+#pragma clang fp contract(off)
         gg *= gscale;
-        pp *= (1.f - lr * wd);
-        mm = b1 * mm + (1.f - b1) * gg;
-        vv = b2 * vv + (1.f - b2) * gg * gg;
-        const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
-        pp -= lr * inv_bc1 * (mm / denom);
+        mm = fmaf(1.f - b1, gg, b1 * mm);
+        vv = fmaf((1.f - b2) * gg, gg, b2 * vv);
+        const float denom = fmaf(sqrtf(vv), inv_sqrt_bc2, eps);
+        pp = fmaf(decay, pp, -(step_size * (mm / denom)));
     };
     for (int64_t i = t0; i < n4; i += stride) {
         float4 pp = reinterpret_cast<float4*>(p)[i];
@@ -127,16 +132,22 @@ extern "C" int sm3_loss_scale_update(float* loss_scale, int32_t* found_inf, int3
 }
 
 namespace {
+// m t + (1 - m) p with the one fusion the float4 body has always had written out: the same bits in the body and in the
+// scalar tail (see adamw_kernel)
+__device__ __forceinline__ float ema1(float m, float t, float p) {
+#pragma clang fp contract(off)
+    return fmaf(m, t, (1.f - m) * p);
+}
 __global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ t, const float* __restrict__ p, int64_t n, float m) {
     const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     for (int64_t i = t0; i < n4; i += stride) {
         float4 a = reinterpret_cast<float4*>(t)[i];
         const float4 b = reinterpret_cast<const float4*>(p)[i];
-        a.x = m * a.x + (1.f - m) * b.x; a.y = m * a.y + (1.f - m) * b.y;
-        a.z = m * a.z + (1.f - m) * b.z; a.w = m * a.w + (1.f - m) * b.w;
+        a.x = ema1(m, a.x, b.x); a.y = ema1(m, a.y, b.y);
+        a.z = ema1(m, a.z, b.z); a.w = ema1(m, a.w, b.w);
         reinterpret_cast<float4*>(t)[i] = a;
     }
-    for (int64_t i = (n4 << 2) + t0; i < n; i += stride) t[i] = m * t[i] + (1.f - m) * p[i];
+    for (int64_t i = (n4 << 2) + t0; i < n; i += stride) t[i] = ema1(m, t[i], p[i]);
 }
 }  // namespace
 

@@ -67,6 +67,12 @@ __device__ __forceinline__ void normalize_rows_body(const float* __restrict__ z,
     if (lane == 0) inv_norm[row] = inv;
 }
 
+// P_ij = exp(s_ij - lse_i), the softmax of row i over its candidates j != i.  With R = 2 the positive is the only candidate
+// and the softmax over one element is 1 by definition.  The exponential alone does not give that: the compiler folds the
+// logit's product into the subtraction (one FMA on the unrounded a / T), while lse_i was built from the rounded logit, so it
+// returns exp(+-half an ulp of the logit) -- dz was round-off noise times 1 / ||z|| where it is exactly 0.
+__device__ __forceinline__ float row_prob(float s, float lse, bool single) { return single ? 1.f : __expf(s - lse); }
+
 __device__ __forceinline__ int logit_col(int i, int j, int p) {
     // column of S[i][j] in the reference layout: positive first, then ascending j without {i, p}
     return j == p ? 0 : 1 + j - (j > i ? 1 : 0) - (j > p ? 1 : 0);
@@ -242,7 +248,7 @@ __global__ __launch_bounds__(256) void fused_bwd_kernel(const float* __restrict_
             float c = 0.f;
             if (j != i) {
                 const float pos = (j == p) ? 1.f : 0.f;  // p_j == i  <=>  j == p_i  (R even)
-                c = k * ((__expf(a - lse_i) - pos) + (__expf(a - lse[j]) - pos));
+                c = k * ((row_prob(a, lse_i, R == 2) - pos) + (row_prob(a, lse[j], R == 2) - pos));
             }
             coef[j] = c;
         }
@@ -499,7 +505,7 @@ __device__ __forceinline__ void ntxent_tile_body(const float* __restrict__ zn, c
                 float c = 0.f;
                 if (valid) {
                     const float pos = (j == p) ? 1.f : 0.f;  // p_j == i  <=>  j == p_i  (R even)
-                    c = k * ((__expf(s - lse_i) - pos) + (__expf(s - lse_t[jj + 32 * h]) - pos));
+                    c = k * ((row_prob(s, lse_i, R == 2) - pos) + (row_prob(s, lse_t[jj + 32 * h], R == 2) - pos));
                 }
                 coef[il * NTX_CP + jj + 32 * h] = c;
             } else if (valid) {
