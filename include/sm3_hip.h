@@ -854,6 +854,41 @@ int sm3_calib_counts(const int64_t* q, const uint8_t* ev, const int* order, cons
                      int64_t* sums, int N, int S, int X, int T, int M, int binning, uint64_t seed, int64_t r0, int c, int point,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Operating-point report: the integer counts behind average precision, the Youden and F1 optima, sensitivity at a specificity
+ * floor, specificity at a sensitivity floor and the counts at given thresholds, for the point estimate and for case-resampling
+ * bootstrap replicates (csrc/operating.hip, sm3hip/operating.py; ABI 9, additive).
+ * N cases, T labels, K columns; colmap, targets, order, gs, ge as sm3_report_counts (the same ranking).  With integer case
+ * multiplicities m[n] >= 0, sum m = N:
+ *   Ppre[j] / S[j] = sum of m over the positive / negative cases at sorted positions < j,  P = Ppre[N],  Q = S[N];
+ *   an operating point is a group start a (gs[a] == a: "positive iff score >= the group's value") or the empty point a = N;
+ *   TP(a) = P - Ppre[a], FP(a) = Q - S[a].  Groups whose cases all have m = 0 stay points: they repeat a neighbour's counts and
+ *   matter for the tie-breaks alone.
+ *   APN    = sum over groups [a, b) of dTP * precQ, dTP = Ppre[b] - Ppre[a], precQ = (TP * 2^32 + den / 2) / den in integer
+ *            division, den = TP + FP at a; a group with dTP = 0 contributes 0 and its quotient is never formed;
+ *   Youden = the point that maximises (TP * Q - FP * P, a);
+ *   F1     = the point that maximises 2 TP / (TP + FP + P), compared by cross-multiplication in int64, then a;
+ *   sens at spec floor sigma [Ls] int64 (floor(s0 * 2^32), 0 .. 2^32): among the points with (Q - FP) * 2^32 >= sigma * Q the
+ *            one that maximises (TP, -FP, a);
+ *   spec at sens floor rho [Lr] int64 (floor(r0 * 2^32)): among the points with TP * 2^32 >= rho * P the one that maximises
+ *            (-FP, TP, a);
+ *   fixed  = (TP(f), FP(f)) at the positions fixpos [K][Lt] int32 (0 .. N; the host's searchsorted of a threshold).
+ *   Each search is a maximum under a total order, so no reduction order shows.
+ * sm3_operating_counts: out [c][K][9 + 3 Ls + 3 Lr + 2 Lt] int64 = (P, Q, APN, Youden (TP, FP, a), F1 (TP, FP, a), Ls x (TP, FP,
+ *   a), Lr x (TP, FP, a), Lt x (TP, FP)) for replicates r = r0 .. r0 + c - 1, one workgroup per (replicate, label); a column whose
+ *   label is outside [0, T) is left unwritten.  point != 0: m = 1 everywhere, c must be 1, no random words.  Otherwise m_r is the
+ *   multiplicity vector of sm3_report_counts, exactly (Philox4x32-10, key = the seed, counter (d / 4, r, 0, 2), case (w * N) >>
+ *   32): with one seed, replicate r of the three reports resamples the same cases.  1 <= N <= sm3_report_max_cases(), 1 <= T
+ *   <= 64, 1 <= K <= 64, 0 <= Ls, Lr, Lt <= sm3_operating_max_levels() (32; a list of length 0 may be a null pointer), c >= 1,
+ *   0 <= r0, r0 + c <= 2^32; SM3_EINVAL otherwise, before anything is launched; out, sigma and rho 8-byte aligned (SM3_EALIGN).
+ *   Entries of order are clamped to N - 1, of gs / ge / fixpos to N and of sigma / rho to [0, 2^32]: no input can make an
+ *   access leave its array.  Integers only, no float anywhere: equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_operating_max_levels(void);
+int sm3_operating_counts(const int* order, const int* gs, const int* ge, const int* targets, const int* colmap, const int64_t* sigma,
+                         const int64_t* rho, const int* fixpos, int64_t* out, int N, int T, int K, int Ls, int Lr, int Lt,
+                         uint64_t seed, int64_t r0, int c, int point, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,8 @@ SIGNATURES = {
     "sm3_report_max_cases": [],
     "sm3_report_counts": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
     "sm3_calib_counts": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
+    "sm3_operating_max_levels": [],
+    "sm3_operating_counts": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
 }
 
 _lib = None

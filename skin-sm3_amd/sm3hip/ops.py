@@ -1528,6 +1528,50 @@ def calib_counts(q, ev, order, slabel, xq, bins, sums, labels, binning, seed, r0
                                            _stream()), "sm3_calib_counts")
 
 
+OPERATING_MAX_LEVELS = 32  # sm3_operating_max_levels(): entries of each of the two floor lists and of the fixed positions
+
+
+def operating_record(Ls, Lr, Lt):
+    """int64 entries of one (replicate, column) record of sm3_operating_counts."""
+    return 9 + 3 * (Ls + Lr) + 2 * Lt
+
+
+def operating_counts(order, gs, ge, targets, colmap, sigma, rho, fixpos, out, seed, r0, point=False):
+    """out [c, K, 9 + 3 Ls + 3 Lr + 2 Lt] int64 = (P, Q, APN, Youden (TP, FP, pos), F1 (TP, FP, pos), Ls x sens at a spec floor (TP,
+    FP, pos), Lr x spec at a sens floor (TP, FP, pos), Lt x (TP, FP) at a fixed position) of the K columns for bootstrap replicates
+    r0 .. r0 + c - 1, or for the point estimate (point: c = 1, every case once) (sm3_operating_counts).  order, gs, ge, targets,
+    colmap: as report_counts.  sigma [Ls], rho [Lr] int64 = floor(floor value * 2^32) in [0, 2^32]; fixpos [K, Lt] int32 in
+    [0, N]; each may be empty."""
+    for t, n in ((order, "order"), (gs, "gs"), (ge, "ge"), (targets, "targets"), (colmap, "colmap"), (fixpos, "fixpos")):
+        _chk(t, torch.int32, n)
+    for t, n in ((sigma, "sigma"), (rho, "rho"), (out, "out")):
+        _chk(t, torch.int64, n)
+    if order.dim() != 2 or targets.dim() != 2 or out.dim() != 3 or sigma.dim() != 1 or rho.dim() != 1 or fixpos.dim() != 2:
+        raise ValueError("operating_counts: order [K, N], targets [N, T], sigma [Ls], rho [Lr], fixpos [K, Lt] and out [c, K, R]")
+    K, N = order.shape
+    T = targets.shape[1]
+    c = out.shape[0]
+    Ls, Lr, Lt = sigma.shape[0], rho.shape[0], fixpos.shape[1]
+    if not 1 <= N <= REPORT_MAX_CASES:
+        raise ValueError(f"operating_counts: {N} cases, 1 to {REPORT_MAX_CASES} are supported")
+    if max(Ls, Lr, Lt) > OPERATING_MAX_LEVELS:
+        raise ValueError(f"operating_counts: {Ls} spec floors, {Lr} sens floors, {Lt} fixed positions, at most "
+                         f"{OPERATING_MAX_LEVELS} of each are supported")
+    if tuple(gs.shape) != (K, N) or tuple(ge.shape) != (K, N) or tuple(targets.shape) != (N, T) or tuple(colmap.shape) != (K, 2) or \
+            tuple(fixpos.shape) != (K, Lt) or tuple(out.shape) != (c, K, operating_record(Ls, Lr, Lt)):
+        raise ValueError("operating_counts: order, gs, ge [K, N], targets [N, T], colmap [K, 2], fixpos [K, Lt] and out [c, K, 9 + "
+                         "3 Ls + 3 Lr + 2 Lt] do not match")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("operating_counts: seed must fit 64 bits")
+    if point and c != 1:
+        raise ValueError("operating_counts: the point estimate is one table")
+    with _prof("operating_counts", 0.0, 4.0 * 3 * K * N * c):
+        check(_lib.load().sm3_operating_counts(_ptr(order), _ptr(gs), _ptr(ge), _ptr(targets), _ptr(colmap),
+                                               _ptr(sigma) if Ls else None, _ptr(rho) if Lr else None, _ptr(fixpos) if Lt else None,
+                                               _ptr(out), N, T, K, Ls, Lr, Lt, seed, int(r0), c, int(bool(point)), _stream()),
+              "sm3_operating_counts")
+
+
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):
     """Stem weight gradient with bn1's backward apply fused into the operand load (sm3_stem_wgrad_bn; bf16 / fp16 / exact f32).
     slabs: fp32 workspace of STEM_WGRAD_SLABS * 64 * 147 floats -> fixed-order sum instead of float atomics."""

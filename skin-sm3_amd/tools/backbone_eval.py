@@ -10,6 +10,9 @@ reference's Recall / Spec / Prec of the 8 labels (sm3hip.report).  The validatio
 and val_report.csv (the reference's table layout) to --log-path; --bootstrap B adds case-resampling intervals to them.
 --calibration adds val_calibration.json / .csv of the same pass at T = 1 (sm3hip.calibration: NLL, Brier, ECE, MCE, class-wise ECE and
 the reliability diagram; --calib-bins M, --calib-binning width|mass; the same bootstrap replicates).
+--operating adds val_operating.json / .csv of the same pass (sm3hip.operating: average precision, the Youden and F1 optima,
+sensitivity at --operating-spec floors, specificity at --operating-sens floors, net benefit at --operating-decision; the same
+bootstrap replicates).
 Any other value fine-tunes everything through the autograd bridge.
 
 `--data-name SevenPCBaseDataset --data-path DIR`: derm7pt's train and test splits decoded once into the device image store
@@ -32,7 +35,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from sm3hip import calibration, report  # noqa: E402
+from sm3hip import calibration, operating, report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.baseline import Baseline  # noqa: E402
 
@@ -51,6 +54,7 @@ def get_parser(calibration_flags=True):
     report.add_flags(p)
     if calibration_flags:
         calibration.add_flags(p)
+    operating.add_flags(p)
     p.set_defaults(arch="resnet50", epochs=50, batch_size=128)
     return p
 
@@ -127,6 +131,7 @@ def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
     calibration.check_flags(args)
+    operating.check_flags(args)
     from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
     require_baseline_arch(args.arch, "backbone_eval")
     real = require_data(args, "backbone_eval")
@@ -177,6 +182,9 @@ def main(argv=None):
         if args.calibration and epoch == args.epochs - 1:  # val_calibration.json / .csv next to val_report.*
             cal = calibration.validation_calibration(va["preds"], va["targets"], args, args.log_path)
             print(f"epoch {epoch}: val {calibration.stats_line(cal)}", flush=True)
+        if args.operating and epoch == args.epochs - 1:  # val_operating.json / .csv next to val_report.*
+            opr = operating.validation_operating(va["preds"], va["targets"], args, args.log_path)
+            print(f"epoch {epoch}: val {operating.stats_line(opr)}", flush=True)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG (backbone_eval.py:386,405-411)
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},

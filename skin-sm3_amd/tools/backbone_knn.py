@@ -12,7 +12,7 @@ frozen and in eval mode (one fused conv + BN + ReLU kernel per layer); a case's 
 become fractions p = votes / sum(votes); AUC_AVG is sm3hip.metrics.auc_avg of log p (softmax(log p) = p) and top-1 is the
 first of the stable descending order, as KNNOnlineEvaluator.predict ranks.  knn_predictions.pt goes to --log-path, and with it
 val_report.json / val_report.csv: Recall / Spec / Prec and every class's AUROC of the same log p (sm3hip.report; --bootstrap B
-adds case-resampling intervals).
+adds case-resampling intervals); --operating adds val_operating.json / .csv of the same log p (sm3hip.operating).
 `--data-name synthetic`: --steps-per-epoch batches form the bank, --val-steps batches the queries; --random-features N B D
 replaces the encoders by N bank and B query rows of unit-norm random features of width D (the kNN stage alone, at bank sizes
 no encoder pass in a test reaches).
@@ -32,7 +32,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import backbone_eval  # noqa: E402
-from sm3hip import report  # noqa: E402
+from sm3hip import operating, report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.baseline import Baseline  # noqa: E402
 
@@ -68,6 +68,7 @@ def random_features(n, d, dev, gen):
 def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
+    operating.check_flags(args)
     from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
     require_baseline_arch(args.arch, "backbone_knn")
     real = require_data(args, "backbone_knn")
@@ -135,6 +136,9 @@ def main(argv=None):
           + " ".join(f"{n} {a:.3f}" for n, a in zip(CLASSES_NAME, top1))
           + f" | bank {bank.N} queries {query_f.shape[0]} | {stat['pairs_per_s']:.0f} pairs/s", flush=True)
     print(f"knn k={args.knn_k} T={args.knn_t}: {report.stats_line(stat, rep)}", flush=True)
+    if args.operating:  # val_operating.json / .csv next to val_report.*
+        opr = operating.validation_operating([p.log() for p in probs], query_t, args, args.log_path)
+        print(f"knn k={args.knn_k} T={args.knn_t}: {operating.stats_line(opr)}", flush=True)
     return stat
 
 

@@ -20,6 +20,15 @@ reliability diagram; --calib-bins M, --calib-binning width|mass) with the SAME b
 example the validation split's predictions, and reports PRED.pt both at T = 1 and at the fitted temperatures
 (<name>_calibration_fitted.json / .csv), with the paired difference fitted - unscaled and its interval
 (<name>_calibration_compare.json).
+
+    python tools/eval_report.py logs/linear/test_predictions.pt --bootstrap 2000 --operating --operating-rule "spec>=0.9" \
+        --fit-on logs/linear/val_predictions.pt
+
+--operating adds the operating-point report (sm3hip/operating.py: average precision, the Youden and F1 optima, sensitivity at
+--operating-spec floors, specificity at --operating-sens floors, net benefit at --operating-decision) with the SAME bootstrap
+replicates, written to <name>_operating.json / .csv, and with --against the paired difference (<name>_operating_compare.json).
+With --fit-on OTHER.pt the thresholds that --operating-rule (youden, f1, spec>=X, sens>=X) picks on OTHER.pt are applied to
+PRED.pt: sens / spec / PPV / NPV at the transferred thresholds with their intervals (<name>_operating_fitted.json / .csv).
 """
 import argparse
 import json
@@ -34,7 +43,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 
 import torch  # noqa: E402
 
-from sm3hip import calibration, report  # noqa: E402
+from sm3hip import calibration, operating, report  # noqa: E402
 
 
 def get_parser():
@@ -45,6 +54,7 @@ def get_parser():
     p.add_argument("--chunk", type=int, default=None, help="bootstrap replicates per launch (any value gives the same bits)")
     report.add_flags(p)
     calibration.add_flags(p)
+    operating.add_flags(p)
     p.add_argument("--fit-on", metavar="OTHER.pt", default=None,
                    help="fit the temperatures on this predictions file; report PRED.pt at T = 1 and at the fitted T (implies --calibration)")
     return p
@@ -94,9 +104,38 @@ def calibrate(args, preds, targets, kw, out, stem, dev):
     return result
 
 
+def operate(args, preds, targets, kw, out, stem, dev):
+    """The --operating part: prints the tables, writes the files, returns what it computed."""
+    if targets.shape[0] > report.MAX_CASES:
+        print(operating.stats_line(None), flush=True)
+        return {}
+    okw = dict(kw, **operating.flag_settings(args))
+    opr = operating.operating_report(preds, targets, **okw)
+    print(operating.format_table(opr), flush=True)
+    operating.save(opr, out, stem + "_operating")
+    result = {"operating": opr}
+    if args.against:
+        cmp = operating.compare(opr, operating.operating_report(*report.load_predictions(args.against, dev), **okw))
+        print(f"{args.pred} - {args.against}", flush=True)
+        print(operating.format_compare(cmp), flush=True)
+        _dump(cmp, os.path.join(out, stem + "_operating_compare.json"))
+        result["operating_compare"] = cmp
+    if args.fit_on:
+        thr = operating.fit_thresholds(*report.load_predictions(args.fit_on, dev), args.operating_rule)
+        print(f"thresholds fitted on {args.fit_on} by {args.operating_rule}: " + " ".join(
+            f"{n} {float(v):.4f}" for n, v in zip(report.CLASS_COLUMNS, thr)), flush=True)
+        fitted = operating.operating_report(preds, targets, thresholds=thr, **okw)
+        fitted.update({"rule": args.operating_rule, "fit_on": args.fit_on})
+        print(operating.format_table(fitted), flush=True)
+        operating.save(fitted, out, stem + "_operating_fitted")
+        result.update({"operating_thresholds": thr, "operating_fitted": fitted})
+    return result
+
+
 def main(argv=None):
     args = get_parser().parse_args(argv)
     calibration.check_flags(args)
+    operating.check_flags(args)
     out = args.out or os.path.dirname(os.path.abspath(args.pred))
     stem = os.path.splitext(os.path.basename(args.pred))[0]
     kw = dict(bootstrap=args.bootstrap, confidence=args.confidence, seed=args.bootstrap_seed, chunk=args.chunk)
@@ -118,6 +157,8 @@ def main(argv=None):
         result.update({"other": other, "compare": cmp})
     if args.calibration or args.fit_on:
         result.update(calibrate(args, preds, targets, kw, out, stem, dev))
+    if args.operating:
+        result.update(operate(args, preds, targets, kw, out, stem, dev))
     return result
 
 
