@@ -260,6 +260,11 @@ __global__ __launch_bounds__(256) void mlc_ce_kernel(const float* __restrict__ l
     const float k = 1.f / ((float)B * (float)H);
     double a = 0.0;
     for (int i = threadIdx.x; i < B * H; i += 256) {
+        // No contraction in this block: every scaled logit x * inv_t is rounded once, and the subtractions below take that
+        // value.  Folded into an FMA, x * inv_t - m and lse - x_t * inv_t see the unrounded product, half an ulp of the
+        // scaled logit away from the m and the lse built from the rounded one: a class that leads by more than exp()
+        // resolves (its probability is 1) then gets a term of either sign and a gradient p - 1 that is round-off noise.
+#pragma clang fp contract(off)
         const int b = i / H, h = i - b * H;
         const int c0 = off[h], c1 = off[h + 1];
         const float* row = logits + (int64_t)b * Tn;
@@ -267,11 +272,14 @@ __global__ __launch_bounds__(256) void mlc_ce_kernel(const float* __restrict__ l
         for (int c = c0; c < c1; ++c) m = fmaxf(m, row[c] * inv_t);
         float se = 0.f;
         for (int c = c0; c < c1; ++c) se += __expf(row[c] * inv_t - m);
-        const float lse = m + __logf(se);
+        const bool one = c1 - c0 == 1;  // a head of one class: its softmax is 1 by definition, loss term and gradient 0
+        const float lse = one ? m : m + __logf(se);
         const int t = (int)targets[(int64_t)h * B + b];
         a += (double)(k * (lse - row[c0 + t] * inv_t));
-        for (int c = c0; c < c1; ++c)
-            dlogits[(int64_t)b * Tn + c] = k * inv_t * (__expf(row[c] * inv_t - lse) - (c == c0 + t ? 1.f : 0.f));
+        for (int c = c0; c < c1; ++c) {
+            const float pr = one ? 1.f : __expf(row[c] * inv_t - lse);
+            dlogits[(int64_t)b * Tn + c] = k * inv_t * (pr - (c == c0 + t ? 1.f : 0.f));
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
