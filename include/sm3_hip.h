@@ -889,6 +889,37 @@ int sm3_operating_counts(const int* order, const int* gs, const int* ge, const i
                          const int64_t* rho, const int* fixpos, int64_t* out, int N, int T, int K, int Ls, int Lr, int Lt,
                          uint64_t seed, int64_t r0, int c, int point, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Cross-modal retrieval report: what lies between S = query . gallery^T and Recall@k, mean / median rank and MRR, for the point
+ * estimate and for case-resampling bootstrap replicates (csrc/retrieval.hip, sm3hip/retrieval.py; ABI 9, additive).
+ * N cases; row i of the queries and row i of the gallery belong to case i.  For j != i, b[i][j] = 1 iff S[i][j] > S[i][i], or
+ * S[i][j] == S[i][i] and j < i (the lower index wins a tie, as in sm3_knn_vote); b[i][i] = 0.  Packed: bits [N][W] uint32,
+ * W = ceil(N / 32), bit j & 31 of word j >> 5; the bits of j >= N are 0.  With integer case multiplicities m[n] >= 0, sum m = N:
+ *   rho_i = sum_j m_j b[i][j]  (0-based rank; copies of case i in the gallery are its positive, not competitors),
+ *   H_l = sum_i m_i [rho_i < k_l],  R = sum_i m_i rho_i,  Q = sum_i m_i floor(2^32 / (rho_i + 1)),
+ *   M   = the least rho with 2 sum_i m_i [rho_i <= rho] >= N  (the lower weighted median).
+ * sm3_retrieval_beats: for the n query rows q0 .. q0 + n - 1, whose similarities are the rows of S [n][ld] f32 (row r is query
+ *   q0 + r, its positive is column q0 + r; columns N .. ld - 1 are not read): bits [n][W], rank [n] int32 = rho with m = 1, and
+ *   term [n] f64 = log sum_{j < N} exp(S[r][j] / tau) - S[r][q0 + r] / tau, S widened to f64 before the division, the row maximum
+ *   subtracted inside the exponential, the sum taken lane-strided in ascending j and folded by one shuffle tree: an order that
+ *   depends on N alone.  One wave per row, the row is read once.  S must be finite (the caller checks).  1 <= N <=
+ *   sm3_report_max_cases(), n >= 1, 0 <= q0, q0 + n <= N, ld >= N, 0 < tau < inf; SM3_EINVAL otherwise, before anything is
+ *   launched; term 8-byte, the others 4-byte aligned (SM3_EALIGN).
+ * sm3_retrieval_counts: out [c][L + 3] int64 = (H_1 .. H_L, R, Q, M) for replicates r = r0 .. r0 + c - 1, one workgroup per
+ *   replicate.  ks [L] int32 is HOST memory (copied into the launch), 1 <= L <= 8, 1 <= k <= sm3_report_max_cases().  point != 0:
+ *   m = 1 everywhere, c must be 1, no random words.  Otherwise m_r is the multiplicity vector of sm3_report_counts, exactly
+ *   (Philox4x32-10, key = the seed, counter (d / 4, r, 0, 2), case (w * N) >> 32): with one seed, replicate r of the four reports
+ *   resamples the same cases.  m is split into bit-planes M_p [W] in LDS (bit j of plane p = bit p of m_j), P = the bits of
+ *   max m, and rho_i = sum_w sum_p 2^p popcount(bits[i][w] & M_p[w]); the planes are 0 past N, so whatever the padding bits of
+ *   `bits` hold, rho <= N and no access leaves its array.  1 <= N <= sm3_report_max_cases(), c >= 1, 0 <= r0, r0 + c <= 2^32;
+ *   SM3_EINVAL otherwise, before anything is launched; out 8-byte, bits 4-byte aligned (SM3_EALIGN).  Integers only, no float
+ *   anywhere: a replicate is a function of (seed, r, N, bits) alone.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_retrieval_beats(const float* S, int64_t ld, int n, int q0, int N, double tau, uint32_t* bits, int32_t* rank, double* term,
+                        void* stream);
+int sm3_retrieval_counts(const uint32_t* bits, int N, const int32_t* ks, int L, int64_t* out, uint64_t seed, int64_t r0, int c,
+                         int point, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

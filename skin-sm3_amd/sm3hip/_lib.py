@@ -187,6 +187,8 @@ SIGNATURES = {
     "sm3_calib_counts": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
     "sm3_operating_max_levels": [],
     "sm3_operating_counts": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
+    "sm3_retrieval_beats": [_P, _L, _I, _I, _I, _D, _P, _P, _P, _P],
+    "sm3_retrieval_counts": [_P, _I, _P, _I, _P, C.c_uint64, _L, _I, _I, _P],
 }
 
 _lib = None

@@ -1492,6 +1492,58 @@ def report_counts(order, gs, ge, targets, yhat, colmap, out, seed, r0, point=Fal
                                             N, T, K, seed, int(r0), c, int(bool(point)), _stream()), "sm3_report_counts")
 
 
+RETRIEVAL_MAX_LEVELS = 8  # Recall@k levels of one sm3_retrieval_counts record
+
+
+def retrieval_beats(S, q0, N, temperature, bits, rank, term):
+    """For the query rows q0 .. q0 + n - 1, whose similarities to the N gallery rows are S [n, ld >= N] float32 (the positive of row
+    r is column q0 + r): bits [n, ceil(N / 32)] int32 = the packed "gallery row j comes back before the positive" flags (equal
+    similarities: the lower index first), rank [n] int32 = their number, term [n] float64 = log sum_j exp(S_rj / T) - S_rr / T
+    (sm3_retrieval_beats)."""
+    _chk(S, torch.float32, "S"); _chk(bits, torch.int32, "bits"); _chk(rank, torch.int32, "rank"); _chk(term, torch.float64, "term")
+    if S.dim() != 2 or bits.dim() != 2 or rank.dim() != 1 or term.dim() != 1:
+        raise ValueError("retrieval_beats: S [n, ld], bits [n, W], rank [n] and term [n]")
+    n, ld = S.shape
+    if not 1 <= N <= REPORT_MAX_CASES:
+        raise ValueError(f"retrieval_beats: {N} cases, 1 to {REPORT_MAX_CASES} are supported")
+    W = (N + 31) // 32
+    if n < 1 or ld < N or tuple(bits.shape) != (n, W) or tuple(rank.shape) != (n,) or tuple(term.shape) != (n,):
+        raise ValueError(f"retrieval_beats: S [n, ld >= {N}], bits [n, {W}], rank [n] and term [n] do not match")
+    if not 0 <= q0 <= N - n:
+        raise ValueError(f"retrieval_beats: rows {q0} .. {q0 + n - 1} are not among the {N} cases")
+    if not 0 < temperature < float("inf"):
+        raise ValueError("retrieval_beats: the temperature must be positive and finite")
+    with _prof("retrieval_beats", 0.0, 4.0 * n * N + 4.0 * n * W):
+        check(_lib.load().sm3_retrieval_beats(_ptr(S), ld, n, int(q0), int(N), float(temperature), _ptr(bits), _ptr(rank), _ptr(term),
+                                              _stream()), "sm3_retrieval_beats")
+
+
+def retrieval_counts(bits, ks, out, seed, r0, point=False):
+    """out [c, L + 3] int64 = (H_1 .. H_L, R, Q, M) of the packed flags bits [N, ceil(N / 32)] int32 for bootstrap replicates r0 ..
+    r0 + c - 1, or for the point estimate (point: c = 1, every case once) (sm3_retrieval_counts).  ks: the L Recall@k levels, a
+    sequence of integers in [1, REPORT_MAX_CASES], L <= RETRIEVAL_MAX_LEVELS."""
+    _chk(bits, torch.int32, "bits"); _chk(out, torch.int64, "out")
+    if bits.dim() != 2 or out.dim() != 2:
+        raise ValueError("retrieval_counts: bits [N, W] and out [c, L + 3]")
+    N, c = bits.shape[0], out.shape[0]
+    ks = list(ks)
+    L = len(ks)
+    if not 1 <= N <= REPORT_MAX_CASES:
+        raise ValueError(f"retrieval_counts: {N} cases, 1 to {REPORT_MAX_CASES} are supported")
+    if not 1 <= L <= RETRIEVAL_MAX_LEVELS or not all(isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= REPORT_MAX_CASES
+                                                     for k in ks):
+        raise ValueError(f"retrieval_counts: 1 to {RETRIEVAL_MAX_LEVELS} integer levels in [1, {REPORT_MAX_CASES}], got {ks!r}")
+    if bits.shape[1] != (N + 31) // 32 or c < 1 or tuple(out.shape) != (c, L + 3):
+        raise ValueError(f"retrieval_counts: bits [N, {(N + 31) // 32}] and out [c, {L + 3}] do not match")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("retrieval_counts: seed must fit 64 bits")
+    if point and c != 1:
+        raise ValueError("retrieval_counts: the point estimate is one record")
+    with _prof("retrieval_counts", 0.0, 4.0 * bits.numel() * c):
+        check(_lib.load().sm3_retrieval_counts(_ptr(bits), N, (C.c_int32 * L)(*ks), L, _ptr(out), seed, int(r0), c, int(bool(point)),
+                                               _stream()), "sm3_retrieval_counts")
+
+
 CALIB_MAX_BINS = 64
 CALIB_BINNINGS = ("width", "mass")
 

@@ -65,6 +65,9 @@ def get_parser():
                    help="synthetic uint8 source images + the reference's augmentation chain on the GPU instead of "
                         "ready-made normalised tensors")
     p.add_argument("--engine", default="fused", choices=["fused", "compat"])
+    p.add_argument("--retrieval-freq", default=0, type=int,
+                   help="every E epochs (0: never) rank 0 prints the label-free cross-modal retrieval report of held-out pairs")
+    p.add_argument("--retrieval-cases", default=256, type=int, help="synthetic data only: held-out pairs of that report")
     p.set_defaults(arch="resnet50", port=29533)
     return p
 
@@ -92,9 +95,56 @@ def synthetic_batch(bs, size, device, gen, kind="noise"):
     return [view(base), view(base)], [view(other), view(other)]
 
 
+def held_out_pairs(args, real, store, dev, bs):
+    """The held-out (derm, clinic) batches of --retrieval-freq: the split backbone_eval validates on through its validation
+    chain, or --retrieval-cases synthetic latent pairs (first views) from a generator of their own, seeded seed + 2000 -- the
+    training stream's generators are not advanced."""
+    if real:
+        from sm3hip.augment import chain
+        from src.utils.data.sampler import eval_batches
+        split = store.splits["test"]
+        aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
+        for sel in eval_batches(len(split), bs):
+            yield (store.augment(aug, split.derm_ids[sel], None, whole=True)[0],
+                   store.augment(aug, split.clinic_ids[sel], None, whole=True)[0])
+        return
+    gen = torch.Generator(device=dev).manual_seed(args.seed + 2000)
+    for n0 in range(0, args.retrieval_cases, bs):
+        derm, clinic = synthetic_batch(min(bs, args.retrieval_cases - n0), args.img_sz, dev, gen, "latent")
+        yield derm[0], clinic[0]
+
+
+def retrieval_line(model, pairs, epoch):
+    """`Retrieval epoch: [e] derm->clinic R@1 .. R@5 .. median .. | clinic->derm .. | loss ..` of the model in eval mode."""
+    from sm3hip import retrieval
+    zd, zc = [], []
+    for derm, clinic in pairs:
+        a, b = retrieval.embed(model, derm, clinic)
+        zd.append(a)
+        zc.append(b)
+    rep = retrieval.cross_modal_report(torch.cat(zd), torch.cat(zc), ks=(1, 5))
+    parts = []
+    for d in rep["directions"]:
+        v = rep[d]["values"]
+        parts.append(f"{d} R@1 {float(v[0]):.4f} R@5 {float(v[1]):.4f} median {int(v[3])}")
+    loss = 0.5 * (rep["derm->clinic"]["loss"] + rep["clinic->derm"]["loss"])
+    return f"Retrieval epoch: [{epoch}] " + " | ".join(parts) + f" | loss {loss:.4f}"
+
+
 def main(local_rank, args):
     from src.utils.misc import require_data
     real = require_data(args, "backbone_train")
+    retrieval_freq = getattr(args, "retrieval_freq", 0)  # a caller's own namespace may predate the flag
+    if retrieval_freq:  # refused here, before the device is touched and before any epoch is trained
+        from sm3hip.ops import REPORT_MAX_CASES
+        if real:
+            from src.utils.data.datasets import read_split
+            held_out = len(read_split(args.data_path, "test")[2])
+        else:
+            held_out = args.retrieval_cases
+        if retrieval_freq < 0 or not 1 <= held_out <= REPORT_MAX_CASES:
+            raise SystemExit(f"backbone_train: --retrieval-freq must be >= 0 and the retrieval report takes 1 to {REPORT_MAX_CASES} "
+                             f"held-out cases, got {held_out}")
     world = args.world_size
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
@@ -143,7 +193,7 @@ def main(local_rank, args):
         from sm3hip.augment import chain
         from sm3hip.imagestore import build_for
         from src.utils.data.sampler import train_batches
-        store = build_for(args, ["train"], dev)
+        store = build_for(args, ["train", "test"] if retrieval_freq else ["train"], dev)
         train = store.splits["train"]
         augment = chain("backbone_train", tuple(args.img_sz), args.mean, args.std)
         aug_gen = torch.Generator().manual_seed(args.seed + 1000 + local_rank)
@@ -195,6 +245,10 @@ def main(local_rank, args):
             torch.save(state, path)
             if (epoch + 1) % args.save_freq == 0:
                 torch.save(state, os.path.join(args.log_path, f"ckp_{epoch + 1}.pth"))
+            if retrieval_freq and (epoch + 1) % retrieval_freq == 0:
+                model.eval()
+                print(retrieval_line(model, held_out_pairs(args, real, store, dev, bs), epoch), flush=True)
+                model.train()
     if world > 1:
         dist.destroy_process_group()
     return history
