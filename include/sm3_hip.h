@@ -292,6 +292,8 @@ int sm3_linbn_moments(const float* slabs, int nslabs, int64_t n, float* out, con
 int sm3_linbn_fwd_stats(int dtype, const float* G, const void* w_dgrad, const void* w_fwd, const double* s, float* Tm,
                         double* sums_ws, int C, int p, int views, void* stream);
 /* reduce_ws / groups: what sm3_bn_stats_reduce(partials of (dz, .), sums = NULL) left -- its stage B runs here.
+ * reduce_ws is [views][groups][2C] fp64 and only the first C entries of a row (the sums of dz) are read: the second
+ * half may hold anything.  No alignment of C or p is required.
  * lsums: [views][2C] fp64, both halves written (sum dz | sum dz xhat); dgamma += sum dz xhat, dbeta += sum dz (NULL to
  * skip).  count > 0 (single rank: the local sums are the global ones): coef is written too; count <= 0: the caller
  * all-reduces lsums and calls sm3_linbn_coef.  P: [views][C][p] fp32; w_fwd: dtype [C][p]. */
@@ -301,7 +303,7 @@ int sm3_linbn_stats(int dtype, const float* P, const void* w_fwd, const float* m
 int sm3_linbn_coef(const double* global_sums, double count, const float* gamma, const float* mean, const float* invstd,
                    float* coef, int C, int views, void* stream);
 /* wa = diag(a) W and wbn = -diag(b) W in data-gradient order (dtype [views][p][C], from w_dgrad [p][C]);
- * col_const [views][p] = (b mu - a m1) W, summed over the rounded products. */
+ * col_const [views][p] = (b mu - a m1) W, summed over the rounded products.  C a multiple of 8; any p. */
 int sm3_linbn_banks(int dtype, const void* w_dgrad, const float* coef, void* wa, void* wbn, float* col_const, int C, int p,
                     int views, void* stream);
 /* out[v][e] = sum over the `groups` partial rows of sums_ws [views][groups][n] (n = 2C), fixed order: what a data-parallel
@@ -309,7 +311,7 @@ int sm3_linbn_banks(int dtype, const void* w_dgrad, const float* coef, void* wa,
 int sm3_linbn_fold(const double* sums_ws, int groups, int n, int views, double* out, void* stream);
 /* out3[v][c][:] = scale3[v][c] w3[c][:] ([C][K3] banks), outd[v][c][:] = scaled[v][c] wd[c][:] ([C][Kd]), and
  * bias[v][c] = shift3[v][c] + shiftd[v][c]: what sm3_conv_seg_act needs to run conv3 + bn3 + downsample conv + its BatchNorm
- * + add + ReLU as one two-segment GEMM. */
+ * + add + ReLU as one two-segment GEMM.  K3, Kd multiples of 8; any C.  Both banks are rounded once from the fp32 product. */
 int sm3_linbn_scale_banks(int dtype, const void* w3, int K3, const float* scale3, const float* shift3, void* out3,
                           const void* wd, int Kd, const float* scaled, const float* shiftd, void* outd, float* bias, int C,
                           int views, void* stream);

@@ -1,6 +1,7 @@
 """What the explanation modules (cam.py, attr.py, faith.py) share: the two kinds of model they take -- the linear probe
 (src/models/baseline.py `Baseline`) and the SM3 multi-label model (inference.py `Model`) -- their input checks, target classes,
 logits and head gradients, the baseline images, and the measurement of what a forward's saved records hold."""
+import gc
 from itertools import accumulate
 
 import torch
@@ -138,6 +139,16 @@ def expand_baseline(b, x):
 def forward_measured(eng, x):
     """(features, device bytes per image that the saved records took) of one eval forward of x that keeps the records; they
     are dropped on return.  For the chunk planners."""
-    before = torch.cuda.memory_allocated(x.device)
-    f, ctx = eng.encoder_only("main", x, False, True)
-    return f, (torch.cuda.memory_allocated(x.device) - before) // x.shape[0]
+    # The figure is a difference of the allocator's counter, so nothing else may be released inside the window: unreachable
+    # cycles that still hold device tensors (engines and models of earlier calls) go first, and the collector stays off
+    # until the second reading -- collected in the middle of the forward they made the difference negative.
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        before = torch.cuda.memory_allocated(x.device)
+        f, ctx = eng.encoder_only("main", x, False, True)
+        return f, (torch.cuda.memory_allocated(x.device) - before) // x.shape[0]
+    finally:
+        if was_on:
+            gc.enable()

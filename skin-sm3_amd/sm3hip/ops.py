@@ -780,6 +780,8 @@ def linbn_banks(dtype, w_dgrad, coef, wa, wbn, col_const, Cn, p, views=1):
     if w_dgrad.numel() != p * Cn or wa.numel() < views * p * Cn or wbn.numel() < views * p * Cn or \
             col_const.numel() < views * p or coef.numel() < views * 4 * Cn:
         raise ValueError("linbn_banks: size mismatch")
+    if Cn % 8:
+        raise ValueError(f"linbn_banks: C = {Cn} is not a multiple of 8 (the rows are walked in 16-byte vectors)")
     with _prof(_lin_tag("linbn_banks", Cn, p), 0.0, _sz(dtype) * p * Cn * (1 + 2 * views)):
         check(_lib.load().sm3_linbn_banks(dtype, _ptr(w_dgrad), _ptr(coef), _ptr(wa), _ptr(wbn), _ptr(col_const), Cn, p,
                                           views, _stream()), "sm3_linbn_banks")

@@ -49,6 +49,27 @@ def need_repr(t, dt, what):
     assert torch.equal(t.to(dt).double(), t), f"{what}: not representable in {dt}"
 
 
+def need_f32(t, what):
+    """Every element of the fp64 tensor t is an fp32 value: the fp32 operation that produces it is exact."""
+    assert bool(torch.isfinite(t).all()) and torch.equal(t.float().double(), t), f"{what}: not exact in fp32"
+
+
+def need_exact64(abs_sum, q, what):
+    """need_exact for an fp64 accumulation: below 2^53 quanta."""
+    worst = float(abs_sum.max()) / q if abs_sum.numel() else 0.0
+    assert worst < 2.0 ** 53, f"{what}: worst-case partial sum is {worst:.0f} quanta (>= 2^53): not exact in fp64"
+
+
+def stored(v, dt):
+    """What a store of the fp64 value v in dt holds (one rounding, nearest even), as fp64."""
+    return v.to(dt).double()
+
+
+def pick(gen, vals, shape):
+    """Elements of the 1-D tensor vals drawn uniformly."""
+    return vals[torch.randint(0, len(vals), shape, generator=gen)]
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # GPU helpers
 # ------------------------------------------------------------------------------------------------------------------------

@@ -403,6 +403,40 @@ def test_chunk_planner():
             plan_chunk(**{**dict(steps=4, n=1, image_bytes=1, free_bytes=1), **bad})
 
 
+def test_forward_measured_leaves_the_cycle_collector_as_it_found_it(monkeypatch):
+    """The records' size is a difference of the allocator's counter taken with the collector off; it comes back on (or stays
+    off) as the caller had it, also when the forward raises."""
+    import gc
+    from sm3hip.explain import forward_measured
+    readings = iter([1000, 1000 + 2 * 4096, 0, 0, 0])
+    monkeypatch.setattr(torch.cuda, "memory_allocated", lambda dev=None: next(readings))
+
+    class Eng:
+        def __init__(self, fail=False):
+            self.fail = fail
+
+        def encoder_only(self, lane, x, train, keep):
+            assert not gc.isenabled()
+            if self.fail:
+                raise RuntimeError("forward failed")
+            return x * 2, object()
+
+    x = torch.ones(2, 3)
+    was_on = gc.isenabled()
+    try:
+        gc.enable()
+        f, per_image = forward_measured(Eng(), x)
+        assert gc.isenabled() and per_image == 4096 and torch.equal(f, x * 2)
+        with pytest.raises(RuntimeError):
+            forward_measured(Eng(fail=True), x)
+        assert gc.isenabled()
+        gc.disable()
+        forward_measured(Eng(), x)
+        assert not gc.isenabled()
+    finally:
+        gc.enable() if was_on else gc.disable()
+
+
 def test_drivers_refuse_train_mode_cpu_tensors_and_bad_arguments():
     from sm3hip.attr import integrated_gradients, smooth_grad
     from src.models.baseline import Baseline
