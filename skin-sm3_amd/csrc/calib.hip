@@ -12,34 +12,23 @@
 //     plain sum x:   sum over n of m[n] * xq[x][n].
 //
 //   sm3_calib_counts: bins[j][s][b] = (n_b, E_b, Q_b), sums[j][x], int64, for replicate r = r0 + j.  One workgroup per
-//                     (replicate, label): it builds m_r ONCE in LDS, exactly as sm3_report_counts does (the same Philox stream,
-//                     so replicate r resamples the same cases in both reports), and serves every series whose label it is and
+//                     (replicate, label): it builds m_r ONCE in LDS by resample_multiplicities (resample.h: the resampling
+//                     rule, so replicate r resamples the same cases in every report), and serves every series whose label it is and
 //                     every plain sum x with x % T == label: 3 to 6 series and 2 sums for derm7pt, and the point table (one
 //                     replicate) still fills 8 CUs.  Both binnings walk the series in sorted order, 4 consecutive positions per
 //                     thread, where the bin index never decreases: a thread adds up a run of equal bins in registers and
 //                     spends two 64-bit LDS atomics per run (n_b and E_b share one word, 32 bits each), not three per case.
-//                     The mass binning needs R_j: a workgroup prefix scan of m along the order (tiles of kTile positions, wave
-//                     scan by shuffles, wave totals through LDS, one barrier per tile), consumed in the same pass.
+//                     The mass binning needs R_j: a workgroup prefix scan of m along the order (tile_scan), consumed in the
+//                     same pass.
 // Every sum is an integer: no order shows, no float exists.  A replicate is a function of (seed, r, N) alone.
-#include "exact_f32.h"
+#include "resample.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPer = 4;                    // sorted positions per thread and tile
-constexpr int kTile = kThreads * kPer;     // 1024
-constexpr int kMaxCases = 8192;            // sm3_report_max_cases(): m of a replicate is 32 KiB of LDS
 constexpr int kMaxSeries = 64;
 constexpr int kMaxSums = 64;
 constexpr int kMaxLabels = 64;
 constexpr int kMaxBins = 64;
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // grid (c, T); q [S][N]; ev [S][N]; order [S][N]; slabel [S]; xq [X][N]; bins [c][S][M][3]; sums [c][X]
 __global__ void __launch_bounds__(kThreads) calib_counts_kernel(const long long* __restrict__ q, const uint8_t* __restrict__ ev,
@@ -54,18 +43,7 @@ __global__ void __launch_bounds__(kThreads) calib_counts_kernel(const long long*
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t r = r0 + blockIdx.x;
 
-    for (int i = tid; i < N; i += kThreads) mult[i] = point ? 1u : 0u;
-    __syncthreads();
-    if (!point) {
-        for (int d = tid; 4 * d < N; d += kThreads) {
-            uint32_t w[4];
-            philox4x32_10((uint32_t)d, r, 0u, 2u, key0, key1, w);
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                if (4 * d + l < N) atomicAdd(&mult[(uint32_t)(((uint64_t)w[l] * (uint32_t)N) >> 32)], 1u);
-        }
-        __syncthreads();
-    }
+    resample_multiplicities(mult, N, key0, key1, r, point);
 
     const int t = blockIdx.y;
     for (int s = 0; s < S; ++s) {
@@ -89,25 +67,7 @@ __global__ void __launch_bounds__(kThreads) calib_counts_kernel(const long long*
                 tot += mv[e];
             }
             int rank = 0;  // R of the thread's first position (mass binning)
-            if (mass) {    // the same for the whole grid
-                int incl = tot;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int u = __shfl_up(incl, o, 64);
-                    if (lane >= o) incl += u;
-                }
-                if (lane == 63) wsum[it & 1][wave] = incl;
-                __syncthreads();
-                int before = carry, total = 0;
-#pragma unroll
-                for (int w = 0; w < kWaves; ++w) {
-                    const int ws = wsum[it & 1][w];
-                    before += w < wave ? ws : 0;
-                    total += ws;
-                }
-                rank = before + incl - tot;
-                carry += total;
-            }
+            if (mass) rank = tile_scan(tot, carry, wsum, it);  // the same for the whole grid
             int cur = -1;  // the run of equal bins held in registers
             unsigned long long ne = 0ull, qsum = 0ull;
 #pragma unroll
@@ -160,7 +120,7 @@ __global__ void __launch_bounds__(kThreads) calib_counts_kernel(const long long*
         const long long* xs = xq + (int64_t)x * N;
         long long a = 0;
         for (int i = tid; i < N; i += kThreads) a += (long long)mult[i] * xs[i];
-        a = wave_sum_i64(a);
+        a = wave_sum(a);
         if (lane == 0) red[wave] = a;
         __syncthreads();
         if (tid == 0) {
@@ -178,9 +138,9 @@ extern "C" int sm3_calib_counts(const int64_t* q, const uint8_t* ev, const int* 
                                 int64_t* bins, int64_t* sums, int N, int S, int X, int T, int M, int binning, uint64_t seed,
                                 int64_t r0, int c, int point, void* stream) {
     if (!q || !ev || !order || !slabel || !xq || !bins || !sums) return SM3_EINVAL;
-    if (N < 1 || N > kMaxCases || S < 1 || S > kMaxSeries || X < 1 || X > kMaxSums || T < 1 || T > kMaxLabels) return SM3_EINVAL;
-    if (M < 1 || M > kMaxBins || (binning != 0 && binning != 1) || c < 1) return SM3_EINVAL;
-    if (r0 < 0 || r0 + (int64_t)c > ((int64_t)1 << 32) || (point && c != 1)) return SM3_EINVAL;
+    if (!resample_args_ok(N, r0, c, point) || S < 1 || S > kMaxSeries || X < 1 || X > kMaxSums || T < 1 || T > kMaxLabels)
+        return SM3_EINVAL;
+    if (M < 1 || M > kMaxBins || (binning != 0 && binning != 1)) return SM3_EINVAL;
     if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(xq) | reinterpret_cast<uintptr_t>(bins) |
          reinterpret_cast<uintptr_t>(sums)) & 7)
         return SM3_EALIGN;

@@ -20,23 +20,19 @@
 //
 //   sm3_operating_counts: out[j][k] = [P, Q, APN, youden (TP, FP, a), f1 (TP, FP, a), Ls x (TP, FP, a), Lr x (TP, FP, a),
 //                      Lt x (TP, FP)] int64 for replicate r = r0 + j.  One workgroup per (replicate, label), as
-//                      report_counts_kernel: m_r in LDS from Philox (the same draws), the label's y packed beside it.  Per
-//                      column ONE workgroup prefix scan along order gives both sums: S <= 8192 in the low and Ppre <= 8192 in the
-//                      high half of one 32-bit word (neither half can carry), so the LDS budget is report.hip's.  Then passes
+//                      report_counts_kernel: m_r in LDS by resample_multiplicities (resample.h: the resampling rule), the
+//                      label's y packed beside it.  Per column ONE workgroup prefix scan along order (tile_scan) gives both
+//                      sums: S <= 8192 in the low and Ppre <= 8192 in the high half of one 32-bit word (neither half can
+//                      carry), so the LDS budget is report.hip's (two 32-bit arrays of kMaxCases: 64 KiB + 4).  Then passes
 //                      over the group starts: pass 0 takes APN, Youden, F1 and the first kLv levels of both floor lists, every
 //                      later pass kLv more levels of each (the default of three levels each is one pass).  Every search is the
 //                      maximum of a TOTAL order -- the integer searches of one packed int64 key whose lowest field is the
 //                      position -- so wave shuffles and the sum across waves give the same answer in any order.
 // Every value is an integer: no order shows, no float exists.  A replicate is a function of (seed, r, N) alone.
-#include "exact_f32.h"
+#include "resample.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPer = 4;                    // sorted positions per thread and tile
-constexpr int kTile = kThreads * kPer;     // 1024
-constexpr int kMaxCases = 8192;            // two 32-bit arrays of N in LDS: 64 KiB + 4 of the 160 KiB; 8192 fits 16 bits
 constexpr int kMaxColumns = 64;
 constexpr int kMaxLabels = 64;
 constexpr int kMaxLevels = 32;
@@ -53,11 +49,6 @@ __device__ __forceinline__ bool f1_less(long long a, long long b) {
     return l != r ? l < r : (a & 0xffff) < (b & 0xffff);
 }
 
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ long long wave_max_i64(long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -96,18 +87,7 @@ __global__ void __launch_bounds__(kThreads) operating_counts_kernel(const int* _
     const uint32_t r = r0 + blockIdx.x;
     const int rec = 9 + 3 * (Ls + Lr) + 2 * Lt;
 
-    for (int i = tid; i < N; i += kThreads) word[i] = point ? 1u : 0u;
-    __syncthreads();
-    if (!point) {
-        for (int q = tid; 4 * q < N; q += kThreads) {
-            uint32_t w[4];
-            philox4x32_10((uint32_t)q, r, 0u, 2u, key0, key1, w);
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                if (4 * q + l < N) atomicAdd(&word[(uint32_t)(((uint64_t)w[l] * (uint32_t)N) >> 32)], 1u);
-        }
-        __syncthreads();
-    }
+    resample_multiplicities(word, N, key0, key1, r, point);
 
     const int t = blockIdx.y;
     for (int i = tid; i < N; i += kThreads) word[i] = (word[i] & 0xffffu) | (((uint32_t)y[(int64_t)i * T + t] & 0xffu) << 16);
@@ -136,28 +116,12 @@ __global__ void __launch_bounds__(kThreads) operating_counts_kernel(const int* _
                 }
                 s += v[e];
             }
-            uint32_t incl = s;  // inclusive scan of the threads' sums over the wave
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t u = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += u;
-            }
-            if (lane == 63) wsum[it & 1][wave] = incl;
-            __syncthreads();
-            uint32_t before = carry, total = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) {
-                const uint32_t ws = wsum[it & 1][w];
-                before += w < wave ? ws : 0;
-                total += ws;
-            }
-            uint32_t run = before + incl - s;
+            uint32_t run = tile_scan(s, carry, wsum, it);
 #pragma unroll
             for (int e = 0; e < kPer; ++e) {
                 if (j0 + e < N) PS[j0 + e] = run;
                 run += v[e];
             }
-            carry += total;
         }
         if (tid == 0) PS[N] = carry;
         __syncthreads();
@@ -206,7 +170,7 @@ __global__ void __launch_bounds__(kThreads) operating_counts_kernel(const int* _
                 }
             }
             if (pass == 0) {
-                apn = wave_sum_i64(apn), by = wave_max_i64(by), bf = wave_max_f1(bf);
+                apn = wave_sum(apn), by = wave_max_i64(by), bf = wave_max_f1(bf);
                 if (lane == 0) red[wave][0] = apn, red[wave][1] = by, red[wave][2] = bf;
             }
 #pragma unroll
@@ -262,10 +226,9 @@ extern "C" int sm3_operating_counts(const int* order, const int* gs, const int* 
                                     const int64_t* sigma, const int64_t* rho, const int* fixpos, int64_t* out, int N, int T, int K,
                                     int Ls, int Lr, int Lt, uint64_t seed, int64_t r0, int c, int point, void* stream) {
     if (!order || !gs || !ge || !targets || !colmap || !out) return SM3_EINVAL;
-    if (N < 1 || N > kMaxCases || T < 1 || T > kMaxLabels || K < 1 || K > kMaxColumns || c < 1) return SM3_EINVAL;
+    if (!resample_args_ok(N, r0, c, point) || T < 1 || T > kMaxLabels || K < 1 || K > kMaxColumns) return SM3_EINVAL;
     if (Ls < 0 || Ls > kMaxLevels || Lr < 0 || Lr > kMaxLevels || Lt < 0 || Lt > kMaxLevels) return SM3_EINVAL;
     if ((Ls && !sigma) || (Lr && !rho) || (Lt && !fixpos)) return SM3_EINVAL;
-    if (r0 < 0 || r0 + (int64_t)c > ((int64_t)1 << 32) || (point && c != 1)) return SM3_EINVAL;
     if ((reinterpret_cast<uintptr_t>(out) & 7) || (reinterpret_cast<uintptr_t>(sigma) & 7) || (reinterpret_cast<uintptr_t>(rho) & 7))
         return SM3_EALIGN;
     hipLaunchKernelGGL(operating_counts_kernel, dim3((uint32_t)c, (uint32_t)T), dim3(kThreads), 0, (hipStream_t)stream, order, gs, ge,

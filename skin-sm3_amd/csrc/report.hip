@@ -11,37 +11,19 @@
 //
 //   sm3_report_counts: out[j][k] = (A2, P, Q, TP, FP, FN) int64 for replicate r = r0 + j.  One workgroup per (replicate, label):
 //                      the columns of a label share y and yhat, and the point estimate (one replicate) still fills 8 CUs.  m_r
-//                      is built in LDS: draw d < N hits case (w * N) >> 32, w = word d % 4 of Philox4x32-10 with key = the
-//                      64-bit seed (low word first) and counter (d / 4, r, 0, 2), counted by integer LDS atomics (the 8
-//                      workgroups of a replicate each count the same draws: N / 4 Philox calls beside N gathers per column);
-//                      `point`: m = 1, no random words.  The LDS word of a case then takes y and yhat of the label beside m
-//                      (m in the low 16 bits, a byte each), so a column costs ONE LDS gather per sorted position.  Per
-//                      column: a workgroup prefix scan of the negatives' multiplicities into S (tiles of kTile positions, 4
-//                      per thread, wave scan by shuffles, one barrier per tile; P, TP and FP fall out of the same pass, since
-//                      the ranking visits every case once), then a pass over the positives for A2.
+//                      is built in LDS by resample_multiplicities (resample.h: the resampling rule; the 8 workgroups of a
+//                      replicate each count the same draws: N / 4 Philox calls beside N gathers per column).  The LDS word
+//                      of a case then takes y and yhat of the label beside m (m in the low 16 bits, a byte each), so a
+//                      column costs ONE LDS gather per sorted position.  Per column: a workgroup prefix scan of the
+//                      negatives' multiplicities into S (tile_scan; P, TP and FP fall out of the same pass, since the
+//                      ranking visits every case once), then a pass over the positives for A2.
 // Every sum is an integer: no order shows, no float exists.  A replicate is a function of (seed, r, N) alone.
-#include "exact_f32.h"
+#include "resample.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPer = 4;                    // sorted positions per thread and tile
-constexpr int kTile = kThreads * kPer;     // 1024
-constexpr int kMaxCases = 8192;            // two int32 arrays of N in LDS: 64 KiB + 4 of the 160 KiB
-constexpr int kMaxColumns = 64;
+constexpr int kMaxColumns = 64;            // word and S: two int32 arrays of kMaxCases in LDS, 64 KiB + 4 of the 160 KiB
 constexpr int kMaxLabels = 64;
-
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // grid (c, T); order, gs, ge [K][N]; y, yhat [N][T]; colmap [K][2] = (label, class); out [c][K][6]
 __global__ void __launch_bounds__(kThreads) report_counts_kernel(const int* __restrict__ order, const int* __restrict__ gs,
@@ -56,18 +38,7 @@ __global__ void __launch_bounds__(kThreads) report_counts_kernel(const int* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t r = r0 + blockIdx.x;
 
-    for (int i = tid; i < N; i += kThreads) word[i] = point ? 1u : 0u;
-    __syncthreads();
-    if (!point) {
-        for (int q = tid; 4 * q < N; q += kThreads) {
-            uint32_t w[4];
-            philox4x32_10((uint32_t)q, r, 0u, 2u, key0, key1, w);
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                if (4 * q + l < N) atomicAdd(&word[(uint32_t)(((uint64_t)w[l] * (uint32_t)N) >> 32)], 1u);
-        }
-        __syncthreads();
-    }
+    resample_multiplicities(word, N, key0, key1, r, point);
 
     const int t = blockIdx.y;
     for (int i = tid; i < N; i += kThreads)
@@ -97,28 +68,12 @@ __global__ void __launch_bounds__(kThreads) report_counts_kernel(const int* __re
                 }
                 s += v[e];
             }
-            int incl = s;  // inclusive scan of the threads' sums over the wave
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int u = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += u;
-            }
-            if (lane == 63) wsum[it & 1][wave] = incl;
-            __syncthreads();
-            int before = carry, total = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) {
-                const int ws = wsum[it & 1][w];
-                before += w < wave ? ws : 0;
-                total += ws;
-            }
-            int run = before + incl - s;
+            int run = tile_scan(s, carry, wsum, it);
 #pragma unroll
             for (int e = 0; e < kPer; ++e) {
                 if (j0 + e < N) S[j0 + e] = run;
                 run += v[e];
             }
-            carry += total;
         }
         if (tid == 0) S[N] = carry;
         __syncthreads();
@@ -132,8 +87,7 @@ __global__ void __launch_bounds__(kThreads) report_counts_kernel(const int* __re
                 a2 += (long long)m * (S[lo] + S[hi]);
             }
         }
-        a2 = wave_sum_i64(a2);
-        p = wave_sum_i32(p), tp = wave_sum_i32(tp), fp = wave_sum_i32(fp);
+        a2 = wave_sum(a2), p = wave_sum(p), tp = wave_sum(tp), fp = wave_sum(fp);
         if (lane == 0) red[wave][0] = a2, red[wave][1] = p, red[wave][2] = tp, red[wave][3] = fp;
         __syncthreads();  // also: every read of S is done before the next column writes it
         if (tid == 0) {
@@ -155,8 +109,7 @@ extern "C" int sm3_report_counts(const int* order, const int* gs, const int* ge,
                                  const int* colmap, int64_t* out, int N, int T, int K, uint64_t seed, int64_t r0, int c, int point,
                                  void* stream) {
     if (!order || !gs || !ge || !targets || !yhat || !colmap || !out) return SM3_EINVAL;
-    if (N < 1 || N > kMaxCases || T < 1 || T > kMaxLabels || K < 1 || K > kMaxColumns || c < 1) return SM3_EINVAL;
-    if (r0 < 0 || r0 + (int64_t)c > ((int64_t)1 << 32) || (point && c != 1)) return SM3_EINVAL;
+    if (!resample_args_ok(N, r0, c, point) || T < 1 || T > kMaxLabels || K < 1 || K > kMaxColumns) return SM3_EINVAL;
     if (reinterpret_cast<uintptr_t>(out) & 7) return SM3_EALIGN;
     hipLaunchKernelGGL(report_counts_kernel, dim3((uint32_t)c, (uint32_t)T), dim3(kThreads), 0, (hipStream_t)stream, order, gs, ge, targets,
                        yhat, colmap, reinterpret_cast<long long*>(out), N, T, K, (uint32_t)seed, (uint32_t)(seed >> 32),

@@ -14,8 +14,8 @@
 //                         along.  The InfoNCE term log sum_j exp(S_ij / tau) - S_ii / tau is fp64: lane l adds
 //                         exp((S_ij - max) / tau) of j = l, l + 64, ... in ascending j (an order that depends on N alone),
 //                         then one xor butterfly.
-//   sm3_retrieval_counts: one workgroup per replicate.  m_r is built in LDS exactly as report_counts_kernel builds it (Philox,
-//                         integer LDS atomics), then split into bit-planes M_p [W] (bit j of plane p = bit p of m_j; __ballot
+//   sm3_retrieval_counts: one workgroup per replicate.  m_r is built in LDS by resample_multiplicities (resample.h: the
+//                         resampling rule), then split into bit-planes M_p [W] (bit j of plane p = bit p of m_j; __ballot
 //                         again), P = the bits of max m, so that
 //                             rho_i = sum_w sum_p 2^p popcount(bits[i][w] & M_p[w])
 //                         costs W * P popcounts per row where a per-bit loop costs N multiply-adds.  A wave takes a row
@@ -23,17 +23,15 @@
 //                         the lanes fold by shuffles.  This is the simplest mapping and it is UNMEASURED: for small W (the
 //                         13 words of 395 cases) most lanes of the wave idle, and sub-wave groups per row may do better.
 //                         H, R, Q are integer wave / workgroup sums; M comes from an integer LDS histogram of the ranks
-//                         (N + 1 bins) and one workgroup scan.  No float exists in this kernel: a replicate is a function
+//                         (N + 1 bins) and one workgroup scan (one shot through wred: resample.h's tile_scan would need a
+//                         second row of wave totals in LDS).  No float exists in this kernel: a replicate is a function
 //                         of (seed, r, N, bits) alone.
-#include "exact_f32.h"
+#include "resample.h"
 
 namespace {
 
-constexpr int kMaxCases = 8192;  // sm3_report_max_cases()
 constexpr int kMaxWords = kMaxCases / 32;
 constexpr int kMaxLevels = 8;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kMaxPlanes = 14;   // m <= N <= 2^13
 
 // ---- beats --------------------------------------------------------------------------------------------------------------
@@ -76,17 +74,6 @@ struct Levels {
     int k[kMaxLevels];
 };
 
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // grid c; bits [N][W]; out [c][L + 3].  One wave per row, kWaves rows in flight.
 __global__ void __launch_bounds__(kThreads) retrieval_counts_kernel(const uint32_t* __restrict__ bits, long long* __restrict__ out,
                                                                     int N, Levels ks, int L, uint32_t key0, uint32_t key1,
@@ -99,19 +86,9 @@ __global__ void __launch_bounds__(kThreads) retrieval_counts_kernel(const uint32
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = (N + 31) >> 5;
     const uint32_t r = r0 + blockIdx.x;
 
-    for (int i = tid; i < N; i += kThreads) m[i] = point ? 1u : 0u;
-    for (int i = tid; i <= N; i += kThreads) hist[i] = 0;
-    __syncthreads();
-    if (!point) {
-        for (int q = tid; 4 * q < N; q += kThreads) {
-            uint32_t w[4];
-            philox4x32_10((uint32_t)q, r, 0u, 2u, key0, key1, w);
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                if (4 * q + l < N) atomicAdd(&m[(uint32_t)(((uint64_t)w[l] * (uint32_t)N) >> 32)], 1u);
-        }
-        __syncthreads();
-    }
+    resample_multiplicities(m, N, key0, key1, r, point, [&] {
+        for (int i = tid; i <= N; i += kThreads) hist[i] = 0;
+    });
 
     // P = the bits of max m (m <= N < 2^14), then the planes: 64 cases a wave step, one ballot per plane
     uint32_t mmax = 0;
@@ -150,7 +127,7 @@ __global__ void __launch_bounds__(kThreads) retrieval_counts_kernel(const uint32
                 for (int p = 0; p < P; ++p) rho += __popc(x & plane[p][w]) << p;
             }
         }
-        rho = wave_sum_i32(rho);
+        rho = wave_sum(rho);
         if (mi && lane == 0) {
             rho = min(rho, N);  // planes are 0 past N, so this holds already: the bin index cannot leave hist whatever bits holds
 #pragma unroll
@@ -161,8 +138,8 @@ __global__ void __launch_bounds__(kThreads) retrieval_counts_kernel(const uint32
         }
     }
 #pragma unroll
-    for (int l = 0; l < kMaxLevels; ++l) h[l] = wave_sum_i32(h[l]);
-    R = wave_sum_i64(R), Q = wave_sum_i64(Q);
+    for (int l = 0; l < kMaxLevels; ++l) h[l] = wave_sum(h[l]);
+    R = wave_sum(R), Q = wave_sum(Q);
     if (lane == 0) {
 #pragma unroll
         for (int l = 0; l < kMaxLevels; ++l) red[wave][l] = h[l];
@@ -221,8 +198,7 @@ extern "C" int sm3_retrieval_beats(const float* S, int64_t ld, int n, int q0, in
 extern "C" int sm3_retrieval_counts(const uint32_t* bits, int N, const int32_t* ks, int L, int64_t* out, uint64_t seed, int64_t r0,
                                     int c, int point, void* stream) {
     if (!bits || !ks || !out) return SM3_EINVAL;
-    if (N < 1 || N > kMaxCases || L < 1 || L > kMaxLevels || c < 1) return SM3_EINVAL;
-    if (r0 < 0 || r0 + (int64_t)c > ((int64_t)1 << 32) || (point && c != 1)) return SM3_EINVAL;
+    if (!resample_args_ok(N, r0, c, point) || L < 1 || L > kMaxLevels) return SM3_EINVAL;
     Levels lv;
     for (int l = 0; l < kMaxLevels; ++l) {
         lv.k[l] = l < L ? ks[l] : 0;

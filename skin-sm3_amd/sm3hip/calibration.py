@@ -15,8 +15,7 @@ positive floats (default all 1); 1 <= N <= report.MAX_CASES.
         q_br[n, t]  = sum over c of (p[n, c] - [y == c])^2, added one class at a time in ascending class index.
   * a series is a pair (q [N] int64, e [N] 0/1).  S = 32 series: s = 0 .. 7 the top-label series of the labels, s = 8 + k the
     class-wise series of column k.  X = 16 plain sums: x = t is q_nll, x = 8 + t is q_br of label t.
-  * multiplicities: integers m[n] >= 0, sum m = N.  The point estimate has m = 1.  Replicate r has the draws of
-    sm3_report_counts, exactly: Philox4x32-10, key = the 64-bit seed, counter (d / 4, r, 0, 2), word d % 4, case (w * N) >> 32.
+  * multiplicities: integers m[n] >= 0, sum m = N; the point estimate has m = 1, replicate r the m_r of resample.py's rule.
     With one seed, replicate r here resamples the same cases as replicate r of evaluation_report: the intervals of
     discrimination and calibration are joint, and comparisons are paired.
   * bins: M of them, 1 <= M <= MAX_BINS = 64, default 15.
@@ -37,19 +36,17 @@ positive floats (default all 1); 1 <= N <= report.MAX_CASES.
   * tables: label_values [4, 9], rows NLL, Brier, ECE, MCE of the top-label series, columns the 8 labels and "AVG" (summed in
     ascending label order, then ONE division by 8); class_values [1, 29], the class-wise ECE of the 24 columns and the five
     averages of report.AVERAGES (report.averages); diagram [32, M, 3] = (n_b, acc_b, conf_b).
-  * intervals and undefined: report.interval / report.interval_index, unchanged.  No table value has a zero denominator (N >=
+  * intervals and undefined: resample.interval, unchanged.  No table value has a zero denominator (N >=
     1); a bin with n_b = 0 in a replicate makes that replicate undefined for that bin's acc_b / conf_b only (their value is 0).
 
 The bin tables and sums come from sm3_calib_counts (csrc/calib.hip): one workgroup per replicate and label, integers only, so
 equal inputs give equal bits.  fit_temperature is a function of its inputs alone and runs on the host."""
-import json
 import math
-import os
 
 import numpy as np
 import torch
 
-from . import ops, report
+from . import ops, report, resample
 from .metrics import CLASSES_NAME, NUM_CLASSES
 
 MAX_BINS = ops.CALIB_MAX_BINS
@@ -71,7 +68,7 @@ HALVINGS = 60
 
 
 def check_bins(bins, binning, who="calibration_report"):
-    if not report._is_int(bins) or not 1 <= bins <= MAX_BINS:
+    if not resample.is_int(bins) or not 1 <= bins <= MAX_BINS:
         raise ValueError(f"{who}: bins must be an integer in [1, {MAX_BINS}], got {bins!r}")
     if binning not in BINNINGS:
         raise ValueError(f"{who}: binning must be one of {BINNINGS}, got {binning!r}")
@@ -118,12 +115,7 @@ def fixed_point(preds, targets, temperature=None):
 
 
 def _div(num, den):
-    """num / den in fp64, 0 where den == 0: ONE division of two integers."""
-    num, den = np.asarray(num).astype(np.float64), np.asarray(den).astype(np.float64)
-    num, den = np.broadcast_arrays(num, den)
-    out = np.zeros(num.shape, dtype=np.float64)
-    np.divide(num, den, out=out, where=den != 0)
-    return out
+    return resample.safe_div(num, den)[0]
 
 
 def values_from_counts(bins, sums, N):
@@ -172,26 +164,16 @@ def calibration_report(preds, targets, temperature=None, bins=DEFAULT_BINS, binn
     check_bins(bins, binning, who)
     temperature = check_temperature(temperature, who)
     N = report.check_inputs(preds, targets, who)
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{who}: needs a GPU (the SM3 HIP path has no CPU fallback)")
-    dev = preds[0].device if preds[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = resample.device_for(preds, who)
     B, M = bootstrap, bins
     with torch.no_grad(), torch.cuda.device(dev), ops.stream_scope():
         q, ev, xq = fixed_point([p.detach().to(dev) for p in preds], targets.to(dev), temperature)
         order = torch.sort(q, dim=1, stable=True).indices.int().contiguous()
         slabel = torch.tensor(SERIES_LABEL, dtype=torch.int32, device=dev)
-        pb = torch.empty((1, S, M, 3), dtype=torch.int64, device=dev)
-        ps = torch.empty((1, X), dtype=torch.int64, device=dev)
-        ops.calib_counts(q, ev, order, slabel, xq, pb, ps, T, binning, seed, 0, point=True)
-        if B:
-            c = min(B, DEFAULT_CHUNK) if chunk is None else chunk
-            rb = torch.empty((B, S, M, 3), dtype=torch.int64, device=dev)
-            rs = torch.empty((B, X), dtype=torch.int64, device=dev)
-            for r0 in range(0, B, c):
-                e = r0 + min(c, B - r0)
-                ops.calib_counts(q, ev, order, slabel, xq, rb[r0:e], rs[r0:e], T, binning, seed, r0)
-            rb, rs = rb.cpu().numpy(), rs.cpu().numpy()
-        pb, ps = pb[0].cpu().numpy(), ps[0].cpu().numpy()
+        (pb, ps), (rb, rs) = resample.replicate_tables(
+            lambda outs, seed, r0, point: ops.calib_counts(q, ev, order, slabel, xq, outs[0], outs[1], T, binning, seed, r0,
+                                                           point=point),
+            [(S, M, 3), (X,)], B, seed, chunk, DEFAULT_CHUNK, dev)
     v = values_from_counts(pb, ps, N)
     out = {"bins": torch.from_numpy(pb), "sums": torch.from_numpy(ps), "label_values": torch.from_numpy(v["label_values"]),
            "class_values": torch.from_numpy(v["class_values"]), "diagram": torch.from_numpy(v["diagram"]),
@@ -200,12 +182,9 @@ def calibration_report(preds, targets, temperature=None, bins=DEFAULT_BINS, binn
            "binning": binning, "targets": targets.detach().cpu().clone(), "n": N}
     if B:
         rv = values_from_counts(rb, rs, N)
-        for name, key in (("label", "label_values"), ("class", "class_values"), ("diagram", "diagram")):
-            lo, hi = report.interval(rv[key], confidence)
-            und = rv["diagram_undefined"].sum(axis=0) if name == "diagram" else np.zeros(lo.shape)
-            out.update({f"{name}_replicates": torch.from_numpy(rv[key]), f"{name}_lo": torch.from_numpy(lo.copy()),
-                        f"{name}_hi": torch.from_numpy(hi.copy()), f"{name}_undefined": torch.from_numpy(und.astype(np.int64))})
-        out.update({"bootstrap": B, "seed": seed, "confidence": float(confidence)})
+        resample.pack_intervals(out, [("label_", rv["label_values"], np.zeros(rv["label_values"].shape[1:])),
+                                      ("class_", rv["class_values"], np.zeros(rv["class_values"].shape[1:])),
+                                      ("diagram_", rv["diagram"], rv["diagram_undefined"].sum(axis=0))], B, seed, confidence)
     return out
 
 
@@ -257,32 +236,12 @@ def compare(a, b):
     {"label_delta" [4, 9], "class_delta" [1, 29] = a - b, the metric and column names} and, with a bootstrap, x_lo, x_hi by the
     interval rule on the replicates' differences and x_frac_le_zero = the fraction of replicates with a difference <= 0, for x
     in "label", "class", and "bootstrap", "seed", "confidence"."""
-    for r in (a, b):
-        if not isinstance(r, dict) or "label_values" not in r or "targets" not in r:
-            raise ValueError("compare: two dicts from calibration_report are needed")
-    if tuple(a["targets"].shape) != tuple(b["targets"].shape) or not bool(torch.equal(a["targets"], b["targets"])):
-        raise ValueError("compare: the two reports must be of the same cases (equal targets)")
-    if a.get("n_bins") != b.get("n_bins"):
-        raise ValueError(f"compare: bins differ ({a.get('n_bins')} and {b.get('n_bins')})")
-    if a.get("binning") != b.get("binning"):
-        raise ValueError(f"compare: binning differs ({a.get('binning')} and {b.get('binning')})")
-    if a.get("bootstrap", 0) != b.get("bootstrap", 0):
-        raise ValueError(f"compare: bootstrap differs ({a.get('bootstrap', 0)} and {b.get('bootstrap', 0)})")
-    if a.get("seed") != b.get("seed"):
-        raise ValueError(f"compare: seed differs ({a.get('seed')} and {b.get('seed')}): the replicates would not be paired")
-    if a.get("confidence") != b.get("confidence"):
-        raise ValueError(f"compare: confidence differs ({a.get('confidence')} and {b.get('confidence')})")
+    resample.check_paired(a, b, "calibration_report", ("label_values", "targets"),
+                          (("n_bins", "bins differ ({} and {})"), ("binning", "binning differs ({} and {})")))
     out = {"label_delta": a["label_values"] - b["label_values"], "class_delta": a["class_values"] - b["class_values"],
            "label_metrics": list(LABEL_METRICS), "label_columns": list(LABEL_COLUMNS), "class_metrics": list(CLASS_METRICS),
            "class_columns": list(CLASS_COLUMNS)}
-    if a.get("bootstrap", 0):
-        for name in ("label", "class"):
-            d = (a[f"{name}_replicates"] - b[f"{name}_replicates"]).numpy()
-            lo, hi = report.interval(d, a["confidence"])
-            out.update({f"{name}_lo": torch.from_numpy(lo.copy()), f"{name}_hi": torch.from_numpy(hi.copy()),
-                        f"{name}_frac_le_zero": torch.from_numpy((d <= 0).sum(axis=0) / float(d.shape[0]))})
-        out.update({"bootstrap": a["bootstrap"], "seed": a["seed"], "confidence": a["confidence"]})
-    return out
+    return resample.paired_intervals(out, a, b, ("label_", "class_"))
 
 
 def _tables(rep):
@@ -316,21 +275,12 @@ def csv_rows(rep):
 
 def to_csv(rep, path):
     """The long format of csv_rows with a header; repr of the fp64 values: they parse back exactly."""
-    with open(path, "w") as f:
-        f.write("table,row,column,value" + (",lo,hi,undefined" if "label_lo" in rep else "") + "\n")
-        for row in csv_rows(rep):
-            f.write(",".join(repr(v) if isinstance(v, float) else str(v) for v in row) + "\n")
+    resample.write_long_csv(path, "table,row,column,value" + (",lo,hi,undefined" if "label_lo" in rep else ""), csv_rows(rep))
 
 
 def to_json(rep, path):
     """Everything but the replicates and the targets, as lists (json writes repr of a float: the values parse back exactly)."""
-    out = {}
-    for k, v in rep.items():
-        if k.endswith("_replicates") or k == "targets":
-            continue
-        out[k] = v.tolist() if isinstance(v, torch.Tensor) else v
-    with open(path, "w") as f:
-        json.dump(out, f, indent=1)
+    resample.write_json(rep, path, ("label_replicates", "class_replicates", "diagram_replicates", "targets"))
 
 
 def format_table(rep):
@@ -379,9 +329,7 @@ def check_flags(args):
 
 def save(rep, log_path, stem="val_calibration"):
     """<stem>.json and <stem>.csv under log_path."""
-    os.makedirs(log_path, exist_ok=True)
-    to_json(rep, os.path.join(log_path, stem + ".json"))
-    to_csv(rep, os.path.join(log_path, stem + ".csv"))
+    resample.save(rep, log_path, stem, to_json, to_csv)
 
 
 def stats_line(rep):

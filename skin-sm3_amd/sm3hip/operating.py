@@ -11,8 +11,7 @@ one-past-last sorted position of position j's group.
 
   * operating points of a column: one per tie group g with sorted positions [a_g, b_g), "positive iff score >= the group's
     value", named by pos = a_g, and the empty point (pos = N, threshold +inf, TP = FP = 0).
-  * multiplicities: integers m[n] >= 0, sum m = N.  The point estimate has m = 1.  Replicate r has the draws of
-    sm3_report_counts, exactly: Philox4x32-10, key = the 64-bit seed, counter (d / 4, r, 0, 2), word d % 4, case (w * N) >> 32.
+  * multiplicities: integers m[n] >= 0, sum m = N; the point estimate has m = 1, replicate r the m_r of resample.py's rule.
     With one seed, replicate r here resamples the same cases as replicate r of evaluation_report and calibration_report: the
     intervals of the three reports are joint, and comparisons are paired.
   * counts, all int64: Ppre[j] / S[j] = the sum of m over the positive / negative cases at positions < j; P = Ppre[N], Q = S[N];
@@ -44,7 +43,7 @@ one-past-last sorted position of position j's group.
         w = pt / (1 - pt),  NB = (TP - FP * w) / N,  NB_all = (P - Q * w) / N.
   * rows of the value table: "AP"; "<point> <metric>" for the points "youden", "f1", "spec>=<s0>", "sens>=<r0>" and the fixed
     ones ("pt=<pt>" or "thr[i]") and the six metrics; "NB pt=<pt>" and "NB_all pt=<pt>".  Columns: the 24 classes and the five
-    averages of report.averages.  Intervals and undefined counts by report.interval / interval_index, unchanged; an average
+    averages of report.averages.  Intervals and undefined counts by resample.interval, unchanged; an average
     is undefined in the replicates in which any contributing column is.
   * curves (point estimate): per column the ROC and PR point lists at every operating point in ascending pos (descending
     threshold last): fpr = FP / Q, tpr = recall = TP / P, precision = TP / (TP + FP), thresholds -- from the integer cumulative
@@ -52,14 +51,13 @@ one-past-last sorted position of position j's group.
 
 The counts come from sm3_operating_counts (csrc/operating.hip): one workgroup per replicate and label, integers only, so equal
 inputs give equal bits whatever the chunk.  len(spec_floors), len(sens_floors), Lt <= MAX_LEVELS; floors lie in [0, 1]."""
-import json
 import math
-import os
 
 import numpy as np
 import torch
 
-from . import ops, report
+from . import ops, report, resample
+from .resample import safe_div as _div
 
 MAX_LEVELS = ops.OPERATING_MAX_LEVELS
 ONE = 1 << 32                       # 1.0 in Q32
@@ -146,14 +144,6 @@ def row_names(points, decision):
             + [f"{kind} pt={pt!r}" for pt in decision for kind in ("NB", "NB_all")])
 
 
-def _div(num, den):
-    """(num / den in fp64, 0 where den == 0; den == 0): ONE division of two exactly represented integers."""
-    num, den = np.asarray(num).astype(np.float64), np.asarray(den).astype(np.float64)
-    out = np.zeros(num.shape, dtype=np.float64)
-    np.divide(num, den, out=out, where=den != 0)
-    return out, den == 0
-
-
 def values_from_counts(counts, Ls, Lr, Lt, decision, N):
     """counts [..., 24, 9 + 3 Ls + 3 Lr + 2 Lt] int64 -> (values [..., rows, 29] fp64, undefined [..., rows, 29] bool), rows as
     row_names; decision: the threshold probabilities of the Lt fixed points, or () when those are the caller's thresholds."""
@@ -225,9 +215,7 @@ def operating_report(preds, targets, spec_floors=DEFAULT_SPEC, sens_floors=DEFAU
     spec_floors, sens_floors, decision = check_levels(spec_floors, sens_floors, decision, who)
     thresholds = check_thresholds(thresholds, who)
     report.check_inputs(preds, targets, who)
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{who}: needs a GPU (the SM3 HIP path has no CPU fallback)")
-    dev = preds[0].device if preds[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = resample.device_for(preds, who)
     with torch.cuda.device(dev), ops.stream_scope():
         return _report(preds, targets, spec_floors, sens_floors, decision, thresholds, bootstrap, confidence, seed, chunk, dev,
                        ops.operating_counts)
@@ -253,15 +241,9 @@ def _report(preds, targets, spec_floors, sens_floors, decision, thresholds, boot
         sigma = torch.tensor([q32_floor(s) for s in spec_floors], dtype=torch.int64, device=dev)
         rho = torch.tensor([q32_floor(r) for r in sens_floors], dtype=torch.int64, device=dev)
         R = ops.operating_record(Ls, Lr, Lt)
-        point = torch.empty((1, K, R), dtype=torch.int64, device=dev)
-        counts_fn(order, gs, ge, y, colmap, sigma, rho, fixpos, point, seed, 0, point=True)
-        if B:
-            c = min(B, DEFAULT_CHUNK) if chunk is None else chunk
-            reps = torch.empty((B, K, R), dtype=torch.int64, device=dev)
-            for r0 in range(0, B, c):
-                counts_fn(order, gs, ge, y, colmap, sigma, rho, fixpos, reps[r0:r0 + min(c, B - r0)], seed, r0)
-            reps = reps.cpu().numpy()
-        point = point[0].cpu().numpy()
+        (point,), (reps,) = resample.replicate_tables(
+            lambda outs, seed, r0, point: counts_fn(order, gs, ge, y, colmap, sigma, rho, fixpos, outs[0], seed, r0, point=point),
+            [(K, R)], B, seed, chunk, DEFAULT_CHUNK, dev)
         ss, fixed = sorted_scores.cpu().numpy(), fixed.cpu().numpy()
         y_cols = np.stack([dt[:, t].cpu().numpy() == c for t, c in report.COLUMN_PAIRS])
         curves = curves_from_ranking(ss, order.cpu().numpy(), gs.cpu().numpy(), y_cols)
@@ -280,11 +262,8 @@ def _report(preds, targets, spec_floors, sens_floors, decision, thresholds, boot
            "decision": list(decision), "targets": targets.detach().cpu().clone(), "n": N}
     if B:
         rv, ru = values_from_counts(reps, Ls, Lr, Lt, decision, N)
-        lo, hi = report.interval(rv, confidence)
-        out.update({"replicates": torch.from_numpy(rv), "replicate_counts": torch.from_numpy(reps),
-                    "lo": torch.from_numpy(lo.copy()), "hi": torch.from_numpy(hi.copy()),
-                    "undefined": torch.from_numpy(ru.sum(axis=0).astype(np.int64)), "bootstrap": B, "seed": seed,
-                    "confidence": float(confidence)})
+        boot = resample.pack_intervals({}, [("", rv, ru.sum(axis=0))], B, seed, confidence)
+        out.update({"replicates": boot.pop("replicates"), "replicate_counts": torch.from_numpy(reps)}, **boot)
     return out
 
 
@@ -310,27 +289,10 @@ def compare(a, b):
     bootstrap, seed and confidence (ValueError otherwise), so replicate r of both resamples the same cases.  Returns {"delta":
     a.values - b.values [rows, 29], "rows", "columns"} and, with a bootstrap, "lo", "hi" by the interval rule on a.replicates -
     b.replicates, "frac_le_zero" = the fraction of replicates with a difference <= 0, "bootstrap", "seed", "confidence"."""
-    for r in (a, b):
-        if not isinstance(r, dict) or "values" not in r or "targets" not in r or "rows" not in r:
-            raise ValueError("compare: two dicts from operating_report are needed")
-    if tuple(a["targets"].shape) != tuple(b["targets"].shape) or not bool(torch.equal(a["targets"], b["targets"])):
-        raise ValueError("compare: the two reports must be of the same cases (equal targets)")
-    if a["rows"] != b["rows"]:
-        raise ValueError("compare: the two reports hold different rows (floors, decision thresholds or thresholds differ)")
-    if a.get("bootstrap", 0) != b.get("bootstrap", 0):
-        raise ValueError(f"compare: bootstrap differs ({a.get('bootstrap', 0)} and {b.get('bootstrap', 0)})")
-    if a.get("seed") != b.get("seed"):
-        raise ValueError(f"compare: seed differs ({a.get('seed')} and {b.get('seed')}): the replicates would not be paired")
-    if a.get("confidence") != b.get("confidence"):
-        raise ValueError(f"compare: confidence differs ({a.get('confidence')} and {b.get('confidence')})")
-    out = {"delta": a["values"] - b["values"], "rows": list(a["rows"]), "columns": list(a["columns"])}
-    if a.get("bootstrap", 0):
-        d = (a["replicates"] - b["replicates"]).numpy()
-        lo, hi = report.interval(d, a["confidence"])
-        out.update({"lo": torch.from_numpy(lo.copy()), "hi": torch.from_numpy(hi.copy()),
-                    "frac_le_zero": torch.from_numpy((d <= 0).sum(axis=0) / float(d.shape[0])),
-                    "bootstrap": a["bootstrap"], "seed": a["seed"], "confidence": a["confidence"]})
-    return out
+    resample.check_paired(a, b, "operating_report", ("values", "targets", "rows"),
+                          (("rows", "the two reports hold different rows (floors, decision thresholds or thresholds differ)"),))
+    return resample.paired_intervals({"delta": a["values"] - b["values"], "rows": list(a["rows"]), "columns": list(a["columns"])},
+                                     a, b)
 
 
 def csv_rows(rep):
@@ -348,28 +310,13 @@ def csv_rows(rep):
 
 def to_csv(rep, path):
     """The long format of csv_rows with a header; repr of the fp64 values: they parse back exactly."""
-    with open(path, "w") as f:
-        f.write("row,column,value" + (",lo,hi,undefined" if "lo" in rep else "") + "\n")
-        for row in csv_rows(rep):
-            f.write(",".join(repr(v) if isinstance(v, float) else str(v) for v in row) + "\n")
-
-
-def _plain(v):
-    if isinstance(v, torch.Tensor):
-        return v.tolist()
-    if isinstance(v, dict):
-        return {k: _plain(x) for k, x in v.items()}
-    if isinstance(v, (list, tuple)):
-        return [_plain(x) for x in v]
-    return v
+    resample.write_long_csv(path, "row,column,value" + (",lo,hi,undefined" if "lo" in rep else ""), csv_rows(rep))
 
 
 def to_json(rep, path):
     """Everything but the replicates and the targets, as lists (json writes repr of a float: the values parse back exactly; the
     empty point's threshold is written as Infinity, which json reads back)."""
-    out = {k: _plain(v) for k, v in rep.items() if k not in ("replicates", "replicate_counts", "targets")}
-    with open(path, "w") as f:
-        json.dump(out, f, indent=1)
+    resample.write_json(rep, path, ("replicates", "replicate_counts", "targets"))
 
 
 def _shown():
@@ -430,9 +377,7 @@ def flag_settings(args):
 
 def save(rep, log_path, stem="val_operating"):
     """<stem>.json and <stem>.csv under log_path."""
-    os.makedirs(log_path, exist_ok=True)
-    to_json(rep, os.path.join(log_path, stem + ".json"))
-    to_csv(rep, os.path.join(log_path, stem + ".csv"))
+    resample.save(rep, log_path, stem, to_json, to_csv)
 
 
 def stats_line(rep):

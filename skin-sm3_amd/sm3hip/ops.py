@@ -1468,6 +1468,14 @@ def rise_accumulate(table, weights, maps, cells, p):
 REPORT_MAX_CASES = 8192  # sm3_report_max_cases(): the multiplicities and the prefix sums of a replicate live in LDS
 
 
+def _replicates_chk(who, seed, point, c, one="table"):
+    """What the four *_counts wrappers ask of the replicates (sm3hip/resample.py: the rule): a 64-bit seed, one point table."""
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{who}: seed must fit 64 bits")
+    if point and c != 1:
+        raise ValueError(f"{who}: the point estimate is one {one}")
+
+
 def report_counts(order, gs, ge, targets, yhat, colmap, out, seed, r0, point=False):
     """out [c, K, 6] int64 = (A2, P, Q, TP, FP, FN) of the K columns for bootstrap replicates r0 .. r0 + c - 1, or for the point
     estimate (point: c = 1, every case once) (sm3_report_counts).  order, gs, ge [K, N] int32: per column the cases in ascending
@@ -1485,10 +1493,7 @@ def report_counts(order, gs, ge, targets, yhat, colmap, out, seed, r0, point=Fal
     if tuple(gs.shape) != (K, N) or tuple(ge.shape) != (K, N) or tuple(targets.shape) != (N, T) or \
             tuple(yhat.shape) != (N, T) or tuple(colmap.shape) != (K, 2) or tuple(out.shape) != (c, K, 6):
         raise ValueError("report_counts: order, gs, ge [K, N], targets, yhat [N, T], colmap [K, 2] and out [c, K, 6] do not match")
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("report_counts: seed must fit 64 bits")
-    if point and c != 1:
-        raise ValueError("report_counts: the point estimate is one table")
+    _replicates_chk("report_counts", seed, point, c)
     with _prof("report_counts", 0.0, 4.0 * 3 * K * N * c):
         check(_lib.load().sm3_report_counts(_ptr(order), _ptr(gs), _ptr(ge), _ptr(targets), _ptr(yhat), _ptr(colmap), _ptr(out),
                                             N, T, K, seed, int(r0), c, int(bool(point)), _stream()), "sm3_report_counts")
@@ -1537,10 +1542,7 @@ def retrieval_counts(bits, ks, out, seed, r0, point=False):
         raise ValueError(f"retrieval_counts: 1 to {RETRIEVAL_MAX_LEVELS} integer levels in [1, {REPORT_MAX_CASES}], got {ks!r}")
     if bits.shape[1] != (N + 31) // 32 or c < 1 or tuple(out.shape) != (c, L + 3):
         raise ValueError(f"retrieval_counts: bits [N, {(N + 31) // 32}] and out [c, {L + 3}] do not match")
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("retrieval_counts: seed must fit 64 bits")
-    if point and c != 1:
-        raise ValueError("retrieval_counts: the point estimate is one record")
+    _replicates_chk("retrieval_counts", seed, point, c, "record")
     with _prof("retrieval_counts", 0.0, 4.0 * bits.numel() * c):
         check(_lib.load().sm3_retrieval_counts(_ptr(bits), N, (C.c_int32 * L)(*ks), L, _ptr(out), seed, int(r0), c, int(bool(point)),
                                                _stream()), "sm3_retrieval_counts")
@@ -1572,10 +1574,7 @@ def calib_counts(q, ev, order, slabel, xq, bins, sums, labels, binning, seed, r0
         raise ValueError("calib_counts: q, ev, order [S, N], slabel [S], xq [X, N], bins [c, S, M, 3] and sums [c, X] do not match")
     if binning not in CALIB_BINNINGS:
         raise ValueError(f"calib_counts: binning must be one of {CALIB_BINNINGS}, got {binning!r}")
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("calib_counts: seed must fit 64 bits")
-    if point and c != 1:
-        raise ValueError("calib_counts: the point estimate is one table")
+    _replicates_chk("calib_counts", seed, point, c)
     with _prof("calib_counts", 0.0, (8.0 + 4 + 1) * S * N * c):
         check(_lib.load().sm3_calib_counts(_ptr(q), _ptr(ev), _ptr(order), _ptr(slabel), _ptr(xq), _ptr(bins), _ptr(sums), N, S, X,
                                            int(labels), M, CALIB_BINNINGS.index(binning), seed, int(r0), c, int(bool(point)),
@@ -1615,10 +1614,7 @@ def operating_counts(order, gs, ge, targets, colmap, sigma, rho, fixpos, out, se
             tuple(fixpos.shape) != (K, Lt) or tuple(out.shape) != (c, K, operating_record(Ls, Lr, Lt)):
         raise ValueError("operating_counts: order, gs, ge [K, N], targets [N, T], colmap [K, 2], fixpos [K, Lt] and out [c, K, 9 + "
                          "3 Ls + 3 Lr + 2 Lt] do not match")
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("operating_counts: seed must fit 64 bits")
-    if point and c != 1:
-        raise ValueError("operating_counts: the point estimate is one table")
+    _replicates_chk("operating_counts", seed, point, c)
     with _prof("operating_counts", 0.0, 4.0 * 3 * K * N * c):
         check(_lib.load().sm3_operating_counts(_ptr(order), _ptr(gs), _ptr(ge), _ptr(targets), _ptr(colmap),
                                                _ptr(sigma) if Ls else None, _ptr(rho) if Lr else None, _ptr(fixpos) if Lt else None,

@@ -20,26 +20,19 @@ pairs, label-major in CLASSES_NAME order with NUM_CLASSES = [5, 3, 2, 3, 3, 3, 3
   * averages, five per metric, each summed one column at a time in ascending column index, then one division:
         "8 all avg" all 24 columns; "8 avg" the 8 columns (t, CLS_WEIGHTS[t]) -- the reference's AUC_AVG, Recall_AVG, ...
         (misc.py:312-316); "7 all avg" the 19 non-DIAG columns; "7 avg" the 7 selected non-DIAG columns; "DIAG avg" DIAG's 5.
-  * resampling: replicate r, draw d (0 <= d < N): word d % 4 of Philox4x32-10 (csrc/exact_f32.h), key = the 64-bit seed (low word
-    first), counter (d / 4, r, 0, 2) -- the last word keeps the stream apart from SmoothGrad's 0 and RISE's 1; the case index is
-    (w * N) >> 32 in 64-bit integers; m_r[i] = the number of draws that hit case i.  ONE m_r is shared by all 24 columns and all
-    four metrics, so the averages' intervals are joint.  A replicate is a function of (seed, r, N) alone: not of B, the chunk or
-    the launch geometry.
-  * interval: per series (4 x 29) the B replicate values sorted ascending, lo = v[i], hi = v[B - 1 - i], i = floor((B - 1) *
-    (1 - confidence) / 2) in float64.  undefined[metric, column] = the replicates whose denominator was 0 (their value is 0); for
+  * resampling and interval: the rule of resample.py.  ONE m_r is shared by all 24 columns and all four metrics, so the
+    averages' intervals are joint.  undefined[metric, column] = the replicates whose denominator was 0 (their value is 0); for
     an average, the replicates in which any contributing column was undefined.
 
 The counts come from sm3_report_counts (csrc/report.hip): one workgroup per replicate and label, integers only, so equal inputs give equal
 bits; values, averages and order statistics are small and done on the host, adding one at a time (as faith.auc does).
 N <= MAX_CASES (the multiplicities and the prefix sums of a replicate live in LDS)."""
-import json
-import os
-
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, resample
 from .metrics import CLASSES_NAME, CLS_WEIGHTS, NUM_CLASSES
+from .resample import MAX_BOOTSTRAP, check_settings, interval, interval_index  # noqa: F401  (this module's names too)
 
 MAX_CASES = ops.REPORT_MAX_CASES
 METRICS = ("AUC", "Recall", "Spec", "Prec")
@@ -60,24 +53,7 @@ K, NV = len(COLUMN_PAIRS), len(COLUMNS)  # 24, 29
 CSV_COLUMNS = [n for lab in ("BWV", "DaG", "PIG", "PN", "RS", "STR", "VS", "DIAG") for n in CLASS_COLUMNS
                if n.split("-")[0] == lab] + list(AVERAGES)
 CSV_ROWS = ("Acc",) + METRICS  # Acc = Recall
-MAX_BOOTSTRAP = 2 ** 24
 DEFAULT_CHUNK = 4096  # replicates per launch: a choice (4096 x 24 x 6 int64 = 4.5 MiB of counts)
-
-
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
-def check_settings(bootstrap, confidence, seed, chunk, who="evaluation_report"):
-    """The refusals that need neither a tensor nor a device."""
-    if not _is_int(bootstrap) or not 0 <= bootstrap <= MAX_BOOTSTRAP:
-        raise ValueError(f"{who}: bootstrap must be an integer in [0, 2^24], got {bootstrap!r}")
-    if isinstance(confidence, bool) or not isinstance(confidence, (int, float)) or not 0 < confidence < 1:
-        raise ValueError(f"{who}: confidence must be a number with 0 < confidence < 1, got {confidence!r}")
-    if not _is_int(seed) or not 0 <= seed < 2 ** 64:
-        raise ValueError(f"{who}: seed must be an integer in [0, 2^64), got {seed!r}")
-    if chunk is not None and (not _is_int(chunk) or not 1 <= chunk <= max(bootstrap, 1)):
-        raise ValueError(f"{who}: chunk must be None or an integer in [1, {max(bootstrap, 1)}], got {chunk!r}")
 
 
 def check_inputs(preds, targets, who="evaluation_report"):
@@ -121,14 +97,6 @@ def ranking(preds, targets):
     return order.int().contiguous(), gs.int().contiguous(), ge.int().contiguous(), yhat.int().contiguous()
 
 
-def _safe_div(num, den):
-    """num / den in fp64, 0 where den == 0: ONE division of two exactly represented integers."""
-    num, den = num.astype(np.float64), den.astype(np.float64)
-    out = np.zeros_like(num)
-    np.divide(num, den, out=out, where=den != 0)
-    return out
-
-
 def averages(v):
     """v [..., 24] fp64 -> the five averages [..., 5]: each summed one column at a time in ascending column index, then ONE
     division by the number of columns."""
@@ -152,25 +120,11 @@ def values_from_counts(counts):
     values = np.zeros(counts.shape[:-2] + (len(METRICS), NV), dtype=np.float64)
     undefined = np.zeros(values.shape, dtype=bool)
     for i, (num, den) in enumerate(zip(nums, dens)):
-        values[..., i, :K] = _safe_div(num, den)
-        undefined[..., i, :K] = den == 0
+        values[..., i, :K], undefined[..., i, :K] = resample.safe_div(num, den)
         values[..., i, K:] = averages(values[..., i, :K])
         for a, cols in enumerate(AVERAGES.values()):
             undefined[..., i, K + a] = undefined[..., i, cols].any(axis=-1)
     return values, undefined
-
-
-def interval_index(B, confidence):
-    """i of lo = v[i], hi = v[B - 1 - i] over the B sorted replicate values: floor((B - 1) * (1 - confidence) / 2) in float64."""
-    return int(np.floor(np.float64(B - 1) * (np.float64(1.0) - np.float64(confidence)) / np.float64(2.0)))
-
-
-def interval(replicates, confidence):
-    """replicates [B, ...] fp64 -> (lo, hi) [...] by the order-statistic rule."""
-    v = np.sort(np.asarray(replicates, dtype=np.float64), axis=0)
-    B = v.shape[0]
-    i = interval_index(B, confidence)
-    return v[i], v[B - 1 - i]
 
 
 def evaluation_report(preds, targets, bootstrap=0, confidence=0.95, seed=0, chunk=None):
@@ -186,32 +140,20 @@ def evaluation_report(preds, targets, bootstrap=0, confidence=0.95, seed=0, chun
     who = "evaluation_report"
     check_settings(bootstrap, confidence, seed, chunk, who)
     N = check_inputs(preds, targets, who)
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{who}: needs a GPU (the SM3 HIP path has no CPU fallback)")
-    dev = preds[0].device if preds[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
-    B = bootstrap
+    dev = resample.device_for(preds, who)
     with torch.no_grad(), torch.cuda.device(dev), ops.stream_scope():
         order, gs, ge, yhat = ranking([p.detach().to(dev) for p in preds], targets.to(dev))
         y = targets.to(dev).int().contiguous()
         colmap = torch.tensor(COLUMN_PAIRS, dtype=torch.int32, device=dev)
-        point = torch.empty((1, K, 6), dtype=torch.int64, device=dev)
-        ops.report_counts(order, gs, ge, y, yhat, colmap, point, seed, 0, point=True)
-        if B:
-            c = min(B, DEFAULT_CHUNK) if chunk is None else chunk
-            reps = torch.empty((B, K, 6), dtype=torch.int64, device=dev)
-            for r0 in range(0, B, c):
-                ops.report_counts(order, gs, ge, y, yhat, colmap, reps[r0:r0 + min(c, B - r0)], seed, r0)
-            reps = reps.cpu().numpy()
-        point = point[0].cpu().numpy()
+        (point,), (reps,) = resample.replicate_tables(
+            lambda outs, seed, r0, point: ops.report_counts(order, gs, ge, y, yhat, colmap, outs[0], seed, r0, point=point),
+            [(K, 6)], bootstrap, seed, chunk, DEFAULT_CHUNK, dev)
     values, _ = values_from_counts(point)
     out = {"counts": torch.from_numpy(point), "values": torch.from_numpy(values), "columns": list(COLUMNS),
            "metrics": list(METRICS), "targets": targets.detach().cpu().clone(), "n": N}
-    if B:
+    if bootstrap:
         rv, ru = values_from_counts(reps)
-        lo, hi = interval(rv, confidence)
-        out.update({"replicates": torch.from_numpy(rv), "lo": torch.from_numpy(lo.copy()), "hi": torch.from_numpy(hi.copy()),
-                    "undefined": torch.from_numpy(ru.sum(axis=0).astype(np.int64)), "bootstrap": B, "seed": seed,
-                    "confidence": float(confidence)})
+        resample.pack_intervals(out, [("", rv, ru.sum(axis=0))], bootstrap, seed, confidence)
     return out
 
 
@@ -220,25 +162,8 @@ def compare(a, b):
     replicate r of both resamples the same cases.  Returns {"delta": a.values - b.values [4, 29], "columns", "metrics"} and,
     with a bootstrap, "lo", "hi" by the interval rule on a.replicates - b.replicates, "frac_le_zero" [4, 29] = the fraction of
     replicates with a difference <= 0, "bootstrap", "seed", "confidence"."""
-    for r in (a, b):
-        if not isinstance(r, dict) or "values" not in r or "targets" not in r:
-            raise ValueError("compare: two dicts from evaluation_report are needed")
-    if tuple(a["targets"].shape) != tuple(b["targets"].shape) or not bool(torch.equal(a["targets"], b["targets"])):
-        raise ValueError("compare: the two reports must be of the same cases (equal targets)")
-    if a.get("bootstrap", 0) != b.get("bootstrap", 0):
-        raise ValueError(f"compare: bootstrap differs ({a.get('bootstrap', 0)} and {b.get('bootstrap', 0)})")
-    if a.get("seed") != b.get("seed"):
-        raise ValueError(f"compare: seed differs ({a.get('seed')} and {b.get('seed')}): the replicates would not be paired")
-    if a.get("confidence") != b.get("confidence"):
-        raise ValueError(f"compare: confidence differs ({a.get('confidence')} and {b.get('confidence')})")
-    out = {"delta": a["values"] - b["values"], "columns": list(COLUMNS), "metrics": list(METRICS)}
-    if a.get("bootstrap", 0):
-        d = (a["replicates"] - b["replicates"]).numpy()
-        lo, hi = interval(d, a["confidence"])
-        out.update({"lo": torch.from_numpy(lo.copy()), "hi": torch.from_numpy(hi.copy()),
-                    "frac_le_zero": torch.from_numpy((d <= 0).sum(axis=0) / float(d.shape[0])),
-                    "bootstrap": a["bootstrap"], "seed": a["seed"], "confidence": a["confidence"]})
-    return out
+    resample.check_paired(a, b, "evaluation_report", ("values", "targets"))
+    return resample.paired_intervals({"delta": a["values"] - b["values"], "columns": list(COLUMNS), "metrics": list(METRICS)}, a, b)
 
 
 def selected(report, metric):
@@ -275,13 +200,7 @@ def to_csv(report, path):
 
 def to_json(report, path):
     """Everything but the replicates and the targets, as lists."""
-    out = {}
-    for k, v in report.items():
-        if k in ("replicates", "targets"):
-            continue
-        out[k] = v.tolist() if isinstance(v, torch.Tensor) else v
-    with open(path, "w") as f:
-        json.dump(out, f, indent=1)
+    resample.write_json(report, path, ("replicates", "targets"))
 
 
 def format_table(report):
@@ -299,21 +218,28 @@ def format_table(report):
     return "\n".join(lines)
 
 
+def format_compare(cmp):
+    lines = []
+    for i, m in enumerate(cmp["metrics"]):
+        lines.append(f"{m} difference")
+        for k, name in enumerate(cmp["columns"]):
+            s = f"  {name:<10} {100.0 * float(cmp['delta'][i, k]):+7.2f}"
+            if "lo" in cmp:
+                s += (f"  [{100.0 * float(cmp['lo'][i, k]):+6.2f}, {100.0 * float(cmp['hi'][i, k]):+6.2f}]"
+                      f"  <= 0 in {float(cmp['frac_le_zero'][i, k]):.3f}")
+            lines.append(s)
+    return "\n".join(lines)
+
+
 # ---- what the command-line tools share ----------------------------------------------------------------------------------
 def add_flags(parser):
     """--bootstrap / --bootstrap-seed / --confidence of the evaluation tools."""
-    parser.add_argument("--bootstrap", type=int, default=0,
-                        help="case-resampling bootstrap replicates of the last validation pass's report (0: point estimate only)")
-    parser.add_argument("--bootstrap-seed", type=int, default=0, help="64-bit seed of the bootstrap replicates")
-    parser.add_argument("--confidence", type=float, default=0.95, help="confidence of the bootstrap intervals")
-    return parser
+    return resample.add_bootstrap_flags(parser, " of the last validation pass's report")
 
 
 def save(report, log_path, stem="val_report"):
     """<stem>.json and <stem>.csv under log_path."""
-    os.makedirs(log_path, exist_ok=True)
-    to_json(report, os.path.join(log_path, stem + ".json"))
-    to_csv(report, os.path.join(log_path, stem + ".csv"))
+    resample.save(report, log_path, stem, to_json, to_csv)
 
 
 def validation_stats(preds, targets, args, final, log_path=None):

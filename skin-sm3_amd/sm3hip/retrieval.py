@@ -23,10 +23,8 @@ Row i of each belongs to case i: the positive of query i is gallery row i.
     The Q32 rule of MRR (as the calibration report's): each case's 1 / (rho + 1) enters as floor(2^32 / (rho + 1)), below the
     exact reciprocal by less than 2^-32; both operands of the division are exactly represented (Q <= N 2^32 < 2^46), so the value
     is within 2^-32 of the exact mean reciprocal rank.
-  * resampling: replicate r uses exactly the m_r of sm3_report_counts: Philox4x32-10, key = the seed, counter (d / 4, r, 0, 2),
-    case (w N) >> 32.  With the same seed and the same N cases the intervals are joint with those of the evaluation, calibration
-    and operating reports.  Intervals by report.interval / report.interval_index.  Nothing is ever undefined: every denominator
-    is N.
+  * resampling and interval: the rule of resample.py.  With the same seed and the same N cases the intervals are joint with
+    those of the evaluation, calibration and operating reports.  Nothing is ever undefined: every denominator is N.
   * point-only extras, fp64, no interval:
         loss(T) = mean_i [log sum_{j<N} exp(S_ij / T) - S_ii / T], S widened to fp64 before the division; the row terms come
         from the kernel in one fixed order and are added on the host in ascending i;  positive_similarity = mean_i S_ii, added
@@ -35,13 +33,10 @@ Row i of each belongs to case i: the positive of query i is gallery row i.
     (seed, r, N, bits) alone.
 
 The kernels are sm3_retrieval_beats and sm3_retrieval_counts (csrc/retrieval.hip)."""
-import json
-import os
-
 import numpy as np
 import torch
 
-from . import ops, report
+from . import ops, report, resample
 from .knn import _GEMM_MAX_BYTES, KNNBank, normalize as _normalize
 
 MAX_CASES = ops.REPORT_MAX_CASES
@@ -64,7 +59,7 @@ def check_levels(ks, temperature, who="retrieval_report"):
     if not 1 <= len(ks) <= MAX_LEVELS:
         raise ValueError(f"{who}: 1 to {MAX_LEVELS} Recall@k levels, got {len(ks)}")
     for k in ks:
-        if not report._is_int(k) or not 1 <= k <= MAX_CASES:
+        if not resample.is_int(k) or not 1 <= k <= MAX_CASES:
             raise ValueError(f"{who}: every k must be an integer in [1, MAX_CASES = {MAX_CASES}], got {k!r}")
     if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0 < temperature < float("inf"):
         raise ValueError(f"{who}: temperature must be a positive finite number, got {temperature!r}")
@@ -135,18 +130,10 @@ def beats(query, gallery, temperature=0.1, max_s_bytes=1 << 30):
 
 def counts(bits, ks, bootstrap=0, seed=0, chunk=None):
     """(point [L + 3], replicates [B, L + 3] or None) int64 numpy, from the packed flags on the device."""
-    dev = bits.device
-    L = len(ks)
-    point = torch.empty(1, L + 3, dtype=torch.int64, device=dev)
-    ops.retrieval_counts(bits, ks, point, seed, 0, point=True)
-    reps = None
-    if bootstrap:
-        c = min(bootstrap, DEFAULT_CHUNK) if chunk is None else chunk
-        reps = torch.empty(bootstrap, L + 3, dtype=torch.int64, device=dev)
-        for r0 in range(0, bootstrap, c):
-            ops.retrieval_counts(bits, ks, reps[r0:r0 + min(c, bootstrap - r0)], seed, r0)
-        reps = reps.cpu().numpy()
-    return point[0].cpu().numpy(), reps
+    (point,), (reps,) = resample.replicate_tables(
+        lambda outs, seed, r0, point: ops.retrieval_counts(bits, ks, outs[0], seed, r0, point=point),
+        [(len(ks) + 3,)], bootstrap, seed, chunk, DEFAULT_CHUNK, bits.device)
+    return point, reps
 
 
 def retrieval_report(query, gallery, ks=(1, 5, 10), temperature=0.1, normalize=True, bootstrap=0, confidence=0.95, seed=0,
@@ -159,7 +146,7 @@ def retrieval_report(query, gallery, ks=(1, 5, 10), temperature=0.1, normalize=T
     who = "retrieval_report"
     report.check_settings(bootstrap, confidence, seed, chunk, who)
     ks = check_levels(ks, temperature, who)
-    if not report._is_int(max_s_bytes) or max_s_bytes < 1:
+    if not resample.is_int(max_s_bytes) or max_s_bytes < 1:
         raise ValueError(f"{who}: max_s_bytes must be a positive integer, got {max_s_bytes!r}")
     N, _ = check_inputs(query, gallery, who)
     with torch.no_grad(), torch.cuda.device(query.device), ops.stream_scope():
@@ -173,10 +160,7 @@ def retrieval_report(query, gallery, ks=(1, 5, 10), temperature=0.1, normalize=T
            "ranks": rank.long() + 1, "counts": torch.from_numpy(point), "values": torch.from_numpy(values_from_counts(point, N)),
            "loss": _ascending_sum(term) / N, "positive_similarity": _ascending_sum(diag) / N}
     if bootstrap:
-        rv = values_from_counts(reps, N)
-        lo, hi = report.interval(rv, confidence)
-        out.update({"replicates": torch.from_numpy(rv), "lo": torch.from_numpy(lo.copy()), "hi": torch.from_numpy(hi.copy()),
-                    "bootstrap": bootstrap, "seed": seed, "confidence": float(confidence)})
+        resample.pack_intervals(out, [("", values_from_counts(reps, N), None)], bootstrap, seed, confidence)
     return out
 
 
@@ -199,33 +183,19 @@ def compare(a, b):
     give {"directions", direction: comparison}."""
     if _is_cross(a) and _is_cross(b):
         return {"directions": list(DIRECTIONS), **{d: compare(a[d], b[d]) for d in DIRECTIONS}}
-    for r in (a, b):
-        if not isinstance(r, dict) or "values" not in r or "ks" not in r:
-            raise ValueError("compare: two dicts from retrieval_report (or two from cross_modal_report) are needed")
-    for key, what in (("N", "the number of cases"), ("ks", "ks"), ("bootstrap", "bootstrap"), ("seed", "seed"),
-                      ("confidence", "confidence")):
-        if a.get(key) != b.get(key):
-            raise ValueError(f"compare: {what} differs ({a.get(key)} and {b.get(key)}): the reports are not paired")
-    out = {"delta": a["values"] - b["values"], "series": list(a["series"]), "loss_delta": a["loss"] - b["loss"]}
-    if a.get("bootstrap", 0):
-        d = (a["replicates"] - b["replicates"]).numpy()
-        lo, hi = report.interval(d, a["confidence"])
-        out.update({"lo": torch.from_numpy(lo.copy()), "hi": torch.from_numpy(hi.copy()),
-                    "frac_le_zero": torch.from_numpy((d <= 0).sum(axis=0) / float(d.shape[0])),
-                    "bootstrap": a["bootstrap"], "seed": a["seed"], "confidence": a["confidence"]})
-    return out
+    resample.check_paired(a, b, "retrieval_report (or two from cross_modal_report)", ("values", "ks"),
+                          (("N", "the number of cases differs ({} and {})"), ("ks", "ks differ ({} and {})")))
+    return resample.paired_intervals({"delta": a["values"] - b["values"], "series": list(a["series"]),
+                                      "loss_delta": a["loss"] - b["loss"]}, a, b)
 
 
 def _plain(rep):
     """Everything but the replicates and the ranks, as lists."""
-    if _is_cross(rep):
-        return {k: (_plain(v) if k in DIRECTIONS else v) for k, v in rep.items()}
-    return {k: (v.tolist() if isinstance(v, torch.Tensor) else v) for k, v in rep.items() if k not in ("replicates", "ranks")}
+    return resample.plain(rep, ("replicates", "ranks"))
 
 
 def to_json(rep, path):
-    with open(path, "w") as f:
-        json.dump(_plain(rep), f, indent=1)
+    resample.write_json(rep, path, ("replicates", "ranks"))
 
 
 def csv_rows(rep):
@@ -251,9 +221,7 @@ def to_csv(rep, path):
 
 def save(rep, log_path, stem="retrieval"):
     """<stem>.json and <stem>.csv under log_path."""
-    os.makedirs(log_path, exist_ok=True)
-    to_json(rep, os.path.join(log_path, stem + ".json"))
-    to_csv(rep, os.path.join(log_path, stem + ".csv"))
+    resample.save(rep, log_path, stem, to_json, to_csv)
 
 
 def stats_line(rep, name=""):
@@ -309,10 +277,7 @@ def add_flags(parser):
     """--retrieval-k / --retrieval-t and the bootstrap flags of the report family."""
     parser.add_argument("--retrieval-k", type=int, nargs="+", default=[1, 5, 10], help="the Recall@k levels (1 to 8 of them)")
     parser.add_argument("--retrieval-t", type=float, default=0.1, help="temperature of the held-out InfoNCE value")
-    parser.add_argument("--bootstrap", type=int, default=0, help="case-resampling bootstrap replicates (0: point estimate only)")
-    parser.add_argument("--bootstrap-seed", type=int, default=0, help="64-bit seed of the bootstrap replicates")
-    parser.add_argument("--confidence", type=float, default=0.95, help="confidence of the bootstrap intervals")
-    return parser
+    return resample.add_bootstrap_flags(parser)
 
 
 def check_flags(args, who="backbone_retrieval"):

@@ -31,7 +31,6 @@ With --fit-on OTHER.pt the thresholds that --operating-rule (youden, f1, spec>=X
 PRED.pt: sens / spec / PPV / NPV at the transferred thresholds with their intervals (<name>_operating_fitted.json / .csv).
 """
 import argparse
-import json
 import os
 import sys
 
@@ -43,7 +42,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 
 import torch  # noqa: E402
 
-from sm3hip import calibration, operating, report  # noqa: E402
+from sm3hip import calibration, operating, report, resample  # noqa: E402
 
 
 def get_parser():
@@ -58,24 +57,6 @@ def get_parser():
     p.add_argument("--fit-on", metavar="OTHER.pt", default=None,
                    help="fit the temperatures on this predictions file; report PRED.pt at T = 1 and at the fitted T (implies --calibration)")
     return p
-
-
-def format_compare(cmp):
-    lines = []
-    for i, m in enumerate(cmp["metrics"]):
-        lines.append(f"{m} difference")
-        for k, name in enumerate(cmp["columns"]):
-            s = f"  {name:<10} {100.0 * float(cmp['delta'][i, k]):+7.2f}"
-            if "lo" in cmp:
-                s += (f"  [{100.0 * float(cmp['lo'][i, k]):+6.2f}, {100.0 * float(cmp['hi'][i, k]):+6.2f}]"
-                      f"  <= 0 in {float(cmp['frac_le_zero'][i, k]):.3f}")
-            lines.append(s)
-    return "\n".join(lines)
-
-
-def _dump(obj, path):
-    with open(path, "w") as f:
-        json.dump({k: (v.tolist() if isinstance(v, torch.Tensor) else v) for k, v in obj.items()}, f, indent=1)
 
 
 def calibrate(args, preds, targets, kw, out, stem, dev):
@@ -99,7 +80,7 @@ def calibrate(args, preds, targets, kw, out, stem, dev):
         cmp = calibration.compare(fitted, cal)
         print("fitted - unscaled", flush=True)
         print(calibration.format_compare(cmp), flush=True)
-        _dump(dict(cmp, fit=fit), os.path.join(out, stem + "_calibration_compare.json"))
+        resample.write_json(dict(cmp, fit=fit), os.path.join(out, stem + "_calibration_compare.json"))
         result.update({"fit": fit, "calibration_fitted": fitted, "calibration_compare": cmp})
     return result
 
@@ -118,7 +99,7 @@ def operate(args, preds, targets, kw, out, stem, dev):
         cmp = operating.compare(opr, operating.operating_report(*report.load_predictions(args.against, dev), **okw))
         print(f"{args.pred} - {args.against}", flush=True)
         print(operating.format_compare(cmp), flush=True)
-        _dump(cmp, os.path.join(out, stem + "_operating_compare.json"))
+        resample.write_json(cmp, os.path.join(out, stem + "_operating_compare.json"))
         result["operating_compare"] = cmp
     if args.fit_on:
         thr = operating.fit_thresholds(*report.load_predictions(args.fit_on, dev), args.operating_rule)
@@ -151,9 +132,8 @@ def main(argv=None):
         other = report.evaluation_report(*report.load_predictions(args.against, dev), **kw)
         cmp = report.compare(rep, other)
         print(f"{args.pred} - {args.against}", flush=True)
-        print(format_compare(cmp), flush=True)
-        with open(os.path.join(out, stem + "_compare.json"), "w") as f:
-            json.dump({k: (v.tolist() if isinstance(v, torch.Tensor) else v) for k, v in cmp.items()}, f, indent=1)
+        print(report.format_compare(cmp), flush=True)
+        resample.write_json(cmp, os.path.join(out, stem + "_compare.json"))
         result.update({"other": other, "compare": cmp})
     if args.calibration or args.fit_on:
         result.update(calibrate(args, preds, targets, kw, out, stem, dev))
