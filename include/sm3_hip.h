@@ -922,6 +922,40 @@ int sm3_retrieval_beats(const float* S, int64_t ld, int n, int q0, int N, double
 int sm3_retrieval_counts(const uint32_t* bits, int N, const int32_t* ks, int L, int64_t* out, uint64_t seed, int64_t r0, int c,
                          int point, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact t-SNE maps of embeddings (csrc/tsne.hip, sm3hip/tsne.py; ABI 9, additive).  N points, 4 <= N <=
+ * sm3_tsne_max_points() = 16384; every function refuses a null pointer or an N outside that range with SM3_EINVAL before anything
+ * is launched, and a float / double pointer that is not 4 / 8-byte aligned with SM3_EALIGN (y: 8-byte, it is read as pairs).
+ * No float atomics.  "The fixed order" of a sum over j: thread t of a 256-thread workgroup adds the terms j = t, t + 256, ... in
+ * ascending j in fp64, then the 256 partials fold by the halving tree a[t] += a[t + h], h = 128, 64 .. 1 -- a function of the
+ * terms and their number alone.  Products and sums are rounded separately (no contraction) unless fma is written.
+ * sm3_tsne_sqdist: d2 [N][N] f32, d2[i][j] = sum_k (x_ik - x_jk)^2 as acc = fmaf(d, d, acc), k ascending, x [N][D] f32 row-major,
+ *   1 <= D <= 4096; the diagonal is stored as 0; d2[i][j] and d2[j][i] are the same bits.
+ * sm3_tsne_affinities: one workgroup per row i, fp64.  d'_j = d2[i][j] - min_{j != i} d2[i][j], e_j = exp(-(beta d'_j)),
+ *   S0 = sum_{j != i} e_j, S1 = sum_{j != i} d'_j e_j (the fixed order), H = log S0 + beta S1 / S0.  From beta = 1, exactly 100
+ *   steps of scikit-learn's _binary_search_perplexity (H > log perplexity: the lower end is beta, beta doubles while the upper end
+ *   is infinite, else the midpoint; otherwise the mirror image), no tolerance.  cond [N][N] f32: cond[i][j] = e_j / S0 at the last
+ *   beta, cond[i][i] = 0; beta [N] f64.  1 <= perplexity <= N - 1.  A row whose other points are all at one distance is uniform.
+ * sm3_tsne_symmetrise: P[i][j] = f32((f64(cond[i][j]) + f64(cond[j][i])) / (2 N)); P must not be cond.
+ * sm3_tsne_forces: one workgroup per point i; y [N][2] f32.  Per pair in f32: dx = y_i.x - y_j.x, dy likewise,
+ *   q = fmaf(dy, dy, fmaf(dx, dx, 1)), w = 1 / q correctly rounded; widened to f64 and added over j != i in the fixed order:
+ *   F[i] = (Z_i = sum w, A_i = sum (p_ij w) (dx, dy), R_i = sum (w w) (dx, dy)), F [N][5] f64.
+ * sm3_tsne_update: one workgroup.  Z = sum_i Z_i (the fixed order); g = 4 (exaggeration A - R / Z); per coordinate, in f64 from
+ *   the stored f32 state: gains + 0.2 where update g < 0, else gains 0.8, at least 0.01; update = momentum update - lr (gains g);
+ *   y += update; each rounded once to f32 on store.  out [2] f64 = (sum_i ((gains g)_x^2 + (gains g)_y^2) in the fixed order, Z).
+ *   exaggeration, momentum and lr must be finite.
+ * sm3_tsne_kl: rows [N] f64 (scratch), rows[i] = sum_{j != i, p_ij > 0} p_ij ((log p_ij - log w_ij) + log Z), w as in
+ *   sm3_tsne_forces, Z from F as in sm3_tsne_update; out[0] = sum_i rows[i], out[1] = Z, both in the fixed order; three launches.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_tsne_max_points(void);
+int sm3_tsne_sqdist(const float* x, int N, int D, float* d2, void* stream);
+int sm3_tsne_affinities(const float* d2, int N, double perplexity, float* cond, double* beta, void* stream);
+int sm3_tsne_symmetrise(const float* cond, int N, float* P, void* stream);
+int sm3_tsne_forces(const float* P, const float* y, int N, double* F, void* stream);
+int sm3_tsne_update(const double* F, int N, double exaggeration, double momentum, double lr, float* y, float* update, float* gains,
+                    double* out, void* stream);
+int sm3_tsne_kl(const float* P, const float* y, const double* F, int N, double* rows, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

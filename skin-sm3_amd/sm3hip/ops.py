@@ -1548,6 +1548,100 @@ def retrieval_counts(bits, ks, out, seed, r0, point=False):
                                                _stream()), "sm3_retrieval_counts")
 
 
+TSNE_MAX_POINTS = 16384  # sm3_tsne_max_points()
+TSNE_MAX_DIM = 4096
+
+
+def _tsne_n(who, N):
+    if not 4 <= N <= TSNE_MAX_POINTS:
+        raise ValueError(f"{who}: {N} points, 4 to {TSNE_MAX_POINTS} are supported")
+
+
+def tsne_sqdist(x, d2):
+    """d2 [N, N] float32 = the squared distances of the rows of x [N, D] float32, by differences, k ascending; the diagonal 0 and
+    d2 == d2.T in bits (sm3_tsne_sqdist)."""
+    _chk(x, torch.float32, "x"); _chk(d2, torch.float32, "d2")
+    if x.dim() != 2 or d2.dim() != 2:
+        raise ValueError("tsne_sqdist: x [N, D] and d2 [N, N]")
+    N, D = x.shape
+    _tsne_n("tsne_sqdist", N)
+    if not 1 <= D <= TSNE_MAX_DIM or tuple(d2.shape) != (N, N):
+        raise ValueError(f"tsne_sqdist: x [N, 1 <= D <= {TSNE_MAX_DIM}] and d2 [{N}, {N}] do not match")
+    with _prof("tsne_sqdist", 3.0 * N * N * D, 4.0 * N * N):
+        check(_lib.load().sm3_tsne_sqdist(_ptr(x), N, D, _ptr(d2), _stream()), "sm3_tsne_sqdist")
+
+
+def tsne_affinities(d2, perplexity, cond, beta):
+    """cond [N, N] float32 = the conditional affinities of the rows of d2 [N, N] float32 at the given perplexity (100 bisection
+    steps in fp64, cond[i, i] = 0), beta [N] float64 = the precisions found (sm3_tsne_affinities)."""
+    _chk(d2, torch.float32, "d2"); _chk(cond, torch.float32, "cond"); _chk(beta, torch.float64, "beta")
+    N = d2.shape[0]
+    _tsne_n("tsne_affinities", N)
+    if tuple(d2.shape) != (N, N) or tuple(cond.shape) != (N, N) or tuple(beta.shape) != (N,):
+        raise ValueError(f"tsne_affinities: d2 [{N}, {N}], cond [{N}, {N}] and beta [{N}] do not match")
+    if not 1 <= perplexity <= N - 1:
+        raise ValueError(f"tsne_affinities: the perplexity must lie in [1, N - 1], got {perplexity!r}")
+    with _prof("tsne_affinities", 0.0, 8.0 * N * N):
+        check(_lib.load().sm3_tsne_affinities(_ptr(d2), N, float(perplexity), _ptr(cond), _ptr(beta), _stream()),
+              "sm3_tsne_affinities")
+
+
+def tsne_symmetrise(cond, P):
+    """P [N, N] float32 = float32((cond + cond.T in fp64) / (2 N)) (sm3_tsne_symmetrise)."""
+    _chk(cond, torch.float32, "cond"); _chk(P, torch.float32, "P")
+    N = cond.shape[0]
+    _tsne_n("tsne_symmetrise", N)
+    if tuple(cond.shape) != (N, N) or tuple(P.shape) != (N, N) or cond.data_ptr() == P.data_ptr():
+        raise ValueError(f"tsne_symmetrise: cond [{N}, {N}] and another P [{N}, {N}]")
+    with _prof("tsne_symmetrise", 0.0, 12.0 * N * N):
+        check(_lib.load().sm3_tsne_symmetrise(_ptr(cond), N, _ptr(P), _stream()), "sm3_tsne_symmetrise")
+
+
+def _tsne_state(who, N, P=None, y=None, F=None):
+    _tsne_n(who, N)
+    if (P is not None and tuple(P.shape) != (N, N)) or (y is not None and tuple(y.shape) != (N, 2)) or \
+            (F is not None and tuple(F.shape) != (N, 5)):
+        raise ValueError(f"{who}: P [{N}, {N}], y [{N}, 2] and F [{N}, 5] do not match")
+
+
+def tsne_forces(P, y, F):
+    """F [N, 5] float64 = (Z_i, A_i.x, A_i.y, R_i.x, R_i.y) of the map y [N, 2] float32 under P [N, N] float32 (sm3_tsne_forces)."""
+    _chk(P, torch.float32, "P"); _chk(y, torch.float32, "y"); _chk(F, torch.float64, "F")
+    N = y.shape[0]
+    _tsne_state("tsne_forces", N, P, y, F)
+    with _prof("tsne_forces", 20.0 * N * N, 4.0 * N * N):
+        check(_lib.load().sm3_tsne_forces(_ptr(P), _ptr(y), N, _ptr(F), _stream()), "sm3_tsne_forces")
+
+
+def tsne_update(F, exaggeration, momentum, lr, y, update, gains, out):
+    """One gradient step from the force sums F [N, 5]: y, update and gains [N, 2] float32 are rewritten in place, out [2] float64 =
+    (sum (gains g)^2, Z) (sm3_tsne_update)."""
+    _chk(F, torch.float64, "F"); _chk(out, torch.float64, "out")
+    N = y.shape[0]
+    for t, n in ((y, "y"), (update, "update"), (gains, "gains")):
+        _chk(t, torch.float32, n)
+        if tuple(t.shape) != (N, 2):
+            raise ValueError(f"tsne_update: {n} must be [{N}, 2]")
+    _tsne_state("tsne_update", N, None, y, F)
+    if out.numel() != 2:
+        raise ValueError("tsne_update: out [2]")
+    with _prof("tsne_update", 0.0, 64.0 * N):
+        check(_lib.load().sm3_tsne_update(_ptr(F), N, float(exaggeration), float(momentum), float(lr), _ptr(y), _ptr(update),
+                                          _ptr(gains), _ptr(out), _stream()), "sm3_tsne_update")
+
+
+def tsne_kl(P, y, F, rows, out):
+    """out [2] float64 = (KL(P || Q) of the map y, Z), from F = tsne_forces(P, y); rows [N] float64 is scratch (sm3_tsne_kl)."""
+    _chk(P, torch.float32, "P"); _chk(y, torch.float32, "y"); _chk(F, torch.float64, "F")
+    _chk(rows, torch.float64, "rows"); _chk(out, torch.float64, "out")
+    N = y.shape[0]
+    _tsne_state("tsne_kl", N, P, y, F)
+    if tuple(rows.shape) != (N,) or out.numel() != 2:
+        raise ValueError(f"tsne_kl: rows [{N}] and out [2]")
+    with _prof("tsne_kl", 0.0, 4.0 * N * N):
+        check(_lib.load().sm3_tsne_kl(_ptr(P), _ptr(y), _ptr(F), N, _ptr(rows), _ptr(out), _stream()), "sm3_tsne_kl")
+
+
 CALIB_MAX_BINS = 64
 CALIB_BINNINGS = ("width", "mass")
 

@@ -93,28 +93,34 @@ def load_embeddings(path):
     return d
 
 
-def main(argv=None):
-    parser = get_parser()
-    args = parser.parse_args(argv)
-    retrieval.check_flags(args, "backbone_retrieval")
-    from src.utils.misc import ignored_line, require_data
-    real = require_data(args, "backbone_retrieval")
+def check_checkpoint(args, real, who="backbone_retrieval"):
+    """The refusals about --pretrain-path: real data needs a checkpoint, and a named checkpoint must exist."""
     if real and not (args.pretrain_path and os.path.isfile(args.pretrain_path)):
-        raise SystemExit(f"backbone_retrieval: no checkpoint at --pretrain-path {args.pretrain_path!r}: a report on real data is "
+        raise SystemExit(f"{who}: no checkpoint at --pretrain-path {args.pretrain_path!r}: a report on real data is "
                          "a report of a pre-trained model")
     if args.pretrain_path and not os.path.isfile(args.pretrain_path):
-        raise SystemExit(f"backbone_retrieval: no checkpoint at --pretrain-path {args.pretrain_path!r}")
-    if args.against and not os.path.isfile(args.against):
-        raise SystemExit(f"backbone_retrieval: --against {args.against} does not exist")
+        raise SystemExit(f"{who}: no checkpoint at --pretrain-path {args.pretrain_path!r}")
+
+
+def count_cases(args, real, who="backbone_retrieval", least=1, most=None):
+    """The number of held-out cases these flags embed; SystemExit outside least .. most (MAX_CASES by default)."""
+    most = retrieval.MAX_CASES if most is None else most
     if real:
         from src.utils.data.datasets import read_split
         N = len(read_split(args.data_path, "test")[2])
     else:
         if args.val_steps < 1 or args.batch_size < 1:
-            raise SystemExit("backbone_retrieval: --val-steps and -b must be positive")
+            raise SystemExit(f"{who}: --val-steps and -b must be positive")
         N = args.val_steps * args.batch_size
-    if not 1 <= N <= retrieval.MAX_CASES:
-        raise SystemExit(f"backbone_retrieval: {N} held-out cases, 1 to MAX_CASES = {retrieval.MAX_CASES} are supported")
+    if not least <= N <= most:
+        raise SystemExit(f"{who}: {N} held-out cases, {least} to MAX_CASES = {most} are supported")
+    return N
+
+
+def embed_held_out(args, parser, real):
+    """Builds the model of these flags, loads --pretrain-path, and embeds the held-out pairs on cuda:0: (z_derm, z_clinic,
+    labels [N, 8] int64 on the CPU or None for synthetic data, seconds)."""
+    from src.utils.misc import ignored_line
     model = build_model(args)
     if ignored_line(args, parser, real):
         print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
@@ -125,12 +131,14 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", 0)
     model.to(dev).eval()
+    labels = None
     if real:
         from sm3hip.augment import chain
         from sm3hip.imagestore import build_for
         from src.utils.data.sampler import eval_batches
         store = build_for(args, ["test"], dev)
         split = store.splits["test"]
+        labels = split.labels.cpu()
         aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
         pairs = ((store.augment(aug, split.derm_ids[sel], None, whole=True)[0],
                   store.augment(aug, split.clinic_ids[sel], None, whole=True)[0]) for sel in eval_batches(len(split), args.batch_size))
@@ -140,6 +148,26 @@ def main(argv=None):
     t0 = time.time()
     zd, zc = embed_all(model, pairs)
     torch.cuda.synchronize()
+    return zd, zc, labels, time.time() - t0
+
+
+def embeddings_record(zd, zc, args):
+    """What --save-embeddings stores."""
+    return {"derm": zd.cpu(), "clinic": zc.cpu(), "N": zd.shape[0], "arch": args.arch, "arch_version": args.arch_version,
+            "pretrain_path": args.pretrain_path}
+
+
+def main(argv=None):
+    parser = get_parser()
+    args = parser.parse_args(argv)
+    retrieval.check_flags(args, "backbone_retrieval")
+    from src.utils.misc import require_data
+    real = require_data(args, "backbone_retrieval")
+    check_checkpoint(args, real)
+    if args.against and not os.path.isfile(args.against):
+        raise SystemExit(f"backbone_retrieval: --against {args.against} does not exist")
+    count_cases(args, real)
+    zd, zc, _, embed_s = embed_held_out(args, parser, real)
     t1 = time.time()
     rep = retrieval.cross_modal_report(zd, zc, **retrieval.flag_settings(args))
     torch.cuda.synchronize()
@@ -147,18 +175,18 @@ def main(argv=None):
     os.makedirs(args.log_path, exist_ok=True)
     retrieval.save(rep, args.log_path)
     if args.save_embeddings:
-        torch.save({"derm": zd.cpu(), "clinic": zc.cpu(), "N": zd.shape[0], "arch": args.arch, "arch_version": args.arch_version,
-                    "pretrain_path": args.pretrain_path}, os.path.join(args.log_path, EMBEDDINGS))
+        torch.save(embeddings_record(zd, zc, args), os.path.join(args.log_path, EMBEDDINGS))
     for d in rep["directions"]:
         print(f"retrieval N={zd.shape[0]}: {retrieval.stats_line(rep[d], d)}", flush=True)
-    print(f"retrieval N={zd.shape[0]}: embedded in {t1 - t0:.2f} s ({zd.shape[0] / max(t1 - t0, 1e-9):.0f} pairs/s), report in "
+    print(f"retrieval N={zd.shape[0]}: embedded in {embed_s:.2f} s ({zd.shape[0] / max(embed_s, 1e-9):.0f} pairs/s), report in "
           f"{t2 - t1:.3f} s", flush=True)
     out = {"report": rep, "derm": zd, "clinic": zc}
     if args.against:
         other = load_embeddings(args.against)
         if tuple(other["derm"].shape[:1]) != (zd.shape[0],):
             raise SystemExit(f"backbone_retrieval: --against holds {other['derm'].shape[0]} cases, this run {zd.shape[0]}")
-        rep_b = retrieval.cross_modal_report(other["derm"].to(dev), other["clinic"].to(dev), **retrieval.flag_settings(args))
+        rep_b = retrieval.cross_modal_report(other["derm"].to(zd.device), other["clinic"].to(zd.device),
+                                             **retrieval.flag_settings(args))
         cmp = retrieval.compare(rep, rep_b)
         with open(os.path.join(args.log_path, "retrieval_compare.json"), "w") as f:
             json.dump(retrieval._plain(cmp), f, indent=1)
