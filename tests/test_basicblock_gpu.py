@@ -290,83 +290,20 @@ def test_resnet18_checkpoint_round_trip_in_the_reference_wire_format(tmp_path):
 
 
 # ---- every unit of a bf16 ResNet-18 training pass against fp64 --------------------------------------------------------
-def _basic_ref(x, P, B, p, stride, V, bn):
-    """BasicBlock.forward (reference resnet.py:91-106) on NHWC maps -> (pre-ReLU sum, block output)."""
-    from test_block_parity_gpu import _Conv
-    out = F.relu(bn(_Conv.apply(x, P[p + "conv1.weight"], stride, 1), P, B, p + "bn1", V))
-    out = bn(_Conv.apply(out, P[p + "conv2.weight"], 1, 1), P, B, p + "bn2", V)
-    if p + "downsample.0.weight" in P:
-        idn = bn(_Conv.apply(x, P[p + "downsample.0.weight"], stride, 0), P, B, p + "downsample.1", V)
-    else:
-        idn = x
-    pre = out + idn
-    return pre, F.relu(pre)
-
-
 def test_every_unit_of_a_bf16_resnet18_pass_against_fp64():
-    """Teacher forcing as in tests/test_block_parity_gpu.py: the engine runs one train-mode forward + backward of a bare
-    resnet18 with block-boundary taps (B = 128 per view, two views as one batch, 224 x 224); every unit is recomputed in
-    fp64 from the engine's own input and upstream gradient and compared per tensor with that file's bf16 bounds."""
-    from oracle import procedural
-    from sm3hip.engine import SM3Engine
-    from src.models import resnet
-    from test_block_parity_gpu import BOUNDS, _bn, _compare_unit, _ref_params, _stage, _stem_ref
-    dt, V, Bv, size = torch.bfloat16, 2, 128, 224
-    N = V * Bv
-    torch.manual_seed(5)
-    m = resnet.resnet18()
-    m.fc = torch.nn.Identity()
-    m.to(DEV).train()
-    eng = SM3Engine(m, dtype=dt, kind="encoder")
-    D = torch.device(DEV)
-    eng.prepare(D)
-    eng.refresh_weights()
-    plan = eng.branches["main"][0]
-    assert plan.basic and plan.out_dim == 512
-    imgs = [torch.from_numpy(procedural.make_images(Bv, size, 23, f"view{v}")).to(DEV) for v in range(V)]
-    dfeat = torch.randn(N, 512, generator=torch.Generator().manual_seed(29)).to(DEV)
-    buf0 = {k: b.detach().clone() for k, b in m.named_buffers()}
-    feats = torch.empty(N, 512, device=DEV)
-    ctx, taps = [], {}
-    eng.encoder_forward(plan, imgs, True, feats, None, ctx, views=V, taps=taps)
-    eng.store.flat_g.zero_()
-    eng.encoder_backward(ctx[0], dfeat.to(dt), taps=taps)
-    torch.cuda.synchronize()
-    del ctx
-    st = eng.store
-    P0 = {n: st._view(st.flat_p, n).detach() for n in st.names}
-    run = dict(P={n: (w.to(dt).double() if w.dim() == 4 else w.double()) for n, w in P0.items()},
-               grads={n: st._view(st.flat_g, n) for n in st.names}, bufs=dict(m.named_buffers()), buf0=buf0)
-    lim = BOUNDS["bf16"]
-    rep, fails = {}, []
+    """Teacher forcing as in tests/test_block_parity_gpu.py (tests/parity_harness.py): the engine runs one train-mode forward
+    + backward of a bare resnet18 with block-boundary taps (B = 128 per view, two views as one batch, 224 x 224); every unit
+    is recomputed in fp64 from the engine's own input and upstream gradient and compared per tensor with that file's bf16
+    bounds."""
+    import parity_harness as H
+    from test_block_parity_gpu import BOUNDS
+    run = H.engine_run("resnet18", torch.bfloat16, 256, 2, 224, 224, DEV)
+    plan, taps = run["plan"], run["taps"]
+    assert plan.basic and plan.out_dim == 512 and run["views_ran"] == 2
     assert len(taps["x"]) == len(taps["g"]) == len(plan.blocks) + 1 == 9
     # the stage entries' data gradients came out of the fused (0, 0)-class launch: masked by the previous block's ReLU
     assert [taps["g_pre_relu"][i] for i in (2, 4, 6)] == [True, True, True]
-
-    def hwc(t):
-        hw = t.shape[0] // N
-        h = int(round(hw ** 0.5))
-        return t.double().view(N, h, hw // h, t.shape[1])
-
-    names = ["conv1.weight", "bn1.weight", "bn1.bias"]
-    P, B = _ref_params(run, "bn1.", names)
-    out = _stem_ref(torch.cat(imgs, 0).to(dt).double(), P, B, V)
-    out.backward(hwc(taps["g"][0]))
-    _compare_unit(run, dt, "", "stem", names, out.detach(), hwc(taps["x"][0]), None, None, P, B, V, rep, fails, lim)
-    del out, P, B
-    for bi, blk in enumerate(plan.blocks):
-        prefix = blk["c1"].name[: -len("conv1")]
-        names = [n for n in run["P"] if n.startswith(prefix)]
-        P, B = _ref_params(run, prefix, names)
-        x = hwc(taps["x"][bi]).requires_grad_(True)
-        pre, out = _basic_ref(x, P, B, prefix, blk["c1"].stride, V, _bn)
-        (pre if taps["g_pre_relu"][bi + 1] else out).backward(hwc(taps["g"][bi + 1]))
-        dx = x.grad
-        if taps["g_pre_relu"][bi]:
-            dx = dx * (x.detach() > 0)
-        _compare_unit(run, dt, prefix, _stage(prefix), names, out.detach(), hwc(taps["x"][bi + 1]), dx,
-                      hwc(taps["g"][bi]), P, B, V, rep, fails, lim)
-        del x, pre, out, dx, P, B
+    rep, _, fails = H.check_run(run, "resnet18-bf16-2x128-224", base=BOUNDS["bf16"], restate=False)
     print("\nresnet18 bf16 2x128 224: " + "; ".join(
         f"{s}: out rel {r['out_rel'][0]:.2e}, grad cos {r['g_cos'][0]:.6f} ({r['g_cos'][1]}), rel {r['g_rel'][0]:.2e}"
         for s, r in rep.items()))
