@@ -923,6 +923,30 @@ int sm3_retrieval_counts(const uint32_t* bits, int N, const int32_t* ks, int L, 
                          int point, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Seven-point checklist report: the integer counts behind "melanoma by checklist score" -- the joint table of the predicted
+ * score, the annotated score and the diagnosis, and the AUROC counts of three continuous rankings -- for the point estimate and
+ * for case-resampling bootstrap replicates (csrc/checklist.hip, sm3hip/checklist.py; ABI 9, additive).
+ * N cases.  packed [N] int32 = shat | sstar << 4 | mel << 8: shat / sstar = the checklist score (0 .. 10) of the predicted / the
+ * annotated criteria, mel = 1 iff the case is a melanoma (bits above the ninth are ignored, a score above 10 counts as 10).
+ * order, gs, ge [3][N] int32: three rankings as sm3_report_counts' (ascending, stable, gs / ge = first and one-past-last sorted
+ * position of a position's tie group).  With integer case multiplicities m[n] >= 0, sum m = N:
+ *   J[shat][sstar][mel] = sum of m over the cases with that triple (11 x 11 x 2 = 242 entries, mel fastest);
+ *   per ranking, with "positive" = melanoma: S[j] = sum of m over the negatives at positions < j,
+ *   A2 = sum over positive j of m_j * (S[gs[j]] + S[ge[j]]),  P = sum of m over the positives,  Q = N - P.
+ * sm3_checklist_counts: out [c][sm3_checklist_record() = 251] int64 = (J (242), 3 x (A2, P, Q)) for replicates r = r0 .. r0 + c -
+ *   1; one workgroup per (replicate, part) -- part 0 the table, parts 1 .. 3 the rankings -- for a launch of at most 256
+ *   replicates, one workgroup per replicate beyond; both write the same integers, every entry of every record.  point != 0: m =
+ *   1 everywhere, c must be 1, no random words.  Otherwise m_r is the multiplicity vector of sm3_report_counts, exactly
+ *   (Philox4x32-10, key = the seed, counter (d / 4, r, 0, 2), case (w * N) >> 32): with one seed, replicate r of the five reports
+ *   resamples the same cases.  1 <= N <= sm3_report_max_cases(), c >= 1, 0 <= r0, r0 + c <= 2^32; SM3_EINVAL otherwise, before
+ *   anything is launched; out 8-byte aligned (SM3_EALIGN).  Entries of order are clamped to N - 1 and of gs / ge to N: no input
+ *   can make an access leave its array.  Integers only, no float anywhere: equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_checklist_record(void);
+int sm3_checklist_counts(const int* packed, const int* order, const int* gs, const int* ge, int64_t* out, int N, uint64_t seed,
+                         int64_t r0, int c, int point, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Exact t-SNE maps of embeddings (csrc/tsne.hip, sm3hip/tsne.py; ABI 9, additive).  N points, 4 <= N <=
  * sm3_tsne_max_points() = 16384; every function refuses a null pointer or an N outside that range with SM3_EINVAL before anything
  * is launched, and a float / double pointer that is not 4 / 8-byte aligned with SM3_EALIGN (y: 8-byte, it is read as pairs).

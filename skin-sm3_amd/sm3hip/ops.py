@@ -1469,7 +1469,7 @@ REPORT_MAX_CASES = 8192  # sm3_report_max_cases(): the multiplicities and the pr
 
 
 def _replicates_chk(who, seed, point, c, one="table"):
-    """What the four *_counts wrappers ask of the replicates (sm3hip/resample.py: the rule): a 64-bit seed, one point table."""
+    """What the five *_counts wrappers ask of the replicates (sm3hip/resample.py: the rule): a 64-bit seed, one point table."""
     if not 0 <= seed < 2 ** 64:
         raise ValueError(f"{who}: seed must fit 64 bits")
     if point and c != 1:
@@ -1714,6 +1714,31 @@ def operating_counts(order, gs, ge, targets, colmap, sigma, rho, fixpos, out, se
                                                _ptr(sigma) if Ls else None, _ptr(rho) if Lr else None, _ptr(fixpos) if Lt else None,
                                                _ptr(out), N, T, K, Ls, Lr, Lt, seed, int(r0), c, int(bool(point)), _stream()),
               "sm3_operating_counts")
+
+
+CHECKLIST_RECORD = 242 + 3 * 3  # sm3_checklist_record(): the joint table J[11][11][2], then (A2, P, Q) of three rankings
+
+
+def checklist_counts(packed, order, gs, ge, out, seed, r0, point=False):
+    """out [c, 251] int64 = (J[shat][sstar][mel] (242), 3 x (A2, P, Q)) for bootstrap replicates r0 .. r0 + c - 1, or for the point
+    estimate (point: c = 1, every case once) (sm3_checklist_counts).  packed [N] int32 = shat | sstar << 4 | mel << 8 (scores in
+    0 .. 10); order, gs, ge [3, N] int32: three rankings as report.ranking forms them; "positive" = mel."""
+    for t, n in ((packed, "packed"), (order, "order"), (gs, "gs"), (ge, "ge")):
+        _chk(t, torch.int32, n)
+    _chk(out, torch.int64, "out")
+    if packed.dim() != 1 or order.dim() != 2 or out.dim() != 2:
+        raise ValueError("checklist_counts: packed [N], order, gs, ge [3, N] and out [c, 251]")
+    N = packed.shape[0]
+    c = out.shape[0]
+    if not 1 <= N <= REPORT_MAX_CASES:
+        raise ValueError(f"checklist_counts: {N} cases, 1 to {REPORT_MAX_CASES} are supported")
+    if tuple(order.shape) != (3, N) or tuple(gs.shape) != (3, N) or tuple(ge.shape) != (3, N) or \
+            tuple(out.shape) != (c, CHECKLIST_RECORD):
+        raise ValueError(f"checklist_counts: packed [N], order, gs, ge [3, N] and out [c, {CHECKLIST_RECORD}] do not match")
+    _replicates_chk("checklist_counts", seed, point, c, "record")
+    with _prof("checklist_counts", 0.0, 4.0 * (1 + 3 * 3) * N * c):
+        check(_lib.load().sm3_checklist_counts(_ptr(packed), _ptr(order), _ptr(gs), _ptr(ge), _ptr(out), N, seed, int(r0), c,
+                                               int(bool(point)), _stream()), "sm3_checklist_counts")
 
 
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):

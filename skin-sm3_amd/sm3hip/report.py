@@ -80,11 +80,11 @@ def check_inputs(preds, targets, who="evaluation_report"):
     return N
 
 
-def ranking(preds, targets):
-    """The plumbing around the kernel, on the device of preds: (order, gs, ge [24, N] int32, yhat [N, 8] int32)."""
-    N = targets.shape[0]
-    dev = preds[0].device
-    score = torch.cat([torch.softmax(p.double(), dim=1).t() for p in preds], dim=0)  # [24, N]
+def rank_scores(score):
+    """score [K, N] fp64 -> (order, gs, ge [K, N] int32): each row sorted ascending and stably once, tie groups by ==, gs[j] / ge[j] =
+    first and one-past-last sorted position of position j's group."""
+    K, N = score.shape
+    dev = score.device
     s, order = torch.sort(score, dim=1, stable=True)
     idx = torch.arange(N, device=dev).expand(K, N)
     new = s[:, 1:] != s[:, :-1]
@@ -93,8 +93,14 @@ def ranking(preds, targets):
     last = torch.cat([new, edge], dim=1)   # position j closes one
     gs = torch.cummax(torch.where(first, idx, torch.zeros_like(idx)), dim=1).values
     ge = torch.cummin(torch.where(last, idx + 1, torch.full_like(idx, N)).flip(1), dim=1).values.flip(1)
+    return order.int().contiguous(), gs.int().contiguous(), ge.int().contiguous()
+
+
+def ranking(preds, targets):
+    """The plumbing around the kernel, on the device of preds: (order, gs, ge [24, N] int32, yhat [N, 8] int32)."""
+    score = torch.cat([torch.softmax(p.double(), dim=1).t() for p in preds], dim=0)  # [24, N]
     yhat = torch.stack([p.argmax(dim=1) for p in preds], dim=1)
-    return order.int().contiguous(), gs.int().contiguous(), ge.int().contiguous(), yhat.int().contiguous()
+    return (*rank_scores(score), yhat.int().contiguous())
 
 
 def averages(v):

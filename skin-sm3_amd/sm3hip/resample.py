@@ -1,11 +1,12 @@
-"""What the four case-resampling bootstrap reports share: report.py (evaluation), calibration.py, operating.py, retrieval.py.
+"""What the five case-resampling bootstrap reports share: report.py (evaluation), calibration.py, operating.py, retrieval.py,
+checklist.py.
 
-THE RESAMPLING RULE (csrc/resample.h states it for the device, DESIGN.md 8.10 in prose; the four modules point here).  Integer
+THE RESAMPLING RULE (csrc/resample.h states it for the device, DESIGN.md 8.10 in prose; the five modules point here).  Integer
 case multiplicities m[n] >= 0 with sum m = N weigh every count of a report; the point estimate has m = 1.  Replicate r makes N
 draws: draw d (0 <= d < N) is word d % 4 of Philox4x32-10 (csrc/exact_f32.h) with key = the 64-bit seed (low word first) and
 counter (d / 4, r, 0, 2) -- the last word keeps the stream apart from SmoothGrad's 0 and RISE's 1; it hits case (w * N) >> 32 in
 64-bit integers; m_r[i] = the number of draws that hit case i.  m_r is a function of (seed, r, N) alone: not of B, the chunk,
-the launch geometry or the report.  So with one seed replicate r resamples the same cases in all four reports -- their intervals
+the launch geometry or the report.  So with one seed replicate r resamples the same cases in all five reports -- their intervals
 are joint -- and in two reports of the same cases, which makes `compare` paired at no cost.
 
 Interval: per series the B replicate values sorted ascending, lo = v[i], hi = v[B - 1 - i], i = floor((B - 1) * (1 - confidence)

@@ -13,6 +13,9 @@ the reliability diagram; --calib-bins M, --calib-binning width|mass; the same bo
 --operating adds val_operating.json / .csv of the same pass (sm3hip.operating: average precision, the Youden and F1 optima,
 sensitivity at --operating-spec floors, specificity at --operating-sens floors, net benefit at --operating-decision; the same
 bootstrap replicates).
+--checklist adds val_checklist.json / .csv of the same pass (sm3hip.checklist: melanoma by the seven-point checklist score of the
+predicted criteria beside the DIAG head and the annotated score, the rule "score >= k" at --checklist-thresholds, the agreement
+of the two scores; the same bootstrap replicates).
 Any other value fine-tunes everything through the autograd bridge.
 
 `--data-name SevenPCBaseDataset --data-path DIR`: derm7pt's train and test splits decoded once into the device image store
@@ -35,7 +38,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from sm3hip import calibration, operating, report  # noqa: E402
+from sm3hip import calibration, checklist, operating, report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.baseline import Baseline  # noqa: E402
 
@@ -55,6 +58,7 @@ def get_parser(calibration_flags=True):
     if calibration_flags:
         calibration.add_flags(p)
     operating.add_flags(p)
+    checklist.add_flags(p)
     p.set_defaults(arch="resnet50", epochs=50, batch_size=128)
     return p
 
@@ -132,6 +136,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     calibration.check_flags(args)
     operating.check_flags(args)
+    checklist.check_flags(args)
     from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
     require_baseline_arch(args.arch, "backbone_eval")
     real = require_data(args, "backbone_eval")
@@ -185,6 +190,9 @@ def main(argv=None):
         if args.operating and epoch == args.epochs - 1:  # val_operating.json / .csv next to val_report.*
             opr = operating.validation_operating(va["preds"], va["targets"], args, args.log_path)
             print(f"epoch {epoch}: val {operating.stats_line(opr)}", flush=True)
+        if args.checklist and epoch == args.epochs - 1:  # val_checklist.json / .csv next to val_report.*
+            ckl = checklist.validation_checklist(va["preds"], va["targets"], args, args.log_path)
+            print(f"epoch {epoch}: val {checklist.stats_line(ckl)}", flush=True)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG (backbone_eval.py:386,405-411)
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},

@@ -12,7 +12,8 @@ frozen and in eval mode (one fused conv + BN + ReLU kernel per layer); a case's 
 become fractions p = votes / sum(votes); AUC_AVG is sm3hip.metrics.auc_avg of log p (softmax(log p) = p) and top-1 is the
 first of the stable descending order, as KNNOnlineEvaluator.predict ranks.  knn_predictions.pt goes to --log-path, and with it
 val_report.json / val_report.csv: Recall / Spec / Prec and every class's AUROC of the same log p (sm3hip.report; --bootstrap B
-adds case-resampling intervals); --operating adds val_operating.json / .csv of the same log p (sm3hip.operating).
+adds case-resampling intervals); --operating adds val_operating.json / .csv of the same log p (sm3hip.operating),
+--checklist val_checklist.json / .csv (sm3hip.checklist; --checklist-thresholds).
 `--data-name synthetic`: --steps-per-epoch batches form the bank, --val-steps batches the queries; --random-features N B D
 replaces the encoders by N bank and B query rows of unit-norm random features of width D (the kNN stage alone, at bank sizes
 no encoder pass in a test reaches).
@@ -32,7 +33,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import backbone_eval  # noqa: E402
-from sm3hip import operating, report  # noqa: E402
+from sm3hip import checklist, operating, report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.baseline import Baseline  # noqa: E402
 
@@ -69,6 +70,7 @@ def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
     operating.check_flags(args)
+    checklist.check_flags(args)
     from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
     require_baseline_arch(args.arch, "backbone_knn")
     real = require_data(args, "backbone_knn")
@@ -139,6 +141,9 @@ def main(argv=None):
     if args.operating:  # val_operating.json / .csv next to val_report.*
         opr = operating.validation_operating([p.log() for p in probs], query_t, args, args.log_path)
         print(f"knn k={args.knn_k} T={args.knn_t}: {operating.stats_line(opr)}", flush=True)
+    if args.checklist:  # val_checklist.json / .csv next to val_report.*
+        ckl = checklist.validation_checklist([p.log() for p in probs], query_t, args, args.log_path)
+        print(f"knn k={args.knn_k} T={args.knn_t}: {checklist.stats_line(ckl)}", flush=True)
     return stat
 
 

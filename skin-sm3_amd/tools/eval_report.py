@@ -29,6 +29,13 @@ example the validation split's predictions, and reports PRED.pt both at T = 1 an
 replicates, written to <name>_operating.json / .csv, and with --against the paired difference (<name>_operating_compare.json).
 With --fit-on OTHER.pt the thresholds that --operating-rule (youden, f1, spec>=X, sens>=X) picks on OTHER.pt are applied to
 PRED.pt: sens / spec / PPV / NPV at the transferred thresholds with their intervals (<name>_operating_fitted.json / .csv).
+
+    python tools/eval_report.py logs/linear/test_predictions.pt --bootstrap 2000 --checklist --checklist-thresholds 1 3
+
+--checklist adds the seven-point checklist report (sm3hip/checklist.py: melanoma by the score of the predicted criteria, beside
+the DIAG head and the score of the annotated criteria; the rule "score >= k" at --checklist-thresholds; the agreement of the two
+scores) with the SAME bootstrap replicates, written to <name>_checklist.json / .csv, and with --against the paired difference
+(<name>_checklist_compare.json).
 """
 import argparse
 import os
@@ -42,7 +49,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 
 import torch  # noqa: E402
 
-from sm3hip import calibration, operating, report, resample  # noqa: E402
+from sm3hip import calibration, checklist, operating, report, resample  # noqa: E402
 
 
 def get_parser():
@@ -54,6 +61,7 @@ def get_parser():
     report.add_flags(p)
     calibration.add_flags(p)
     operating.add_flags(p)
+    checklist.add_flags(p)
     p.add_argument("--fit-on", metavar="OTHER.pt", default=None,
                    help="fit the temperatures on this predictions file; report PRED.pt at T = 1 and at the fitted T (implies --calibration)")
     return p
@@ -113,10 +121,30 @@ def operate(args, preds, targets, kw, out, stem, dev):
     return result
 
 
+def check(args, preds, targets, kw, out, stem, dev):
+    """The --checklist part: prints the tables, writes the files, returns what it computed."""
+    if targets.shape[0] > report.MAX_CASES:
+        print(checklist.stats_line(None), flush=True)
+        return {}
+    ckw = dict(kw, **checklist.flag_settings(args))
+    ckl = checklist.checklist_report(preds, targets, **ckw)
+    print(checklist.format_table(ckl), flush=True)
+    checklist.save(ckl, out, stem + "_checklist")
+    result = {"checklist": ckl}
+    if args.against:
+        cmp = checklist.compare(ckl, checklist.checklist_report(*report.load_predictions(args.against, dev), **ckw))
+        print(f"{args.pred} - {args.against}", flush=True)
+        print(checklist.format_compare(cmp), flush=True)
+        resample.write_json(cmp, os.path.join(out, stem + "_checklist_compare.json"))
+        result["checklist_compare"] = cmp
+    return result
+
+
 def main(argv=None):
     args = get_parser().parse_args(argv)
     calibration.check_flags(args)
     operating.check_flags(args)
+    checklist.check_flags(args)
     out = args.out or os.path.dirname(os.path.abspath(args.pred))
     stem = os.path.splitext(os.path.basename(args.pred))[0]
     kw = dict(bootstrap=args.bootstrap, confidence=args.confidence, seed=args.bootstrap_seed, chunk=args.chunk)
@@ -139,6 +167,8 @@ def main(argv=None):
         result.update(calibrate(args, preds, targets, kw, out, stem, dev))
     if args.operating:
         result.update(operate(args, preds, targets, kw, out, stem, dev))
+    if args.checklist:
+        result.update(check(args, preds, targets, kw, out, stem, dev))
     return result
 
 

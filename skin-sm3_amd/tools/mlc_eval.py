@@ -6,6 +6,7 @@ validation pass, the reference's Recall / Spec / Prec of the 8 labels (sm3hip.re
 val_report.json / val_report.csv (--bootstrap B: with intervals) and, under real data, val_predictions.pt to --log-path.
 --calibration adds val_calibration.json / .csv of that pass at T = 1 (sm3hip.calibration; --calib-bins, --calib-binning).
 --operating adds val_operating.json / .csv of that pass (sm3hip.operating; --operating-spec, --operating-sens, --operating-decision).
+--checklist adds val_checklist.json / .csv of that pass (sm3hip.checklist; --checklist-thresholds).
 
     python tools/mlc_eval.py --data-name synthetic -a resnet50 -b 128 -lr 1e-3 --epochs 2 --mlc-proj v4 \
         --mlc-proj-dim 512 --num-heads 1 --sa-dim-ff 128 --sa-dropout 0.1 --finetune projector \
@@ -36,7 +37,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from sm3hip import calibration, operating, report  # noqa: E402
+from sm3hip import calibration, checklist, operating, report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.projector import build_mlc_projectors  # noqa: E402
 from src.models.simclr import SimCLRSkinV32  # noqa: E402
@@ -91,6 +92,7 @@ def get_parser():
     report.add_flags(p)
     calibration.add_flags(p)
     operating.add_flags(p)
+    checklist.add_flags(p)
     p.set_defaults(arch="resnet50", batch_size=128, finetune="projector", pretrain_path="", log_path="./logs/mlc_eval")
     return p
 
@@ -161,6 +163,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     calibration.check_flags(args)
     operating.check_flags(args)
+    checklist.check_flags(args)
     from src.utils.misc import ignored_line, require_data, require_mlc_arch, require_mlc_proj
     require_mlc_arch(args.arch, "mlc_eval")
     require_mlc_proj(args, "mlc_eval")
@@ -239,6 +242,9 @@ def main(argv=None):
         if args.operating and epoch == args.epochs - 1:  # val_operating.json / .csv next to val_report.*
             opr = operating.validation_operating(kept["preds"], kept["targets"], args, args.log_path)
             print(f"epoch {epoch}: val {operating.stats_line(opr)}", flush=True)
+        if args.checklist and epoch == args.epochs - 1:  # val_checklist.json / .csv next to val_report.*
+            ckl = checklist.validation_checklist(kept["preds"], kept["targets"], args, args.log_path)
+            print(f"epoch {epoch}: val {checklist.stats_line(ckl)}", flush=True)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},
