@@ -980,6 +980,47 @@ int sm3_tsne_update(const double* F, int N, double exaggeration, double momentum
                     double* out, void* stream);
 int sm3_tsne_kl(const float* P, const float* y, const double* F, int N, double* rows, double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * L2-regularised multinomial logistic regression on cached features (csrc/logreg.hip, sm3hip/logreg.py; ABI 9,
+ * additive).  X [N][D] f32 row-major, 1 <= N <= sm3_logreg_max_rows() = 16384, 1 <= D <= 4096; targets [N][8] int32; weights
+ * [R][N] f64, all >= 0; table [P][4] int32 = (label, weight row, classes n_t of the label, 0) and Cs [P] f64 name the P problems.
+ * Problem p: S = sum_i s_i over the classes of positive total weight ("present"), lambda = 1 / (C S),
+ *   F(W, b) = (1 / S) sum_i s_i CE(softmax(W x_i + b), y_i) + (lambda / 2) |W|^2, the softmax over the present classes.
+ * Per-class arrays have room for 8 classes: W, gW, coef [P][8][D], b, gb, intercept [P][8], logits [P][Q][8], all f64; rows
+ * c >= n_t are written as 0.  One 256-thread workgroup owns one problem: its result does not depend on the other problems of the
+ * launch (each problem reads X itself, on vector fma: there is no batched product over the problems).  fp64 throughout, X
+ * widened on load, no atomics, every sum in an order that (N, D, n_t) fix (csrc/logreg.hip states
+ * them).  Every function refuses null pointers, sizes outside the caps and a workspace that is too small with SM3_EINVAL and a
+ * misaligned pointer (4 bytes for f32 / int32, 8 for f64) with SM3_EALIGN before anything is launched; a table entry out of
+ * range that reaches a kernel all the same is not followed (status 4, F = NaN).
+ * sm3_logreg_workspace: the f64 elements of workspace ONE problem needs, of the fit (fit != 0) or of value_grad.
+ * sm3_logreg_check_host: HOST arrays (what the device arrays will hold; n_classes [8]): SM3_EINVAL for a label outside [0, 8), a
+ *   weight row outside [0, R), n_t that is not n_classes[label], a C that is not positive and finite, a class index of a used
+ *   label outside [0, n_t), a weight that is negative or not finite.  Launches nothing, touches no device.
+ * sm3_logreg_value_grad: F [P], gW, gb at the given W, b (an intercept of a class that is not present is not read).  A problem
+ *   of total weight 0 gives zeros.
+ * sm3_logreg_fit: L-BFGS (history 10) from zero until |grad F|_inf <= gtol or max_iter iterations.  A class that is not present
+ *   gets coefficient row 0 and intercept -inf.  info [P][2] int32 = (status, iterations): 0 converged, 1 max_iter, 2 no step found,
+ *   3 fewer than two present classes (nothing fitted), 4 bad table entry; res [P][2] f64 = (F, |grad F|_inf) at the returned point.
+ *   A launch runs at most iters >= 1 iterations of every problem and saves each solver's state in ws; status 5 = not finished:
+ *   call again with resume = 1 and the same arguments until no 5 is left (resume = 0 starts from zero).  The result does not
+ *   depend on iters: the launches only bound the time one of them can take.
+ * sm3_logreg_predict: logits[p][q][c] = coef[p][c] . Xq[q] + intercept[p][c] for c < nts[p] (k in the order of the fit's
+ *   logits), Q <= 2^24, P <= 65535 a launch; a row's logits do not depend on the other rows.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_logreg_max_rows(void);
+int sm3_logreg_workspace(int N, int D, int fit, int64_t* doubles_per_problem);
+int sm3_logreg_check_host(const int32_t* targets, const double* weights, const int32_t* table, const double* Cs,
+                          const int32_t* n_classes, int N, int R, int P);
+int sm3_logreg_value_grad(const float* X, const int32_t* targets, const double* weights, const int32_t* table, const double* Cs,
+                          const double* W, const double* b, int N, int D, int R, int P, double* ws, int64_t ws_doubles, double* F,
+                          double* gW, double* gb, void* stream);
+int sm3_logreg_fit(const float* X, const int32_t* targets, const double* weights, const int32_t* table, const double* Cs, int N,
+                   int D, int R, int P, double gtol, int max_iter, int resume, int iters, double* ws, int64_t ws_doubles, double* coef,
+                   double* intercept, int32_t* info, double* res, void* stream);
+int sm3_logreg_predict(const float* Xq, const double* coef, const double* intercept, const int32_t* nts, int Q, int D, int P,
+                       double* logits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,12 @@ SIGNATURES = {
     "sm3_tsne_forces": [_P, _P, _I, _P, _P],
     "sm3_tsne_update": [_P, _I, _D, _D, _D, _P, _P, _P, _P, _P],
     "sm3_tsne_kl": [_P, _P, _P, _I, _P, _P, _P],
+    "sm3_logreg_max_rows": [],
+    "sm3_logreg_workspace": [_I, _I, _I, _P],
+    "sm3_logreg_check_host": [_P, _P, _P, _P, _P, _I, _I, _I],
+    "sm3_logreg_value_grad": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P],
+    "sm3_logreg_fit": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P],
+    "sm3_logreg_predict": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
 }
 
 _lib = None

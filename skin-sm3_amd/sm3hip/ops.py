@@ -1642,6 +1642,125 @@ def tsne_kl(P, y, F, rows, out):
         check(_lib.load().sm3_tsne_kl(_ptr(P), _ptr(y), _ptr(F), N, _ptr(rows), _ptr(out), _stream()), "sm3_tsne_kl")
 
 
+LOGREG_MAX_ROWS = 16384  # sm3_logreg_max_rows()
+LOGREG_MAX_DIM = 4096
+LOGREG_MAX_CLASSES = 8   # the stride of every per-class array of csrc/logreg.hip; n_t <= 8
+
+
+def _logreg_shape(who, N, D):
+    if not 1 <= N <= LOGREG_MAX_ROWS or not 1 <= D <= LOGREG_MAX_DIM:
+        raise ValueError(f"{who}: X [{N}, {D}], at most [{LOGREG_MAX_ROWS}, {LOGREG_MAX_DIM}] and at least [1, 1] are supported")
+
+
+def logreg_workspace(N, D, fit=True):
+    """The float64 elements of workspace one problem needs (sm3_logreg_workspace)."""
+    _logreg_shape("logreg_workspace", N, D)
+    out = C.c_int64(0)
+    check(_lib.load().sm3_logreg_workspace(int(N), int(D), int(bool(fit)), C.byref(out)), "sm3_logreg_workspace")
+    return int(out.value)
+
+
+def logreg_check_host(targets, weights, table, Cs, n_classes):
+    """The refusals that read the problem data, on HOST tensors before anything is uploaded or launched (sm3_logreg_check_host):
+    targets [N, 8] int32, weights [R, N] float64, table [P, 4] int32 = (label, weight row, n_t, 0), Cs [P] float64."""
+    for t, dt, n in ((targets, torch.int32, "targets"), (weights, torch.float64, "weights"), (table, torch.int32, "table"),
+                     (Cs, torch.float64, "Cs")):
+        if not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"logreg_check_host: {n} must be a contiguous host tensor of {dt}")
+    n_classes = [int(c) for c in n_classes]
+    if targets.dim() != 2 or targets.shape[1] != LOGREG_MAX_CLASSES or len(n_classes) != LOGREG_MAX_CLASSES:
+        raise ValueError("logreg_check_host: targets [N, 8] and the classes of 8 labels")
+    N, P = targets.shape[0], table.shape[0]
+    if weights.dim() != 2 or weights.shape[1] != N or weights.shape[0] < 1:
+        raise ValueError(f"logreg_check_host: weights [R >= 1, {N}]")
+    if table.dim() != 2 or table.shape[1] != 4 or tuple(Cs.shape) != (P,) or P < 1:
+        raise ValueError("logreg_check_host: table [P >= 1, 4] and Cs [P]")
+    if not 1 <= N <= LOGREG_MAX_ROWS:
+        raise ValueError(f"logreg_check_host: {N} rows, 1 to {LOGREG_MAX_ROWS} are supported")
+    rc = _lib.load().sm3_logreg_check_host(_ptr(targets), _ptr(weights), _ptr(table), _ptr(Cs), (C.c_int32 * 8)(*n_classes),
+                                           N, weights.shape[0], P)
+    if rc != 0:
+        raise ValueError("logreg: a class index outside [0, n_t), a negative or non-finite weight, a C that is not positive and "
+                         "finite, or a problem that names no label / weight row (sm3_logreg_check_host)")
+
+
+def _logreg_problem_tensors(who, X, targets, weights, table, Cs):
+    _chk(X, torch.float32, "X"); _chk(targets, torch.int32, "targets"); _chk(weights, torch.float64, "weights")
+    _chk(table, torch.int32, "table"); _chk(Cs, torch.float64, "Cs")
+    if X.dim() != 2 or targets.dim() != 2 or weights.dim() != 2 or table.dim() != 2 or Cs.dim() != 1:
+        raise ValueError(f"{who}: X [N, D], targets [N, 8], weights [R, N], table [P, 4] and Cs [P]")
+    N, D = X.shape
+    _logreg_shape(who, N, D)
+    R, P = weights.shape[0], table.shape[0]
+    if tuple(targets.shape) != (N, LOGREG_MAX_CLASSES) or weights.shape[1] != N or R < 1 or P < 1 or \
+            tuple(table.shape) != (P, 4) or tuple(Cs.shape) != (P,):
+        raise ValueError(f"{who}: X [{N}, {D}], targets [{N}, 8], weights [R, {N}], table [P, 4] and Cs [P] do not match")
+    return N, D, R, P
+
+
+def logreg_value_grad(X, targets, weights, table, Cs, W, b, ws, F, gW, gb):
+    """F [P], gW [P, 8, D], gb [P, 8] float64 = value and gradient of the P problems of (table, Cs) at W [P, 8, D], b [P, 8]
+    (sm3_logreg_value_grad); ws: float64 workspace of at least P * logreg_workspace(N, D, fit=False) elements."""
+    N, D, R, P = _logreg_problem_tensors("logreg_value_grad", X, targets, weights, table, Cs)
+    for t, n in ((W, "W"), (b, "b"), (ws, "ws"), (F, "F"), (gW, "gW"), (gb, "gb")):
+        _chk(t, torch.float64, n)
+    K = LOGREG_MAX_CLASSES
+    if tuple(W.shape) != (P, K, D) or tuple(gW.shape) != (P, K, D) or tuple(b.shape) != (P, K) or tuple(gb.shape) != (P, K) or \
+            tuple(F.shape) != (P,) or ws.numel() < P * logreg_workspace(N, D, False):
+        raise ValueError(f"logreg_value_grad: W, gW [{P}, {K}, {D}], b, gb [{P}, {K}], F [{P}] and the workspace do not match")
+    with _prof("logreg_value_grad", 4.0 * N * D * K * P, 4.0 * N * D * P):
+        check(_lib.load().sm3_logreg_value_grad(_ptr(X), _ptr(targets), _ptr(weights), _ptr(table), _ptr(Cs), _ptr(W), _ptr(b),
+                                                N, D, R, P, _ptr(ws), ws.numel(), _ptr(F), _ptr(gW), _ptr(gb), _stream()),
+              "sm3_logreg_value_grad")
+
+
+LOGREG_RUNNING = 5  # info status of a problem whose launch ran out of its iterations
+
+
+def logreg_fit(X, targets, weights, table, Cs, gtol, max_iter, ws, coef, intercept, info, res, resume=False, iters=None):
+    """The minimisers of the P problems: coef [P, 8, D], intercept [P, 8] float64, info [P, 2] int32 = (status, iterations), res
+    [P, 2] float64 = (F, |grad F|_inf) (sm3_logreg_fit); ws: at least P * logreg_workspace(N, D) float64 elements.  ONE launch
+    of at most `iters` iterations a problem (None: max_iter); a problem it leaves unfinished has status LOGREG_RUNNING and goes
+    on in a call with resume=True and the same tensors."""
+    N, D, R, P = _logreg_problem_tensors("logreg_fit", X, targets, weights, table, Cs)
+    for t, n in ((ws, "ws"), (coef, "coef"), (intercept, "intercept"), (res, "res")):
+        _chk(t, torch.float64, n)
+    _chk(info, torch.int32, "info")
+    K = LOGREG_MAX_CLASSES
+    if tuple(coef.shape) != (P, K, D) or tuple(intercept.shape) != (P, K) or tuple(info.shape) != (P, 2) or \
+            tuple(res.shape) != (P, 2) or ws.numel() < P * logreg_workspace(N, D, True):
+        raise ValueError(f"logreg_fit: coef [{P}, {K}, {D}], intercept [{P}, {K}], info, res [{P}, 2] and the workspace do not match")
+    if isinstance(gtol, bool) or not isinstance(gtol, (int, float)) or not 0 <= gtol < float("inf"):
+        raise ValueError(f"logreg_fit: gtol must be a finite number >= 0, got {gtol!r}")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or not 0 <= max_iter < 2 ** 31:
+        raise ValueError(f"logreg_fit: max_iter must be an integer >= 0, got {max_iter!r}")
+    iters = max(max_iter, 1) if iters is None else iters
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters < 2 ** 31:
+        raise ValueError(f"logreg_fit: iters must be an integer >= 1, got {iters!r}")
+    with _prof("logreg_fit", 0.0, 0.0):
+        check(_lib.load().sm3_logreg_fit(_ptr(X), _ptr(targets), _ptr(weights), _ptr(table), _ptr(Cs), N, D, R, P, float(gtol),
+                                         max_iter, int(bool(resume)), iters, _ptr(ws), ws.numel(), _ptr(coef), _ptr(intercept), _ptr(info), _ptr(res),
+                                         _stream()), "sm3_logreg_fit")
+
+
+def logreg_predict(Xq, coef, intercept, nts, logits):
+    """logits [P, Q, 8] float64 of the rows Xq [Q, D] float32 under coef [P, 8, D], intercept [P, 8]; nts [P] int32 = the classes
+    of each problem (sm3_logreg_predict)."""
+    _chk(Xq, torch.float32, "Xq"); _chk(coef, torch.float64, "coef"); _chk(intercept, torch.float64, "intercept")
+    _chk(nts, torch.int32, "nts"); _chk(logits, torch.float64, "logits")
+    if Xq.dim() != 2 or coef.dim() != 3:
+        raise ValueError("logreg_predict: Xq [Q, D] and coef [P, 8, D]")
+    (Q, D), P, K = Xq.shape, coef.shape[0], LOGREG_MAX_CLASSES
+    if not 1 <= Q <= 2 ** 24 or not 1 <= D <= LOGREG_MAX_DIM or not 1 <= P <= 65535:
+        raise ValueError(f"logreg_predict: Q in [1, 2^24], D in [1, {LOGREG_MAX_DIM}] and P in [1, 65535] a launch")
+    if tuple(coef.shape) != (P, K, D) or tuple(intercept.shape) != (P, K) or tuple(nts.shape) != (P,) or \
+            tuple(logits.shape) != (P, Q, K):
+        raise ValueError(f"logreg_predict: coef [{P}, {K}, {D}], intercept [{P}, {K}], nts [{P}] and logits [{P}, {Q}, {K}] do not match")
+    with _prof("logreg_predict", 2.0 * Q * D * K * P, 4.0 * Q * D * P):
+        check(_lib.load().sm3_logreg_predict(_ptr(Xq), _ptr(coef), _ptr(intercept), _ptr(nts), Q, D, P, _ptr(logits), _stream()),
+              "sm3_logreg_predict")
+
+
 CALIB_MAX_BINS = 64
 CALIB_BINNINGS = ("width", "mass")
 

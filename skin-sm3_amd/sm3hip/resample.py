@@ -62,6 +62,31 @@ def safe_div(num, den):
     return out, den == 0
 
 
+# ---- the Philox stream on the host ---------------------------------------------------------------------------------------------
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC 2011; csrc/exact_f32.h on the device) on uint64 arrays holding 32-bit words -> the four
+    output words."""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & _M32 for c in np.broadcast_arrays(c0, c1, c2, c3))
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        n0, n2 = (p1 >> np.uint64(32)) ^ c1 ^ k0, (p0 >> np.uint64(32)) ^ c3 ^ k1
+        c1, c3, c0, c2 = p1 & _M32, p0 & _M32, n0, n2
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return c0, c1, c2, c3
+
+
+def philox_words(n, seed, r, stream):
+    """n 32-bit words (uint64 array): word d is word d % 4 of the call with key = the 64-bit seed (low word first) and counter
+    (d / 4, r, 0, stream).  Streams in use: 0 SmoothGrad, 1 RISE, 2 the bootstrap draws above, 3 and 4 sm3hip/logreg.py."""
+    q = np.arange((n + 3) // 4, dtype=np.uint64)
+    w = philox4x32_10(q, np.uint64(r), np.uint64(0), np.uint64(stream), seed & 0xFFFFFFFF, seed >> 32)
+    return np.stack(w, axis=1).reshape(-1)[:n]
+
+
 # ---- the device and the replicate loop ----------------------------------------------------------------------------------------
 def device_for(preds, who):
     """The device a report of `preds` runs on: that of preds[0] if it is a GPU's, else the current GPU."""
