@@ -988,7 +988,7 @@ int sm3_tsne_kl(const float* P, const float* y, const double* F, int N, double* 
  *   F(W, b) = (1 / S) sum_i s_i CE(softmax(W x_i + b), y_i) + (lambda / 2) |W|^2, the softmax over the present classes.
  * Per-class arrays have room for 8 classes: W, gW, coef [P][8][D], b, gb, intercept [P][8], logits [P][Q][8], all f64; rows
  * c >= n_t are written as 0.  One 256-thread workgroup owns one problem: its result does not depend on the other problems of the
- * launch (each problem reads X itself, on vector fma: there is no batched product over the problems).  fp64 throughout, X
+ * launch (each problem reads X itself, on vector fma; the batched products are the lockstep solver's, below).  fp64 throughout, X
  * widened on load, no atomics, every sum in an order that (N, D, n_t) fix (csrc/logreg.hip states
  * them).  Every function refuses null pointers, sizes outside the caps and a workspace that is too small with SM3_EINVAL and a
  * misaligned pointer (4 bytes for f32 / int32, 8 for f64) with SM3_EALIGN before anything is launched; a table entry out of
@@ -1020,6 +1020,48 @@ int sm3_logreg_fit(const float* X, const int32_t* targets, const double* weights
                    double* intercept, int32_t* info, double* res, void* stream);
 int sm3_logreg_predict(const float* Xq, const double* coef, const double* intercept, const int32_t* nts, int Q, int D, int P,
                        double* logits, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The lockstep solver of the same problems (csrc/logreg.hip; ABI 9, additive): the problems of a call go through
+ * every L-BFGS iteration side by side, and the two passes over X of an iteration are two batched products on
+ * v_mfma_f64_16x16x4_f64 that all problems share.  Problems are COLUMNS: column j is one (problem, class) pair named by
+ * cols [ncols] int32, cols[j] = 8 p + c, 1 <= ncols <= 8 P, the host lists the classes c < n_t of every problem; an entry
+ * outside [0, 8 P) is not followed.  P <= 65535 a call.  Arrays and the caps are those above.
+ * The orders of the sums depend on (N, D) alone -- not on P, a column's place or neighbours, the chunk, the calls, or which
+ * problems are live:
+ *   over features (logits):  groups of 16 features ascending; in a group four instructions j = 0 .. 3, instruction j adding the
+ *                            features k0 + j, k0 + 4 + j, k0 + 8 + j, k0 + 12 + j; the intercept is added last;
+ *   over rows (gradient):    slabs of sm3_logreg_lockstep_slab() = 2048 rows; in a slab groups of 16 rows ascending, the four
+ *                            instructions of a group as above; the slabs' sums are stored plainly and added in slab order;
+ *   gb and every scalar sum: thread t of 256 adds terms t, t + 256, ... ascending, then the halving tree.
+ * No atomics; tails are zero operands; a row of weight 0 has residual exactly 0.
+ * sm3_logreg_lockstep_workspace: the f64 elements one call of the fit (fit != 0) or of value_grad_lockstep needs for P problems in
+ *   ncols columns (per-problem state, the slabs' partial sums, the modes).
+ * sm3_logreg_batch_logits: Z[p][i][c] = sum_k X[i][k] V[p][c][k] + vb[p][c] for every column whose problem has active[p] != 0;
+ *   V [P][8][D], vb [P][8] or null, Z [P][N][8].  Nothing of a problem with active[p] = 0 is written.
+ * sm3_logreg_batch_grad: G[p][c][k] = sum_i Rm[p][i][c] X[i][k], gb[p][c] = sum_i Rm[p][i][c]; Rm [P][N][8], G [P][8][D], gb
+ *   [P][8]; ws: at least ceil(N / 2048) * ncols * D f64 elements.  Nothing of a problem with active[p] = 0 is written.
+ * sm3_logreg_value_grad_lockstep: what sm3_logreg_value_grad computes, through the two products.
+ * sm3_logreg_fit_lockstep: what sm3_logreg_fit solves, by the same rules (history 10, the slope-bracketing line search, the
+ *   certificate on fresh logits, statuses 0 .. 5).  A call enqueues iters (1 .. 1024) iterations of four steps -- per-problem
+ *   direction kernel, logits product, per-problem line-search kernel, gradient product -- and returns; every problem's state lies
+ *   in ws between two launches, a finished problem is not touched again.  Status 5 = not finished: call again with resume = 1.
+ *   The result depends neither on iters nor on how the problems are split over calls.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_logreg_lockstep_slab(void);
+int sm3_logreg_lockstep_workspace(int N, int D, int P, int ncols, int fit, int64_t* doubles);
+int sm3_logreg_batch_logits(const float* X, const double* V, const double* vb, const int32_t* cols, const int32_t* active, int N,
+                            int D, int P, int ncols, double* Z, void* stream);
+int sm3_logreg_batch_grad(const float* X, const double* Rm, const int32_t* cols, const int32_t* active, int N, int D, int P,
+                          int ncols, double* ws, int64_t ws_doubles, double* G, double* gb, void* stream);
+int sm3_logreg_value_grad_lockstep(const float* X, const int32_t* targets, const double* weights, const int32_t* table,
+                                   const double* Cs, const int32_t* cols, const double* W, const double* b, int N, int D, int R,
+                                   int P, int ncols, double* ws, int64_t ws_doubles, double* F, double* gW, double* gb,
+                                   void* stream);
+int sm3_logreg_fit_lockstep(const float* X, const int32_t* targets, const double* weights, const int32_t* table, const double* Cs,
+                            const int32_t* cols, int N, int D, int R, int P, int ncols, double gtol, int max_iter, int resume,
+                            int iters, double* ws, int64_t ws_doubles, double* coef, double* intercept, int32_t* info, double* res,
+                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -204,6 +204,12 @@ SIGNATURES = {
     "sm3_logreg_value_grad": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P],
     "sm3_logreg_fit": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P],
     "sm3_logreg_predict": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "sm3_logreg_lockstep_slab": [],
+    "sm3_logreg_lockstep_workspace": [_I, _I, _I, _I, _I, _P],
+    "sm3_logreg_batch_logits": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "sm3_logreg_batch_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P, _P],
+    "sm3_logreg_value_grad_lockstep": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P],
+    "sm3_logreg_fit_lockstep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P],
 }
 
 _lib = None

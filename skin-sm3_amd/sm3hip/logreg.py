@@ -19,6 +19,13 @@ One workgroup fits one problem, so the result of a problem is a function of (X, 
 alone or in any batch, at any position, for any `chunk`, on repeated calls.  Everything but X is fp64.  A launch runs a bounded
 number of iterations (launch_iterations) and saves the solvers' state; the host reads the statuses and launches again until every
 problem has finished -- the result does not depend on where the launches are cut.
+
+TWO SOLVERS of the same problems, by the same L-BFGS rules.  solver="workgroup" (the default) is the one above.
+solver="lockstep" takes the problems of a chunk through every iteration side by side: the two passes over X of an iteration are
+two products on the f64 MFMA that all problems share -- one [N, D] x [D, columns] product for the logits, one [columns, N] x
+[N, D] product for the gradients, a column being one (problem, class) pair -- and the per-problem steps run between them.  Its
+sums run in other orders than the workgroup solver's, so the two agree to rounding and to the stopping tolerance, not in bits;
+each keeps the bits contract above for itself.
 """
 import math
 
@@ -32,6 +39,7 @@ MAX_ROWS = ops.LOGREG_MAX_ROWS
 MAX_DIM = ops.LOGREG_MAX_DIM
 MAX_CLASSES = ops.LOGREG_MAX_CLASSES
 STATUS = ("ok", "max_iter", "no_step", "one_class", "bad_entry")
+SOLVERS = ("workgroup", "lockstep")
 DEFAULT_CS = tuple(float(c) for c in np.logspace(-4, 4, 16))
 NORMALIZE = ("none", "l2", "standardize")
 WORKSPACE_BYTES = 2 << 30  # what the default chunk keeps a launch's workspace under
@@ -94,6 +102,12 @@ def _require_gpu(X, who):
     return X.contiguous()
 
 
+def _solver(solver, who):
+    if solver not in SOLVERS:
+        raise ValueError(f"{who}: solver must be one of {SOLVERS}, got {solver!r}")
+    return solver
+
+
 def _pad_classes(t):
     """[P, n, ...] -> [P, 8, ...], zero rows behind."""
     if t.shape[1] == MAX_CLASSES:
@@ -118,11 +132,13 @@ def balanced(weights, targets, label):
 
 
 # ---- value and gradient -------------------------------------------------------------------------------------------------------
-def value_and_grad(X, targets, problems, W, b, weights=None):
+def value_and_grad(X, targets, problems, W, b, weights=None, solver="workgroup"):
     """(F [P], grad_W [P, n, D], grad_b [P, n]) float64 of the problems [(label, C, weight row), ...] at W [P, n, D], b [P, n]
     (n >= the classes of every label named, at most 8): the certificate of any solution, scikit-learn's included -- at the
-    optimum grad is 0.  An intercept of -inf is accepted for a class of zero weight."""
+    optimum grad is 0.  An intercept of -inf is accepted for a class of zero weight.  solver: which kernels form the sums
+    (SOLVERS)."""
     who = "value_and_grad"
+    _solver(solver, who)
     X = _features(X, who)
     N, D = X.shape
     tg, wt, pr = _host_targets(targets, N, who), _host_weights(weights, N, who), _host_problems(problems, who)
@@ -136,10 +152,15 @@ def value_and_grad(X, targets, problems, W, b, weights=None):
     X = _require_gpu(X, who)
     dev, n = X.device, W.shape[1]
     Wd, bd = _pad_classes(W.to(dev, torch.float64)), _pad_classes(b.to(dev, torch.float64))
-    ws = torch.empty(P * ops.logreg_workspace(N, D, False), dtype=torch.float64, device=dev)
     F = torch.empty(P, dtype=torch.float64, device=dev)
     gW, gb = torch.empty_like(Wd), torch.empty_like(bd)
-    ops.logreg_value_grad(X, tg.to(dev), wt.to(dev), table.to(dev), Cs.to(dev), Wd, bd, ws, F, gW, gb)
+    if solver == "lockstep":
+        cols = ops.logreg_columns(table[:, 2].tolist())
+        ws = torch.empty(ops.logreg_lockstep_workspace(N, D, P, cols.numel(), False), dtype=torch.float64, device=dev)
+        ops.logreg_value_grad_lockstep(X, tg.to(dev), wt.to(dev), table.to(dev), Cs.to(dev), cols.to(dev), Wd, bd, ws, F, gW, gb)
+    else:
+        ws = torch.empty(P * ops.logreg_workspace(N, D, False), dtype=torch.float64, device=dev)
+        ops.logreg_value_grad(X, tg.to(dev), wt.to(dev), table.to(dev), Cs.to(dev), Wd, bd, ws, F, gW, gb)
     return F, gW[:, :n].contiguous(), gb[:, :n].contiguous()
 
 
@@ -148,7 +169,7 @@ class Fit:
     """What fit returns.  coef [P, n_max, D], intercept [P, n_max] float64 on the GPU (rows behind a label's classes are 0);
     problems [(label, C, weight row), ...] in launch order: weight row, then label, then C ascending as given; status [P] int32
     (STATUS names them), iterations [P] int32, objective, grad_norm [P] float64.  labels, Cs: what was swept; weights: the host
-    rows [R, N] as given (before class_weight); n_classes [P]."""
+    rows [R, N] as given (before class_weight); n_classes [P]; solver: the one of SOLVERS that ran."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -173,9 +194,15 @@ def launch_iterations(N, D):
     return max(1, min(32, LAUNCH_WORK // (N * D)))
 
 
-def _launch_fits(X, tg, rows, launch, gtol, max_iter, chunk, who, launch_iters=None):
+def lockstep_chunk(N, D, P):
+    """The problems of one lockstep chunk: as many as WORKSPACE_BYTES of workspace hold, every problem counted at 8 columns."""
+    return max(1, min(P, WORKSPACE_BYTES // (8 * ops.logreg_lockstep_workspace(N, D, 1, MAX_CLASSES, True))))
+
+
+def _launch_fits(X, tg, rows, launch, gtol, max_iter, chunk, who, launch_iters=None, solver="workgroup"):
     """The kernels' part of a fit: the host rows and launch problems are checked, uploaded and fitted `chunk` at a time, each
     chunk in launches of at most launch_iters iterations; between two launches the host reads the chunk's statuses."""
+    _solver(solver, who)
     N, D = X.shape
     P = len(launch)
     if chunk is not None and (not resample.is_int(chunk) or chunk < 1):
@@ -188,8 +215,14 @@ def _launch_fits(X, tg, rows, launch, gtol, max_iter, chunk, who, launch_iters=N
     if launch_iters is not None and (not resample.is_int(launch_iters) or launch_iters < 1):
         raise ValueError(f"{who}: launch_iters must be None or an integer >= 1, got {launch_iters!r}")
     iters = launch_iterations(N, D) if launch_iters is None else launch_iters
-    c = default_chunk(N, D, P) if chunk is None else min(chunk, P)
-    ws = torch.empty(c * ops.logreg_workspace(N, D, True), dtype=torch.float64, device=dev)
+    lockstep = solver == "lockstep"
+    if lockstep:
+        iters = min(iters, ops.LOGREG_LOCKSTEP_MAX_ITERS)
+        c = min(lockstep_chunk(N, D, P) if chunk is None else chunk, P, ops.LOGREG_LOCKSTEP_MAX_PROBLEMS)
+        ws = torch.empty(ops.logreg_lockstep_workspace(N, D, c, MAX_CLASSES * c, True), dtype=torch.float64, device=dev)
+    else:
+        c = default_chunk(N, D, P) if chunk is None else min(chunk, P)
+        ws = torch.empty(c * ops.logreg_workspace(N, D, True), dtype=torch.float64, device=dev)
     coef = torch.empty(P, MAX_CLASSES, D, dtype=torch.float64, device=dev)
     intercept = torch.empty(P, MAX_CLASSES, dtype=torch.float64, device=dev)
     info = torch.empty(P, 2, dtype=torch.int32, device=dev)
@@ -197,40 +230,48 @@ def _launch_fits(X, tg, rows, launch, gtol, max_iter, chunk, who, launch_iters=N
     for p0 in range(0, P, c):
         p1 = min(P, p0 + c)
         resume = False
+        cols = ops.logreg_columns(table[p0:p1, 2].tolist()).to(dev) if lockstep else None
         while True:
-            ops.logreg_fit(X, tg_d, rows_d, table_d[p0:p1], Cd_d[p0:p1], gtol, max_iter, ws, coef[p0:p1], intercept[p0:p1],
-                           info[p0:p1], res[p0:p1], resume=resume, iters=iters)
+            if lockstep:
+                ops.logreg_fit_lockstep(X, tg_d, rows_d, table_d[p0:p1], Cd_d[p0:p1], cols, gtol, max_iter, ws, coef[p0:p1],
+                                        intercept[p0:p1], info[p0:p1], res[p0:p1], resume=resume, iters=iters)
+            else:
+                ops.logreg_fit(X, tg_d, rows_d, table_d[p0:p1], Cd_d[p0:p1], gtol, max_iter, ws, coef[p0:p1], intercept[p0:p1],
+                               info[p0:p1], res[p0:p1], resume=resume, iters=iters)
             resume = True
             if not bool((info[p0:p1, 0] == ops.LOGREG_RUNNING).any()):  # the one readback between launches
                 break
     return coef, intercept, info, res
 
 
-def _as_fit(out, problems, labels, Cs, wt, class_weight, gtol, max_iter):
+def _as_fit(out, problems, labels, Cs, wt, class_weight, gtol, max_iter, solver):
     coef, intercept, info, res = out
     n_max = max(NUM_CLASSES[t] for t, _, _ in problems)
     return Fit(coef=coef[:, :n_max].contiguous(), intercept=intercept[:, :n_max].contiguous(), problems=problems,
                status=info[:, 0].contiguous(), iterations=info[:, 1].contiguous(), objective=res[:, 0].contiguous(),
                grad_norm=res[:, 1].contiguous(), labels=labels, Cs=Cs, weights=wt, class_weight=class_weight,
-               n_classes=[NUM_CLASSES[t] for t, _, _ in problems], gtol=gtol, max_iter=max_iter)
+               n_classes=[NUM_CLASSES[t] for t, _, _ in problems], gtol=gtol, max_iter=max_iter, solver=solver)
 
 
-def fit_problems(X, targets, problems, weights=None, gtol=1e-9, max_iter=1000, chunk=None, launch_iters=None):
+def fit_problems(X, targets, problems, weights=None, gtol=1e-9, max_iter=1000, chunk=None, launch_iters=None, solver="workgroup"):
     """Fits the listed problems [(label, C, weight row), ...], in that order, over the one X [N, D] float32 on the GPU: what fit
     runs on, for a batch that is not a grid.  labels and Cs of the returned Fit are None."""
     who = "fit_problems"
+    _solver(solver, who)
     X = _features(X, who)
     tg, wt, pr = _host_targets(targets, X.shape[0], who), _host_weights(weights, X.shape[0], who), _host_problems(problems, who)
-    return _as_fit(_launch_fits(X, tg, wt, pr, gtol, max_iter, chunk, who, launch_iters), pr, None, None, wt, None, gtol, max_iter)
+    return _as_fit(_launch_fits(X, tg, wt, pr, gtol, max_iter, chunk, who, launch_iters, solver), pr, None, None, wt, None, gtol, max_iter,
+                   solver)
 
 
 def fit(X, targets, Cs=DEFAULT_CS, weights=None, class_weight=None, labels=range(8), gtol=1e-9, max_iter=1000, chunk=None,
-        launch_iters=None):
+        launch_iters=None, solver="workgroup"):
     """Fits every (weight row, label, C): P = R * len(labels) * len(Cs) problems over the one X [N, D] float32 on the GPU.  Stops a
     problem at |grad F|_inf <= gtol or after max_iter L-BFGS iterations.  class_weight: None or "balanced".  chunk: problems per
     launch (None: as many as WORKSPACE_BYTES of workspace hold), launch_iters: iterations per launch (None: launch_iterations(N,
-    D)); the result depends on neither."""
+    D)); the result depends on neither.  solver: one of SOLVERS."""
     who = "fit"
+    _solver(solver, who)
     X = _features(X, who)
     N, D = X.shape
     tg, wt = _host_targets(targets, N, who), _host_weights(weights, N, who)
@@ -248,8 +289,8 @@ def fit(X, targets, Cs=DEFAULT_CS, weights=None, class_weight=None, labels=range
         launch = [(t, c, r * len(labels) + labels.index(t)) for t, c, r in problems]
     else:
         rows, launch = wt, problems
-    return _as_fit(_launch_fits(X, tg, rows, launch, gtol, max_iter, chunk, who, launch_iters), problems, labels, Cs, wt, class_weight, gtol,
-                   max_iter)
+    return _as_fit(_launch_fits(X, tg, rows, launch, gtol, max_iter, chunk, who, launch_iters, solver), problems, labels, Cs, wt,
+                   class_weight, gtol, max_iter, solver)
 
 
 # ---- prediction ---------------------------------------------------------------------------------------------------------------

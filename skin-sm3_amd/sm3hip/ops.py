@@ -1761,6 +1761,123 @@ def logreg_predict(Xq, coef, intercept, nts, logits):
               "sm3_logreg_predict")
 
 
+LOGREG_LOCKSTEP_SLAB = 2048        # sm3_logreg_lockstep_slab(): the rows of one slab of the batched gradient product
+LOGREG_LOCKSTEP_MAX_PROBLEMS = 65535
+LOGREG_LOCKSTEP_MAX_ITERS = 1024   # iterations one sm3_logreg_fit_lockstep call may enqueue
+
+
+def logreg_columns(nts):
+    """The column table of the lockstep solver for problems of nts[p] classes: int32 [sum nts], entry 8 p + c for c < nts[p]."""
+    nts = [int(n) for n in nts]
+    if not nts or not all(1 <= n <= LOGREG_MAX_CLASSES for n in nts):
+        raise ValueError(f"logreg_columns: every problem has 1 to {LOGREG_MAX_CLASSES} classes")
+    return torch.tensor([LOGREG_MAX_CLASSES * p + c for p, n in enumerate(nts) for c in range(n)], dtype=torch.int32)
+
+
+def _logreg_batch(who, N, D, P, ncols):
+    _logreg_shape(who, N, D)
+    if not 1 <= P <= LOGREG_LOCKSTEP_MAX_PROBLEMS or not 1 <= ncols <= LOGREG_MAX_CLASSES * P:
+        raise ValueError(f"{who}: 1 to {LOGREG_LOCKSTEP_MAX_PROBLEMS} problems a call in 1 to 8 P columns, got P = {P}, {ncols} columns")
+
+
+def logreg_lockstep_workspace(N, D, P, ncols, fit=True):
+    """The float64 elements of workspace ONE call of the lockstep fit (or of logreg_value_grad_lockstep) needs for P problems in
+    ncols columns (sm3_logreg_lockstep_workspace)."""
+    _logreg_batch("logreg_lockstep_workspace", N, D, P, ncols)
+    out = C.c_int64(0)
+    check(_lib.load().sm3_logreg_lockstep_workspace(int(N), int(D), int(P), int(ncols), int(bool(fit)), C.byref(out)),
+          "sm3_logreg_lockstep_workspace")
+    return int(out.value)
+
+
+def logreg_batch_logits(X, V, vb, cols, active, Z):
+    """Z [P, N, 8] float64: Z[p, i, c] = sum_k X[i, k] V[p, c, k] + vb[p, c] for the columns cols (logreg_columns) of the problems
+    with active[p] != 0, on the f64 MFMA (sm3_logreg_batch_logits).  V [P, 8, D], vb [P, 8] or None, active [P] int32.  Nothing
+    of an inactive problem, and nothing outside the columns listed, is written."""
+    _chk(X, torch.float32, "X"); _chk(V, torch.float64, "V"); _chk(cols, torch.int32, "cols"); _chk(active, torch.int32, "active")
+    _chk(Z, torch.float64, "Z")
+    if vb is not None:
+        _chk(vb, torch.float64, "vb")
+    if X.dim() != 2 or V.dim() != 3 or cols.dim() != 1:
+        raise ValueError("logreg_batch_logits: X [N, D], V [P, 8, D] and cols [ncols]")
+    (N, D), P, K, ncols = X.shape, V.shape[0], LOGREG_MAX_CLASSES, cols.shape[0]
+    _logreg_batch("logreg_batch_logits", N, D, P, ncols)
+    if tuple(V.shape) != (P, K, D) or tuple(Z.shape) != (P, N, K) or tuple(active.shape) != (P,) or \
+            (vb is not None and tuple(vb.shape) != (P, K)):
+        raise ValueError(f"logreg_batch_logits: V [{P}, {K}, {D}], vb [{P}, {K}], active [{P}] and Z [{P}, {N}, {K}] do not match")
+    with _prof("logreg_batch_logits", 2.0 * N * D * ncols, 4.0 * N * D):
+        check(_lib.load().sm3_logreg_batch_logits(_ptr(X), _ptr(V), None if vb is None else _ptr(vb), _ptr(cols), _ptr(active), N, D,
+                                                  P, ncols, _ptr(Z), _stream()), "sm3_logreg_batch_logits")
+
+
+def logreg_batch_grad(X, Rm, cols, active, ws, G, gb):
+    """G [P, 8, D], gb [P, 8] float64: G[p, c, k] = sum_i Rm[p, i, c] X[i, k], gb[p, c] = sum_i Rm[p, i, c] for the columns cols
+    of the problems with active[p] != 0, on the f64 MFMA (sm3_logreg_batch_grad).  Rm [P, N, 8]; ws: at least ceil(N /
+    LOGREG_LOCKSTEP_SLAB) * ncols * D float64 elements.  Nothing of an inactive problem is written."""
+    _chk(X, torch.float32, "X"); _chk(Rm, torch.float64, "Rm"); _chk(cols, torch.int32, "cols"); _chk(active, torch.int32, "active")
+    _chk(ws, torch.float64, "ws"); _chk(G, torch.float64, "G"); _chk(gb, torch.float64, "gb")
+    if X.dim() != 2 or Rm.dim() != 3 or cols.dim() != 1:
+        raise ValueError("logreg_batch_grad: X [N, D], Rm [P, N, 8] and cols [ncols]")
+    (N, D), P, K, ncols = X.shape, Rm.shape[0], LOGREG_MAX_CLASSES, cols.shape[0]
+    _logreg_batch("logreg_batch_grad", N, D, P, ncols)
+    need = -(-N // LOGREG_LOCKSTEP_SLAB) * ncols * D
+    if tuple(Rm.shape) != (P, N, K) or tuple(G.shape) != (P, K, D) or tuple(gb.shape) != (P, K) or tuple(active.shape) != (P,) or \
+            ws.numel() < need:
+        raise ValueError(f"logreg_batch_grad: Rm [{P}, {N}, {K}], G [{P}, {K}, {D}], gb [{P}, {K}], active [{P}] and the workspace "
+                         f"(at least {need} elements) do not match")
+    with _prof("logreg_batch_grad", 2.0 * N * D * ncols, 4.0 * N * D):
+        check(_lib.load().sm3_logreg_batch_grad(_ptr(X), _ptr(Rm), _ptr(cols), _ptr(active), N, D, P, ncols, _ptr(ws), ws.numel(),
+                                                _ptr(G), _ptr(gb), _stream()), "sm3_logreg_batch_grad")
+
+
+def logreg_value_grad_lockstep(X, targets, weights, table, Cs, cols, W, b, ws, F, gW, gb):
+    """logreg_value_grad through the two batched products (sm3_logreg_value_grad_lockstep); cols: logreg_columns of the problems'
+    classes; ws: at least logreg_lockstep_workspace(N, D, P, ncols, fit=False) float64 elements."""
+    who = "logreg_value_grad_lockstep"
+    N, D, R, P = _logreg_problem_tensors(who, X, targets, weights, table, Cs)
+    for t, n in ((W, "W"), (b, "b"), (ws, "ws"), (F, "F"), (gW, "gW"), (gb, "gb")):
+        _chk(t, torch.float64, n)
+    _chk(cols, torch.int32, "cols")
+    K, ncols = LOGREG_MAX_CLASSES, cols.numel()
+    _logreg_batch(who, N, D, P, ncols)
+    if cols.dim() != 1 or tuple(W.shape) != (P, K, D) or tuple(gW.shape) != (P, K, D) or tuple(b.shape) != (P, K) or \
+            tuple(gb.shape) != (P, K) or tuple(F.shape) != (P,) or ws.numel() < logreg_lockstep_workspace(N, D, P, ncols, False):
+        raise ValueError(f"{who}: W, gW [{P}, {K}, {D}], b, gb [{P}, {K}], F [{P}], cols [ncols] and the workspace do not match")
+    with _prof(who, 4.0 * N * D * ncols, 8.0 * N * D):
+        check(_lib.load().sm3_logreg_value_grad_lockstep(_ptr(X), _ptr(targets), _ptr(weights), _ptr(table), _ptr(Cs), _ptr(cols),
+                                                         _ptr(W), _ptr(b), N, D, R, P, ncols, _ptr(ws), ws.numel(), _ptr(F), _ptr(gW),
+                                                         _ptr(gb), _stream()), "sm3_logreg_value_grad_lockstep")
+
+
+def logreg_fit_lockstep(X, targets, weights, table, Cs, cols, gtol, max_iter, ws, coef, intercept, info, res, resume=False, iters=1):
+    """logreg_fit's outputs by the lockstep solver (sm3_logreg_fit_lockstep): ONE call enqueues `iters` iterations (1 to
+    LOGREG_LOCKSTEP_MAX_ITERS) of all P problems side by side; a problem it leaves unfinished has status LOGREG_RUNNING and goes on
+    in a call with resume=True and the same tensors.  cols: logreg_columns of the problems' classes; ws: at least
+    logreg_lockstep_workspace(N, D, P, ncols) float64 elements."""
+    who = "logreg_fit_lockstep"
+    N, D, R, P = _logreg_problem_tensors(who, X, targets, weights, table, Cs)
+    for t, n in ((ws, "ws"), (coef, "coef"), (intercept, "intercept"), (res, "res")):
+        _chk(t, torch.float64, n)
+    _chk(info, torch.int32, "info"); _chk(cols, torch.int32, "cols")
+    K, ncols = LOGREG_MAX_CLASSES, cols.numel()
+    _logreg_batch(who, N, D, P, ncols)
+    if cols.dim() != 1 or tuple(coef.shape) != (P, K, D) or tuple(intercept.shape) != (P, K) or tuple(info.shape) != (P, 2) or \
+            tuple(res.shape) != (P, 2) or ws.numel() < logreg_lockstep_workspace(N, D, P, ncols, True):
+        raise ValueError(f"{who}: coef [{P}, {K}, {D}], intercept [{P}, {K}], info, res [{P}, 2], cols [ncols] and the workspace do "
+                         "not match")
+    if isinstance(gtol, bool) or not isinstance(gtol, (int, float)) or not 0 <= gtol < float("inf"):
+        raise ValueError(f"{who}: gtol must be a finite number >= 0, got {gtol!r}")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or not 0 <= max_iter < 2 ** 31:
+        raise ValueError(f"{who}: max_iter must be an integer >= 0, got {max_iter!r}")
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= LOGREG_LOCKSTEP_MAX_ITERS:
+        raise ValueError(f"{who}: iters must be an integer in [1, {LOGREG_LOCKSTEP_MAX_ITERS}], got {iters!r}")
+    with _prof(who, 0.0, 0.0):
+        check(_lib.load().sm3_logreg_fit_lockstep(_ptr(X), _ptr(targets), _ptr(weights), _ptr(table), _ptr(Cs), _ptr(cols), N, D, R,
+                                                  P, ncols, float(gtol), max_iter, int(bool(resume)), iters, _ptr(ws), ws.numel(),
+                                                  _ptr(coef), _ptr(intercept), _ptr(info), _ptr(res), _stream()),
+              "sm3_logreg_fit_lockstep")
+
+
 CALIB_MAX_BINS = 64
 CALIB_BINNINGS = ("width", "mass")
 

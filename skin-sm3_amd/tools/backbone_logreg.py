@@ -9,7 +9,8 @@ score is a function of (features, labels, C).
         --pretrain-path logs/backbone/ckp_399.pth --log-path logs/backbone/logreg_399 --logreg-select val
 
 Takes backbone_eval's command line (its checkpoint loader and data helpers, --bootstrap, --calibration, --operating, --checklist)
-plus the --logreg-* flags, --save-features and --random-features.  A case's feature is cat(derm_f, clinic_f) through the
+plus the --logreg-* flags (--logreg-solver workgroup | lockstep picks the kernels of the fit, recorded in logreg_predictions.pt),
+--save-features and --random-features.  A case's feature is cat(derm_f, clinic_f) through the
 validation chain, then --logreg-normalize (standardize: per-feature mean and deviation of the train rows).
 
   --logreg-select val   every (label, C) is fitted on train and scored on valid (--logreg-by auc | nll; ties: the smaller C); the
@@ -64,6 +65,8 @@ def get_parser():
     p.add_argument("--logreg-normalize", default="standardize", help="none | l2 | standardize")
     p.add_argument("--logreg-gtol", type=float, default=1e-9, help="stop at |grad F|_inf <= gtol")
     p.add_argument("--logreg-max-iter", type=int, default=1000, help="L-BFGS iterations at most")
+    p.add_argument("--logreg-solver", default="workgroup",
+                   help="workgroup | lockstep: one workgroup a problem, or all problems side by side on batched f64-MFMA products")
     p.add_argument("--logreg-refit-trainval", action="store_true",
                    help="with --logreg-select val: the reported model is refitted on train + valid at the selected C")
     p.add_argument("--random-features", type=int, nargs=3, default=None, metavar=("N", "B", "D"),
@@ -78,7 +81,8 @@ def check_flags(args):
     for flag, value, allowed in (("--logreg-select", args.logreg_select, ("val", "cv", "none")),
                                  ("--logreg-by", args.logreg_by, ("auc", "nll")),
                                  ("--logreg-class-weight", args.logreg_class_weight, ("none", "balanced")),
-                                 ("--logreg-normalize", args.logreg_normalize, logreg.NORMALIZE)):
+                                 ("--logreg-normalize", args.logreg_normalize, logreg.NORMALIZE),
+                                 ("--logreg-solver", args.logreg_solver, logreg.SOLVERS)):
         if value not in allowed:
             raise SystemExit(f"{TOOL}: {flag} {value} is not one of {', '.join(allowed)}")
     if not all(0.0 < c < float("inf") for c in args.logreg_c):
@@ -196,7 +200,7 @@ def main(argv=None):
 
     # ---- fit, select, refit
     cw = None if args.logreg_class_weight == "none" else "balanced"
-    kw = dict(class_weight=cw, gtol=args.logreg_gtol, max_iter=args.logreg_max_iter)
+    kw = dict(class_weight=cw, gtol=args.logreg_gtol, max_iter=args.logreg_max_iter, solver=args.logreg_solver)
     Cs = sorted(args.logreg_c)
     fracs = sorted(set(args.logreg_fractions), reverse=True)  # weight row 0: the largest fraction, the one reported
     torch.cuda.synchronize()
@@ -240,6 +244,7 @@ def main(argv=None):
     stat.update(new)
     saved = {"preds": [p.cpu() for p in preds], "targets": tte.cpu(), "AUC_AVG": stat["AUC_AVG"], "AUC": [float(a) for a in per],
              "C": chosen, "selection": selection, "normalize": args.logreg_normalize, "class_weight": args.logreg_class_weight,
+             "solver": args.logreg_solver,
              "status": [{"problems": f.problems, "status": f.status.cpu(), "iterations": f.iterations.cpu(),
                          "objective": f.objective.cpu(), "grad_norm": f.grad_norm.cpu()} for f in fits]}
     if args.save_features:

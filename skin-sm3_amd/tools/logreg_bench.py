@@ -4,6 +4,7 @@ use) on the same standardised features, at N = 413, D = 4096 (the derm7pt train 
 D = 4096.
 
     python tools/logreg_bench.py --out profiles/logreg_measure.json
+    python tools/logreg_bench.py --only fit --solver both --out profiles/logreg_lockstep_measure.json
     rocprofv3 --kernel-trace --stats --output-format csv -d out -o logreg -- python tools/logreg_bench.py --only fit --sizes 413
 
 fit() is timed end to end -- the host checks, the uploads, every launch, by the host clock around a final device synchronise --
@@ -45,6 +46,9 @@ def get_parser():
     p.add_argument("--max-iter", type=int, default=1000)
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--only", choices=("both", "fit", "sklearn"), default="both")
+    p.add_argument("--solver", choices=logreg.SOLVERS + ("both",), default="workgroup",
+                   help="the solver timed; both: the two alternate in one process, run by run, and the record holds each "
+                        "(the lockstep solver's figures under lockstep_*)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out", type=str, default=None, help="JSON file of the result records")
     p.add_argument("--append", action="store_true", help="keep the records --out already holds and add this run's")
@@ -65,12 +69,12 @@ def make_inputs(N, Q, D, seed):
     return xs[:N].contiguous(), torch.stack(t, dim=1)[:N].contiguous(), xs[N:].contiguous()
 
 
-def time_fit(X, T, Cs, args):
+def time_fit(X, T, Cs, args, solver="workgroup"):
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     start.record()
-    f = logreg.fit(X, T, Cs, gtol=args.gtol, max_iter=args.max_iter)
+    f = logreg.fit(X, T, Cs, gtol=args.gtol, max_iter=args.max_iter, solver=solver)
     end.record()
     torch.cuda.synchronize()
     return time.perf_counter() - t0, start.elapsed_time(end) / 1e3, f
@@ -110,17 +114,32 @@ def main(argv=None):
         fit = None
         if args.only != "sklearn":
             Xd = X.cuda()
-            time_fit(Xd, T, Cs[len(Cs) // 2:len(Cs) // 2 + 2], args)  # warm-up on this shape: code objects, the allocator
-            walls, launches = [], []
+            solvers = logreg.SOLVERS if args.solver == "both" else (args.solver,)
+            for s in solvers:
+                time_fit(Xd, T, Cs[len(Cs) // 2:len(Cs) // 2 + 2], args, s)  # warm-up on this shape: code objects, the allocator
+            walls, launches, fits = {s: [] for s in solvers}, {s: [] for s in solvers}, {}
             for _ in range(args.repeats):
-                w, l, fit = time_fit(Xd, T, Cs, args)
-                walls.append(w)
-                launches.append(l)
-            status = fit.status.cpu().numpy()
-            rec.update(fit_s=statistics.median(walls), fit_s_all=walls, launch_s=statistics.median(launches), launch_s_all=launches,
-                       iterations=int(fit.iterations.sum()), iterations_max=int(fit.iterations.max()),
-                       status_counts={logreg.STATUS[k]: int((status == k).sum()) for k in range(len(logreg.STATUS))},
-                       grad_norm_max=float(fit.grad_norm.max()), device=torch.cuda.get_device_name(0))
+                for s in solvers:  # the solvers alternate, so that a drift of the machine meets both
+                    w, l, fits[s] = time_fit(Xd, T, Cs, args, s)
+                    walls[s].append(w)
+                    launches[s].append(l)
+            for s in solvers:
+                # with --solver both the workgroup solver keeps the record's plain keys, the lockstep solver's carry its name
+                pre = "lockstep_" if s == "lockstep" and len(solvers) > 1 else ""
+                status = fits[s].status.cpu().numpy()
+                rec.update({pre + "fit_s": statistics.median(walls[s]), pre + "fit_s_all": walls[s],
+                            pre + "launch_s": statistics.median(launches[s]), pre + "launch_s_all": launches[s],
+                            pre + "iterations": int(fits[s].iterations.sum()), pre + "iterations_max": int(fits[s].iterations.max()),
+                            pre + "status_counts": {logreg.STATUS[k]: int((status == k).sum()) for k in range(len(logreg.STATUS))},
+                            pre + "grad_norm_max": float(fits[s].grad_norm.max())})
+            rec.update(solver=args.solver, device=torch.cuda.get_device_name(0))
+            fit = fits[solvers[0]]
+            if len(solvers) > 1:  # the two optima on the held-out rows: the worst probability gap between the solvers
+                za, zb = (logreg.predict_all(fits[s], Xq.cuda()) for s in solvers)
+                gap = 0.0
+                for p, n in enumerate(fit.n_classes):
+                    gap = max(gap, float((torch.softmax(za[p, :, :n], dim=1) - torch.softmax(zb[p, :, :n], dim=1)).abs().max()))
+                rec["solver_probability_gap"] = gap
         if args.only != "fit":
             import sklearn
             probs, secs, iters = sklearn_loop(X, T, Xq, sk_cs)
