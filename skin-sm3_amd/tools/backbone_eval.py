@@ -31,16 +31,18 @@ import time
 
 SCRIPT_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_PATH = os.path.split(SCRIPT_DIR)[0]
-sys.path.insert(0, ROOT_PATH)
+for _p in (ROOT_PATH, SCRIPT_DIR):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in device memory: see sm3hip/__init__.py
 
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from sm3hip import calibration, checklist, operating, report  # noqa: E402
-from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
-from src.models.baseline import Baseline  # noqa: E402
+import eval_cli  # noqa: E402
+from sm3hip import report  # noqa: E402
+from sm3hip.metrics import CLASSES_NAME, auc_avg  # noqa: E402
 
 
 def get_parser(calibration_flags=True):
@@ -55,42 +57,9 @@ def get_parser(calibration_flags=True):
     p.add_argument("--steps-per-epoch", default=8, type=int)
     p.add_argument("--val-steps", default=4, type=int)
     report.add_flags(p)
-    if calibration_flags:
-        calibration.add_flags(p)
-    operating.add_flags(p)
-    checklist.add_flags(p)
+    eval_cli.add_report_flags(p, calibration=calibration_flags)
     p.set_defaults(arch="resnet50", epochs=50, batch_size=128)
     return p
-
-
-def load_ssl_backbones(evaluator, path):
-    """Split an SSL checkpoint's keys by the derm_backbone.encoder. / clinic_backbone.encoder. prefixes
-    (backbone_eval.py:278-296)."""
-    state = torch.load(path, map_location="cpu")["state_dict"]
-    derm, clinic = {}, {}
-    for k, v in state.items():
-        k = k[7:] if k.startswith("module.") else k
-        if k.startswith("derm_backbone.encoder."):
-            derm[k[len("derm_backbone.encoder."):]] = v
-        elif k.startswith("clinic_backbone.encoder."):
-            clinic[k[len("clinic_backbone.encoder."):]] = v
-    evaluator.derm_backbone.load_state_dict(derm)
-    evaluator.clinic_backbone.load_state_dict(clinic)
-
-
-def synthetic(bs, size, dev, gen):
-    derm = torch.randn(bs, 3, size[0], size[1], device=dev, generator=gen)
-    clinic = torch.randn(bs, 3, size[0], size[1], device=dev, generator=gen)
-    labels = torch.stack([torch.randint(0, n, (bs,), device=dev, generator=gen) for n in NUM_CLASSES], dim=1)
-    return derm, clinic, labels
-
-
-def real_batches(store, split, aug, batches, gen, whole):
-    """(derm, clinic, labels) of each batch of case indices: one augmented view per modality, labels from the device."""
-    for sel in batches:
-        derm = store.augment(aug, split.derm_ids[sel], gen, whole=whole)[0]
-        clinic = store.augment(aug, split.clinic_ids[sel], gen, whole=whole)[0]
-        yield derm, clinic, split.labels.index_select(0, sel.to(split.labels.device, non_blocking=True))
 
 
 def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, data=None):
@@ -100,7 +69,7 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, dat
         evaluator.eval()
     all_preds, all_targets, total, t0 = [], [], 0.0, time.time()
     if data is None:
-        data = (synthetic(args.batch_size, args.img_sz, dev, gen) for _ in range(steps))
+        data = eval_cli.synthetic_batches([args.batch_size] * steps, args.img_sz, dev, gen)
     steps, pairs = 0, 0
     for derm, clinic, labels in data:
         steps += 1
@@ -134,42 +103,23 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, dat
 def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
-    calibration.check_flags(args)
-    operating.check_flags(args)
-    checklist.check_flags(args)
-    from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
-    require_baseline_arch(args.arch, "backbone_eval")
-    real = require_data(args, "backbone_eval")
-    if ignored_line(args, parser, real):
-        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
-    torch.manual_seed(args.seed)
-    dev = torch.device("cuda", 0)
-    evaluator = Baseline(args.arch, args.arch_weights)
-    if args.pretrain_path and os.path.isfile(args.pretrain_path):
-        load_ssl_backbones(evaluator, args.pretrain_path)
-        print(f"loaded pre-trained model weights from '{args.pretrain_path}'")
-    if args.finetune == "fc":
-        evaluator.freeze_backbone()
-    for m in (evaluator.derm_backbone, evaluator.clinic_backbone):
-        m.sm3_dtype = amp_dtype(args)
+    eval_cli.check_report_flags(args)
+    from src.utils.misc import amp_dtype
+    dev, gen, real = eval_cli.refuse_and_seed(args, parser, "backbone_eval")
+    evaluator = eval_cli.baseline_subject(args, dev, freeze=args.finetune == "fc", eval_mode=False)
     args.scaler = torch.amp.GradScaler("cuda", enabled=amp_dtype(args) == torch.float16)  # backbone_eval.py:271
-    evaluator.to(dev)
     params = [p for p in evaluator.parameters() if p.requires_grad]
     optimizer = torch.optim.AdamW(params, lr=args.base_lr, weight_decay=args.wd)
     criterion = nn.CrossEntropyLoss()
-    gen = torch.Generator(device=dev).manual_seed(args.seed)
     train_data = val_data = lambda epoch: None
     if real:
-        from sm3hip.augment import chain
-        from sm3hip.imagestore import build_for
-        from src.utils.data.sampler import eval_batches, train_batches
-        store = build_for(args, ["train", "test"], dev)
+        from src.utils.data.sampler import train_batches
+        store, aug = eval_cli.image_store(args, ["train", "test"], dev)
         tsplit, vsplit = store.splits["train"], store.splits["test"]
-        aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
         aug_gen = torch.Generator().manual_seed(args.seed + 1000)
-        train_data = lambda epoch: real_batches(store, tsplit, aug, train_batches(len(tsplit), 1, 0, epoch, args.batch_size),
-                                                aug_gen, False)
-        val_data = lambda epoch: real_batches(store, vsplit, aug, eval_batches(len(vsplit), args.batch_size), None, True)
+        train_data = lambda epoch: eval_cli.split_batches(
+            args, store, tsplit, aug, train_batches(len(tsplit), 1, 0, epoch, args.batch_size), aug_gen, whole=False)
+        val_data = lambda epoch: eval_cli.split_batches(args, store, vsplit, aug)
     best, history = -1.0, []
     os.makedirs(args.log_path, exist_ok=True)
     for epoch in range(args.epochs):
@@ -184,15 +134,8 @@ def main(argv=None):
         print(f"epoch {epoch}: train loss {tr['loss']:.4f} AUC_AVG {tr['AUC_AVG']:.4f} {tr['pairs_per_s']:.0f} pairs/s | "
               f"val loss {va['loss']:.4f} AUC_AVG {va['AUC_AVG']:.4f} {va['pairs_per_s']:.0f} pairs/s", flush=True)
         print(f"epoch {epoch}: val {report.stats_line(va, rep)}", flush=True)
-        if args.calibration and epoch == args.epochs - 1:  # val_calibration.json / .csv next to val_report.*
-            cal = calibration.validation_calibration(va["preds"], va["targets"], args, args.log_path)
-            print(f"epoch {epoch}: val {calibration.stats_line(cal)}", flush=True)
-        if args.operating and epoch == args.epochs - 1:  # val_operating.json / .csv next to val_report.*
-            opr = operating.validation_operating(va["preds"], va["targets"], args, args.log_path)
-            print(f"epoch {epoch}: val {operating.stats_line(opr)}", flush=True)
-        if args.checklist and epoch == args.epochs - 1:  # val_checklist.json / .csv next to val_report.*
-            ckl = checklist.validation_checklist(va["preds"], va["targets"], args, args.log_path)
-            print(f"epoch {epoch}: val {checklist.stats_line(ckl)}", flush=True)
+        if epoch == args.epochs - 1:  # val_calibration / val_operating / val_checklist .json / .csv next to val_report.*
+            eval_cli.optional_reports(f"epoch {epoch}: val ", va["preds"], va["targets"], args, args.log_path)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG (backbone_eval.py:386,405-411)
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},

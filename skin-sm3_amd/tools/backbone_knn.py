@@ -6,7 +6,7 @@ src/models/evaluator.py) for each of the 8 derm7pt labels.
         --mean 0.7833 0.6712 0.6026 --std 0.2139 0.2472 0.2571 -b 128 -j 4 --img-sz 224 224 \
         --pretrain-path logs/backbone/ckp_399.pth --log-path logs/backbone/knn_399 --knn-k 200 --knn-t 0.07
 
-Takes backbone_eval's command line (and its checkpoint loader and data helpers) plus --knn-k / --knn-t.  The encoders are
+Takes backbone_eval's command line (and eval_cli's subject, batches and features) plus --knn-k / --knn-t.  The encoders are
 frozen and in eval mode (one fused conv + BN + ReLU kernel per layer); a case's feature is normalize(cat(derm_f, clinic_f))
 (sm3_normalize_rows), both splits through the validation chain (Resize -> Normalize of the whole image).  Per label the votes
 become fractions p = votes / sum(votes); AUC_AVG is sm3hip.metrics.auc_avg of log p (softmax(log p) = p) and top-1 is the
@@ -33,9 +33,9 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import backbone_eval  # noqa: E402
-from sm3hip import checklist, operating, report  # noqa: E402
+import eval_cli  # noqa: E402
+from sm3hip import report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
-from src.models.baseline import Baseline  # noqa: E402
 
 
 def get_parser():
@@ -49,71 +49,33 @@ def get_parser():
     return p
 
 
-def encode(evaluator, batches):
-    """normalize(cat(derm_f, clinic_f)) and the labels of every batch, concatenated."""
-    from sm3hip.knn import normalize
-    feats, labels = [], []
-    for derm, clinic, lab in batches:
-        f = torch.cat([evaluator.derm_backbone(derm), evaluator.clinic_backbone(clinic)], dim=1)
-        feats.append(normalize(f))
-        labels.append(lab)
-    return torch.cat(feats), torch.cat(labels)
-
-
-def random_features(n, d, dev, gen):
-    from sm3hip.knn import normalize
-    labels = torch.stack([torch.randint(0, c, (n,), device=dev, generator=gen) for c in NUM_CLASSES], dim=1)
-    return normalize(torch.randn(n, d, device=dev, generator=gen)), labels
-
-
 def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
-    operating.check_flags(args)
-    checklist.check_flags(args)
-    from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
-    require_baseline_arch(args.arch, "backbone_knn")
-    real = require_data(args, "backbone_knn")
-    if real and args.random_features:
-        raise SystemExit("backbone_knn: --random-features goes with --data-name synthetic")
-    if ignored_line(args, parser, real):
-        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
+    eval_cli.check_report_flags(args, calibration=False)
+
+    def check(real):
+        if real and args.random_features:
+            raise SystemExit("backbone_knn: --random-features goes with --data-name synthetic")
+    dev, gen, real = eval_cli.refuse_and_seed(args, parser, "backbone_knn", check)
+    evaluator = None if args.random_features else eval_cli.baseline_subject(args, dev, freeze=True, eval_mode=True)
     from sm3hip.knn import KNNBank, knn_scores
-    torch.manual_seed(args.seed)
-    dev = torch.device("cuda", 0)
-    gen = torch.Generator(device=dev).manual_seed(args.seed)
-    evaluator = None
-    if not args.random_features:
-        evaluator = Baseline(args.arch, args.arch_weights)
-        if args.pretrain_path and os.path.isfile(args.pretrain_path):
-            backbone_eval.load_ssl_backbones(evaluator, args.pretrain_path)
-            print(f"loaded pre-trained model weights from '{args.pretrain_path}'")
-        evaluator.freeze_backbone()
-        for m in (evaluator.derm_backbone, evaluator.clinic_backbone):
-            m.sm3_dtype = amp_dtype(args)
-        evaluator.to(dev).eval()
     if real:
-        from sm3hip.augment import chain
-        from sm3hip.imagestore import build_for
-        from src.utils.data.sampler import eval_batches
-        store = build_for(args, ["train", "test"], dev)
-        aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
-        split_data = lambda split: backbone_eval.real_batches(store, split, aug, eval_batches(len(split), args.batch_size),
-                                                              None, True)
-        bank_data, query_data = split_data(store.splits["train"]), split_data(store.splits["test"])
-    elif not args.random_features:
-        bank_data = (backbone_eval.synthetic(args.batch_size, args.img_sz, dev, gen) for _ in range(args.steps_per_epoch))
-        query_data = (backbone_eval.synthetic(args.batch_size, args.img_sz, dev, gen) for _ in range(args.val_steps))
+        store, aug = eval_cli.image_store(args, ["train", "test"], dev)
+        bank_data, query_data = (eval_cli.split_batches(args, store, store.splits[m], aug) for m in ("train", "test"))
+    elif not args.random_features:  # drawn inside the timed region: the bank, then the queries
+        bank_data, query_data = (eval_cli.synthetic_batches([args.batch_size] * n, args.img_sz, dev, gen)
+                                 for n in (args.steps_per_epoch, args.val_steps))
     torch.cuda.synchronize()
     t0 = time.time()
     with torch.no_grad():
         if args.random_features:
             n, b, d = args.random_features
-            bank_f, bank_t = random_features(n, d, dev, gen)
-            query_f, query_t = random_features(b, d, dev, gen)
+            bank_f, bank_t = eval_cli.random_features(n, d, dev, gen, normalize=True)
+            query_f, query_t = eval_cli.random_features(b, d, dev, gen, normalize=True)
         else:
-            bank_f, bank_t = encode(evaluator, bank_data)
-            query_f, query_t = encode(evaluator, query_data)
+            bank_f, bank_t = eval_cli.encode(evaluator, bank_data, normalize=True)
+            query_f, query_t = eval_cli.encode(evaluator, query_data, normalize=True)
         bank = KNNBank(bank_f, bank_t, NUM_CLASSES)
         votes = knn_scores(query_f, bank, k=args.knn_k, temperature=args.knn_t)
     torch.cuda.synchronize()
@@ -138,12 +100,7 @@ def main(argv=None):
           + " ".join(f"{n} {a:.3f}" for n, a in zip(CLASSES_NAME, top1))
           + f" | bank {bank.N} queries {query_f.shape[0]} | {stat['pairs_per_s']:.0f} pairs/s", flush=True)
     print(f"knn k={args.knn_k} T={args.knn_t}: {report.stats_line(stat, rep)}", flush=True)
-    if args.operating:  # val_operating.json / .csv next to val_report.*
-        opr = operating.validation_operating([p.log() for p in probs], query_t, args, args.log_path)
-        print(f"knn k={args.knn_k} T={args.knn_t}: {operating.stats_line(opr)}", flush=True)
-    if args.checklist:  # val_checklist.json / .csv next to val_report.*
-        ckl = checklist.validation_checklist([p.log() for p in probs], query_t, args, args.log_path)
-        print(f"knn k={args.knn_k} T={args.knn_t}: {checklist.stats_line(ckl)}", flush=True)
+    eval_cli.optional_reports(f"knn k={args.knn_k} T={args.knn_t}: ", [p.log() for p in probs], query_t, args, args.log_path)
     return stat
 
 

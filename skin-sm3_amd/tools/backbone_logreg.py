@@ -8,7 +8,7 @@ score is a function of (features, labels, C).
         --mean 0.7833 0.6712 0.6026 --std 0.2139 0.2472 0.2571 -b 128 -j 4 --img-sz 224 224 \
         --pretrain-path logs/backbone/ckp_399.pth --log-path logs/backbone/logreg_399 --logreg-select val
 
-Takes backbone_eval's command line (its checkpoint loader and data helpers, --bootstrap, --calibration, --operating, --checklist)
+Takes backbone_eval's command line (--bootstrap, --calibration, --operating, --checklist; eval_cli's subject, batches and features)
 plus the --logreg-* flags (--logreg-solver workgroup | lockstep picks the kernels of the fit, recorded in logreg_predictions.pt),
 --save-features and --random-features.  A case's feature is cat(derm_f, clinic_f) through the
 validation chain, then --logreg-normalize (standardize: per-feature mean and deviation of the train rows).
@@ -44,9 +44,9 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import backbone_eval  # noqa: E402
-from sm3hip import calibration, checklist, logreg, operating, report  # noqa: E402
+import eval_cli  # noqa: E402
+from sm3hip import logreg, report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
-from src.models.baseline import Baseline  # noqa: E402
 
 TOOL = "backbone_logreg"
 
@@ -111,20 +111,6 @@ def check_flags(args):
         raise SystemExit(f"{TOOL}: --random-features: at most {logreg.MAX_ROWS} train rows of width {logreg.MAX_DIM}")
 
 
-def encode(evaluator, batches):
-    """cat(derm_f, clinic_f) float32 and the labels of every batch, concatenated."""
-    feats, labels = [], []
-    for derm, clinic, lab in batches:
-        feats.append(torch.cat([evaluator.derm_backbone(derm), evaluator.clinic_backbone(clinic)], dim=1).float())
-        labels.append(lab)
-    return torch.cat(feats).contiguous(), torch.cat(labels)
-
-
-def random_features(n, d, dev, gen):
-    labels = torch.stack([torch.randint(0, c, (n,), device=dev, generator=gen) for c in NUM_CLASSES], dim=1)
-    return torch.randn(n, d, device=dev, generator=gen), labels
-
-
 def score_tables(fit, Xval, tval):
     """(auc, nll) [R, labels, Cs] float64 of every problem on the validation rows."""
     R, nl, nc = fit.weights.shape[0], len(fit.labels), len(fit.Cs)
@@ -143,52 +129,30 @@ def score_tables(fit, Xval, tval):
 def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
-    calibration.check_flags(args)
-    operating.check_flags(args)
-    checklist.check_flags(args)
+    eval_cli.check_report_flags(args)
     check_flags(args)
-    from src.utils.misc import amp_dtype, ignored_line, require_baseline_arch, require_data
-    require_baseline_arch(args.arch, TOOL)
-    real = require_data(args, TOOL)
-    if real and args.random_features:
-        raise SystemExit(f"{TOOL}: --random-features goes with --data-name synthetic")
-    if not real and not args.random_features and args.steps_per_epoch * args.batch_size > logreg.MAX_ROWS:
-        raise SystemExit(f"{TOOL}: {args.steps_per_epoch * args.batch_size} train rows, at most {logreg.MAX_ROWS} are supported")
-    if ignored_line(args, parser, real):
-        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
-    torch.manual_seed(args.seed)
-    dev = torch.device("cuda", 0)
-    gen = torch.Generator(device=dev).manual_seed(args.seed)
-    evaluator = None
-    if not args.random_features:
-        evaluator = Baseline(args.arch, args.arch_weights)
-        if args.pretrain_path and os.path.isfile(args.pretrain_path):
-            backbone_eval.load_ssl_backbones(evaluator, args.pretrain_path)
-            print(f"loaded pre-trained model weights from '{args.pretrain_path}'")
-        evaluator.freeze_backbone()
-        for m in (evaluator.derm_backbone, evaluator.clinic_backbone):
-            m.sm3_dtype = amp_dtype(args)
-        evaluator.to(dev).eval()
+
+    def check(real):
+        if real and args.random_features:
+            raise SystemExit(f"{TOOL}: --random-features goes with --data-name synthetic")
+        if not real and not args.random_features and args.steps_per_epoch * args.batch_size > logreg.MAX_ROWS:
+            raise SystemExit(f"{TOOL}: {args.steps_per_epoch * args.batch_size} train rows, at most {logreg.MAX_ROWS} are supported")
+    dev, gen, real = eval_cli.refuse_and_seed(args, parser, TOOL, check)
+    evaluator = None if args.random_features else eval_cli.baseline_subject(args, dev, freeze=True, eval_mode=True)
     if real:
-        from sm3hip.augment import chain
-        from sm3hip.imagestore import build_for
-        from src.utils.data.sampler import eval_batches
-        store = build_for(args, ["train", "valid", "test"], dev)
-        aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
-        split_data = lambda split: backbone_eval.real_batches(store, split, aug, eval_batches(len(split), args.batch_size),
-                                                              None, True)
-        data = [split_data(store.splits[m]) for m in ("train", "valid", "test")]
-    elif not args.random_features:
-        data = [[backbone_eval.synthetic(args.batch_size, args.img_sz, dev, gen) for _ in range(n)]
+        store, aug = eval_cli.image_store(args, ["train", "valid", "test"], dev)
+        data = [eval_cli.split_batches(args, store, store.splits[m], aug) for m in ("train", "valid", "test")]
+    elif not args.random_features:  # drawn before the timer starts: train, valid, test
+        data = [list(eval_cli.synthetic_batches([args.batch_size] * n, args.img_sz, dev, gen))
                 for n in (args.steps_per_epoch, args.val_steps, args.val_steps)]
     torch.cuda.synchronize()
     t0 = time.time()
     with torch.no_grad():
         if args.random_features:
             n, b, d = args.random_features
-            sets = [random_features(m, d, dev, gen) for m in (n, b, b)]
+            sets = [eval_cli.random_features(m, d, dev, gen) for m in (n, b, b)]
         else:
-            sets = [encode(evaluator, part) for part in data]
+            sets = [eval_cli.encode(evaluator, part) for part in data]
     torch.cuda.synchronize()
     encode_seconds = time.time() - t0
     (Xtr, ttr), (Xva, tva), (Xte, tte) = sets
@@ -271,15 +235,7 @@ def main(argv=None):
           + f" | {problems} problems ({not_ok} not converged), {iterations} iterations | {stat['pairs_per_s']:.0f} pairs/s | "
           f"fit {fit_seconds:.2f} s", flush=True)
     print(f"logreg {args.logreg_select}/{args.logreg_by}: {report.stats_line(stat, rep)}", flush=True)
-    if args.calibration:  # val_calibration.json / .csv next to val_report.*
-        cal = calibration.validation_calibration(preds, tte, args, args.log_path)
-        print(f"logreg: {calibration.stats_line(cal)}", flush=True)
-    if args.operating:  # val_operating.json / .csv next to val_report.*
-        opr = operating.validation_operating(preds, tte, args, args.log_path)
-        print(f"logreg: {operating.stats_line(opr)}", flush=True)
-    if args.checklist:  # val_checklist.json / .csv next to val_report.*
-        ckl = checklist.validation_checklist(preds, tte, args, args.log_path)
-        print(f"logreg: {checklist.stats_line(ckl)}", flush=True)
+    eval_cli.optional_reports("logreg: ", preds, tte, args, args.log_path)  # under the short prefix, as they always were
     return stat
 
 

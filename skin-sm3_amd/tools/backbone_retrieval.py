@@ -31,6 +31,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import backbone_train  # noqa: E402
+import eval_cli  # noqa: E402
 from sm3hip import retrieval  # noqa: E402
 
 EMBEDDINGS = "retrieval_embeddings.pt"
@@ -120,10 +121,8 @@ def count_cases(args, real, who="backbone_retrieval", least=1, most=None):
 def embed_held_out(args, parser, real):
     """Builds the model of these flags, loads --pretrain-path, and embeds the held-out pairs on cuda:0: (z_derm, z_clinic,
     labels [N, 8] int64 on the CPU or None for synthetic data, seconds)."""
-    from src.utils.misc import ignored_line
     model = build_model(args)
-    if ignored_line(args, parser, real):
-        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
+    eval_cli.ignored_notice(args, parser, real)
     if args.pretrain_path:
         load_checkpoint(model, args.pretrain_path)
         print(f"loaded pre-trained model weights from '{args.pretrain_path}'")
@@ -133,15 +132,9 @@ def embed_held_out(args, parser, real):
     model.to(dev).eval()
     labels = None
     if real:
-        from sm3hip.augment import chain
-        from sm3hip.imagestore import build_for
-        from src.utils.data.sampler import eval_batches
-        store = build_for(args, ["test"], dev)
-        split = store.splits["test"]
-        labels = split.labels.cpu()
-        aug = chain("backbone_eval", tuple(args.img_sz), args.mean, args.std)
-        pairs = ((store.augment(aug, split.derm_ids[sel], None, whole=True)[0],
-                  store.augment(aug, split.clinic_ids[sel], None, whole=True)[0]) for sel in eval_batches(len(split), args.batch_size))
+        store, aug = eval_cli.image_store(args, ["test"], dev)
+        labels = store.splits["test"].labels.cpu()
+        pairs = eval_cli.split_batches(args, store, store.splits["test"], aug, labels=False)
     else:
         pairs = synthetic_pairs(args.val_steps, args.batch_size, args.img_sz, dev, args.seed + 2000)
     torch.cuda.synchronize()

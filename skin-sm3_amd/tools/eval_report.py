@@ -43,12 +43,15 @@ import sys
 
 SCRIPT_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_PATH = os.path.split(SCRIPT_DIR)[0]
-sys.path.insert(0, ROOT_PATH)
+for _p in (ROOT_PATH, SCRIPT_DIR):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in device memory: see sm3hip/__init__.py
 
 import torch  # noqa: E402
 
+import eval_cli  # noqa: E402
 from sm3hip import calibration, checklist, operating, report, resample  # noqa: E402
 
 
@@ -59,9 +62,7 @@ def get_parser():
     p.add_argument("--out", default=None, help="directory of the JSON / CSV files (default: next to PRED.pt)")
     p.add_argument("--chunk", type=int, default=None, help="bootstrap replicates per launch (any value gives the same bits)")
     report.add_flags(p)
-    calibration.add_flags(p)
-    operating.add_flags(p)
-    checklist.add_flags(p)
+    eval_cli.add_report_flags(p)
     p.add_argument("--fit-on", metavar="OTHER.pt", default=None,
                    help="fit the temperatures on this predictions file; report PRED.pt at T = 1 and at the fitted T (implies --calibration)")
     return p
@@ -142,9 +143,7 @@ def check(args, preds, targets, kw, out, stem, dev):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
-    calibration.check_flags(args)
-    operating.check_flags(args)
-    checklist.check_flags(args)
+    eval_cli.check_report_flags(args)
     out = args.out or os.path.dirname(os.path.abspath(args.pred))
     stem = os.path.splitext(os.path.basename(args.pred))[0]
     kw = dict(bootstrap=args.bootstrap, confidence=args.confidence, seed=args.bootstrap_seed, chunk=args.chunk)

@@ -9,6 +9,7 @@ import time
 import torch
 
 import backbone_eval
+import eval_cli
 from sm3hip.attr import METHODS as ATTR_METHODS
 from sm3hip.cam import STAGES, TARGETS
 from sm3hip.faith import MODALITIES, MODES
@@ -200,9 +201,8 @@ def subject(args, parser, tool, mlc, check=None, freeze=False):
         raise SystemExit(f"{tool}: {flag} ({what}) is required with real data")
     if args.max_cases < 1:
         raise SystemExit(f"{tool}: --max-cases must be at least 1")
-    if not mlc and misc.ignored_line(args, parser, real):
-        print("accepted for compatibility, without effect in this build:", " ".join(misc.ignored_line(args, parser, real)),
-              flush=True)
+    if not mlc:
+        eval_cli.ignored_notice(args, parser, real)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(args.seed)
@@ -224,19 +224,16 @@ def batches(args, mlc, dev, gen, real):
     --max-cases cases of --split through the validation chain, or synthetic images."""
     size = image_size(args, mlc)
     if real:
-        from sm3hip.augment import chain
-        from sm3hip.imagestore import build_for
         from src.utils.data.sampler import eval_batches
-        store = build_for(args, [args.split], dev)
+        store, aug = eval_cli.image_store(args, [args.split], dev, size, "mlc_eval" if mlc else "backbone_eval")
         split = store.splits[args.split]
         n = min(args.max_cases, len(split))
-        aug = chain("mlc_eval" if mlc else "backbone_eval", size, args.mean, args.std)
         sels = [s[s < n] for s in eval_batches(len(split), args.batch_size)]
         sels = [s for s in sels if s.numel()]
-        return backbone_eval.real_batches(store, split, aug, sels, None, True), torch.cat(sels), args.split
+        return eval_cli.split_batches(args, store, split, aug, sels), torch.cat(sels), args.split
     n = args.max_cases
     sizes = [min(args.batch_size, n - s) for s in range(0, n, args.batch_size)]
-    return (backbone_eval.synthetic(b, size, dev, gen) for b in sizes), torch.arange(n), "synthetic"
+    return eval_cli.synthetic_batches(sizes, size, dev, gen), torch.arange(n), "synthetic"
 
 
 # ---- the loop ---------------------------------------------------------------------------------------------------------------

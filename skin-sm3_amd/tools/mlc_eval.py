@@ -30,14 +30,17 @@ import time
 
 SCRIPT_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_PATH = os.path.split(SCRIPT_DIR)[0]
-sys.path.insert(0, ROOT_PATH)
+for _p in (ROOT_PATH, SCRIPT_DIR):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in device memory: see sm3hip/__init__.py
 
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from sm3hip import calibration, checklist, operating, report  # noqa: E402
+import eval_cli  # noqa: E402
+from sm3hip import report  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.projector import build_mlc_projectors  # noqa: E402
 from src.models.simclr import SimCLRSkinV32  # noqa: E402
@@ -90,9 +93,7 @@ def get_parser():
     p.add_argument("--steps-per-epoch", type=int, default=8)
     p.add_argument("--val-steps", type=int, default=4)
     report.add_flags(p)
-    calibration.add_flags(p)
-    operating.add_flags(p)
-    checklist.add_flags(p)
+    eval_cli.add_report_flags(p)
     p.set_defaults(arch="resnet50", batch_size=128, finetune="projector", pretrain_path="", log_path="./logs/mlc_eval")
     return p
 
@@ -100,13 +101,6 @@ def get_parser():
 def set_requires_grad(module, flag):
     for p in module.parameters():
         p.requires_grad = flag
-
-
-def synthetic(bs, size, dev, gen):
-    derm = torch.randn(bs, 3, size[0], size[1], device=dev, generator=gen)
-    clinic = torch.randn(bs, 3, size[0], size[1], device=dev, generator=gen)
-    labels = torch.stack([torch.randint(0, n, (bs,), device=dev, generator=gen) for n in NUM_CLASSES], dim=1)
-    return derm, clinic, labels
 
 
 def set_train_modes(evaluator, finetune):
@@ -127,7 +121,7 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, dat
         evaluator.eval()
     preds_all, targets_all, total, t0 = [], [], 0.0, time.time()
     if data is None:
-        data = (synthetic(args.batch_size, args.img_sz, dev, gen) for _ in range(steps))
+        data = eval_cli.synthetic_batches([args.batch_size] * steps, args.img_sz, dev, gen)
     steps, pairs = 0, 0
     for derm, clinic, labels in data:
         steps += 1
@@ -161,15 +155,13 @@ def run_epoch(args, evaluator, criterion, optimizer, steps, gen, dev, train, dat
 def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
-    calibration.check_flags(args)
-    operating.check_flags(args)
-    checklist.check_flags(args)
-    from src.utils.misc import ignored_line, require_data, require_mlc_arch, require_mlc_proj
+    eval_cli.check_report_flags(args)
+    from src.utils.misc import require_data, require_mlc_arch, require_mlc_proj
     require_mlc_arch(args.arch, "mlc_eval")
     require_mlc_proj(args, "mlc_eval")
     real = require_data(args, "mlc_eval")
-    if real and ignored_line(args, parser, real):
-        print("accepted for compatibility, without effect in this build:", " ".join(ignored_line(args, parser, real)), flush=True)
+    if real:  # unlike the linear-probe tools (eval_cli.refuse_and_seed), no notice under synthetic data: kept as it was
+        eval_cli.ignored_notice(args, parser, real)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", 0)
     extractor = SimCLRSkinV32(arch=args.arch, proj_dim=args.extractor_proj_dim)
@@ -206,21 +198,15 @@ def main(argv=None):
     if real:
         from sm3hip.augment import chain
         from sm3hip.imagestore import build_for
-        from src.utils.data.sampler import eval_batches, train_batches
+        from src.utils.data.sampler import train_batches
         store = build_for(args, ["train", "test"], dev)
-        tsplit, vsplit = store.splits["train"], store.splits["test"]
         taug = chain("mlc_eval", (args.train_sz, args.train_sz), args.mean, args.std)
         vaug = chain("mlc_eval", (args.test_sz, args.test_sz), args.mean, args.std)
+        tsplit, vsplit = store.splits["train"], store.splits["test"]
         aug_gen = torch.Generator().manual_seed(args.seed + 1000)
-
-        def batches(split, aug, order, g, whole):
-            for sel in order:
-                derm = store.augment(aug, split.derm_ids[sel], g, whole=whole)[0]
-                clinic = store.augment(aug, split.clinic_ids[sel], g, whole=whole)[0]
-                yield derm, clinic, split.labels.index_select(0, sel.to(dev, non_blocking=True))
-        train_data = lambda epoch: batches(tsplit, taug, train_batches(len(tsplit), 1, 0, epoch, args.batch_size), aug_gen,
-                                           False)
-        val_data = lambda epoch: batches(vsplit, vaug, eval_batches(len(vsplit), args.batch_size), None, True)
+        train_data = lambda epoch: eval_cli.split_batches(
+            args, store, tsplit, taug, train_batches(len(tsplit), 1, 0, epoch, args.batch_size), aug_gen, whole=False)
+        val_data = lambda epoch: eval_cli.split_batches(args, store, vsplit, vaug)
     os.makedirs(args.log_path, exist_ok=True)
     best, history = -1.0, []
     for epoch in range(args.epochs):
@@ -236,15 +222,8 @@ def main(argv=None):
         print(f"epoch {epoch}: train loss {tr['loss']:.4f} AUC_AVG {tr['AUC_AVG']:.4f} {tr['pairs_per_s']:.0f} pairs/s | "
               f"val loss {va['loss']:.4f} AUC_AVG {va['AUC_AVG']:.4f}", flush=True)
         print(f"epoch {epoch}: val {report.stats_line(va, rep)}", flush=True)
-        if args.calibration and epoch == args.epochs - 1:  # val_calibration.json / .csv next to val_report.*
-            cal = calibration.validation_calibration(kept["preds"], kept["targets"], args, args.log_path)
-            print(f"epoch {epoch}: val {calibration.stats_line(cal)}", flush=True)
-        if args.operating and epoch == args.epochs - 1:  # val_operating.json / .csv next to val_report.*
-            opr = operating.validation_operating(kept["preds"], kept["targets"], args, args.log_path)
-            print(f"epoch {epoch}: val {operating.stats_line(opr)}", flush=True)
-        if args.checklist and epoch == args.epochs - 1:  # val_checklist.json / .csv next to val_report.*
-            ckl = checklist.validation_checklist(kept["preds"], kept["targets"], args, args.log_path)
-            print(f"epoch {epoch}: val {checklist.stats_line(ckl)}", flush=True)
+        if epoch == args.epochs - 1:  # val_calibration / val_operating / val_checklist .json / .csv next to val_report.*
+            eval_cli.optional_reports(f"epoch {epoch}: val ", kept["preds"], kept["targets"], args, args.log_path)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},

@@ -414,11 +414,11 @@ def test_backbone_saliency_on_synthetic_data(tmp_path, capsys):
     saved = torch.load(tmp_path / "sal" / "saliency.pt", map_location="cpu", weights_only=False)
     _check_maps(saved, 5, 64)
     # the maps of the first batch against direct gradients: regenerate it as the tool did (same seed, same generator)
-    import backbone_eval
+    import eval_cli
     dev = torch.device("cuda", 0)
     torch.manual_seed(9)
     gen = torch.Generator(device=dev).manual_seed(9)
-    derm, clinic, _ = backbone_eval.synthetic(3, [64, 64], dev, gen)
+    derm, clinic, _ = eval_cli.synthetic(3, [64, 64], dev, gen)
     model = Baseline("resnet18", None)
     bs.load_linear(model, str(path))
     for p in model.parameters():

@@ -120,6 +120,6 @@ def test_backbone_knn_parser_takes_a_run_sh_line_and_the_knn_flags():
     assert args.arch == "resnet50" and args.batch_size == 128 and args.img_sz == [224, 224] and args.amp
     args = bk.get_parser().parse_args(line + ["--knn-k", "50", "--knn-t", "0.1"])
     assert (args.knn_k, args.knn_t) == (50, 0.1)
-    # the helpers are backbone_eval's own, not copies
-    import backbone_eval
-    assert bk.backbone_eval is backbone_eval and bk.backbone_eval.load_ssl_backbones is backbone_eval.load_ssl_backbones
+    # the helpers are eval_cli's own, not copies
+    import eval_cli
+    assert bk.eval_cli is eval_cli and bk.eval_cli.load_ssl_backbones is eval_cli.load_ssl_backbones
