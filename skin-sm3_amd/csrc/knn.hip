@@ -13,6 +13,13 @@
 //   4. one thread per label adds exp(s / T) into its own classes in rank order (rank 0 first), no atomics: two calls on
 //      equal inputs give equal bits whatever the grid, and a label's sums do not depend on the other labels.
 // Every pass streams the row (N floats) from L2 / HBM; at large N the kernel is bound by those 5 reads.
+//
+// Values (pinned by tests/test_knn_edges_gpu.py).  Similarities are ordered as floats: +inf first, -inf last, denormals by
+// their value, -0 equal to +0; equal similarities go lower index first.  A +inf neighbour votes +inf, a -inf neighbour is a
+// neighbour like any other (it appears in nbr_idx / nbr_sim) and votes exactly 0.  A target outside [0, C_l) casts no vote
+// for label l; its row is still a neighbour.  Only the N valid columns of a row are read, whatever stands in [N, ld), and
+// rows of any alignment (any ld >= N, any base) give the same bits.  NaN similarities are outside the contract: where a
+// NaN ranks, and what it votes, is not defined.
 #include <math.h>
 
 #include "common.h"
