@@ -947,6 +947,35 @@ int sm3_checklist_counts(const int* packed, const int* order, const int* gs, con
                          int64_t r0, int c, int point, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Significance of a paired comparison: the integer counts behind the paired randomisation (permutation) test of two sets of
+ * predictions of the same cases, and the integer placements behind DeLong's test (csrc/signif.hip, sm3hip/significance.py,
+ * DESIGN.md 8.14; ABI 9, additive).
+ * N cases, T labels, K columns; colmap, targets as sm3_report_counts; yhat_a, yhat_b [N][T] int32 = the two models' predicted
+ * classes.  Per column the 2N scores are ranked jointly: element e = 2 i + w is model w's score of case i (w = 0: a, 1: b),
+ * sorted ascending and stably once; order, gs, ge [K][2N] int32 = the element at joint position j and the bounds of j's tie group.
+ * Replicate r swaps case i iff bit i & 31 of swap word i >> 5 is set, swap word d = word d % 4 of Philox4x32-10 (as
+ * sm3_attr_noise), key = (seed low word, seed high word), counter (d / 4, r, 0, 5) -- stream 5, apart from 0 to 4.  Side A' takes
+ * element w == swap_i of every case, side B' the other, yhat with it.  Per side, with positive = (y == c):
+ *   S[j] = the side's negative elements at joint positions < j,  A2 = sum over the side's positive elements j of (S[gs[j]] +
+ *   S[ge[j]]),  TP / FP = the side's elements with yhat == c that are positive / negative.
+ * sm3_signif_counts: out [c][K][2][3] int64 = (A2, TP, FP) of A' then B' for replicates r = r0 .. r0 + c - 1, one workgroup per
+ *   (replicate, label); a column whose label is outside [0, T) is left unwritten.  point != 0: nothing is swapped, c must be 1,
+ *   no random words.  A replicate is a function of (seed, r, N) alone.  1 <= N <= sm3_report_max_cases() (the case words and the
+ *   packed prefix sums of the 2N positions live in LDS), 1 <= T <= 64, 1 <= K <= 64, c >= 1, 0 <= r0, r0 + c <= 2^32; SM3_EINVAL
+ *   otherwise, before anything is launched; out 8-byte aligned (SM3_EALIGN).  Entries of order are clamped to 2N - 1 and of gs /
+ *   ge to 2N: no input can make an access leave its array.  Integers only, no atomics, no float anywhere.
+ * sm3_signif_placements: order, gs, ge [K][N] as sm3_report_counts' (ONE model's own ranking).  out [K][N] int32 in case order:
+ *   for a positive case 2 * (negatives ranked below) + tied negatives, in [0, 2Q]; for a negative case 2 * (positives ranked
+ *   above) + tied positives, in [0, 2P].  One workgroup per column; every entry is written when order is a permutation.
+ *   1 <= N <= sm3_report_max_cases(), 1 <= T, K <= 64; SM3_EINVAL otherwise; out 4-byte aligned.  The same clamps.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_signif_counts(const int* order, const int* gs, const int* ge, const int* targets, const int* yhat_a, const int* yhat_b,
+                      const int* colmap, int64_t* out, int N, int T, int K, uint64_t seed, int64_t r0, int c, int point,
+                      void* stream);
+int sm3_signif_placements(const int* order, const int* gs, const int* ge, const int* targets, const int* colmap, int32_t* out,
+                          int N, int T, int K, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Exact t-SNE maps of embeddings (csrc/tsne.hip, sm3hip/tsne.py; ABI 9, additive).  N points, 4 <= N <=
  * sm3_tsne_max_points() = 16384; every function refuses a null pointer or an N outside that range with SM3_EINVAL before anything
  * is launched, and a float / double pointer that is not 4 / 8-byte aligned with SM3_EALIGN (y: 8-byte, it is read as pairs).

@@ -1977,6 +1977,54 @@ def checklist_counts(packed, order, gs, ge, out, seed, r0, point=False):
                                                int(bool(point)), _stream()), "sm3_checklist_counts")
 
 
+def signif_counts(order, gs, ge, targets, yhat_a, yhat_b, colmap, out, seed, r0, point=False):
+    """out [c, K, 2, 3] int64 = (A2, TP, FP) of the sides A' and B' of the K columns for the swap replicates r0 .. r0 + c - 1 of
+    the paired randomisation test, or for the point record (point: c = 1, nothing swapped) (sm3_signif_counts).  order, gs, ge
+    [K, 2N] int32: per column the JOINT ranking of the two models' scores, element 2 * i + w = model w's score of case i, and
+    the bounds of each position's tie group; targets, yhat_a, yhat_b [N, T] int32; colmap [K, 2] int32 = (label, class)."""
+    for t, n in ((order, "order"), (gs, "gs"), (ge, "ge"), (targets, "targets"), (yhat_a, "yhat_a"), (yhat_b, "yhat_b"),
+                 (colmap, "colmap")):
+        _chk(t, torch.int32, n)
+    _chk(out, torch.int64, "out")
+    if order.dim() != 2 or targets.dim() != 2 or out.dim() != 4:
+        raise ValueError("signif_counts: order [K, 2N], targets [N, T] and out [c, K, 2, 3]")
+    K = order.shape[0]
+    N, T = targets.shape
+    c = out.shape[0]
+    if not 1 <= N <= REPORT_MAX_CASES:
+        raise ValueError(f"signif_counts: {N} cases, 1 to {REPORT_MAX_CASES} are supported")
+    if tuple(order.shape) != (K, 2 * N) or tuple(gs.shape) != (K, 2 * N) or tuple(ge.shape) != (K, 2 * N) or \
+            tuple(yhat_a.shape) != (N, T) or tuple(yhat_b.shape) != (N, T) or tuple(colmap.shape) != (K, 2) or \
+            tuple(out.shape) != (c, K, 2, 3):
+        raise ValueError("signif_counts: order, gs, ge [K, 2N], targets, yhat_a, yhat_b [N, T], colmap [K, 2] and out [c, K, 2, 3] "
+                         "do not match")
+    _replicates_chk("signif_counts", seed, point, c, "record")
+    with _prof("signif_counts", 0.0, 4.0 * 3 * K * 2 * N * c):
+        check(_lib.load().sm3_signif_counts(_ptr(order), _ptr(gs), _ptr(ge), _ptr(targets), _ptr(yhat_a), _ptr(yhat_b),
+                                            _ptr(colmap), _ptr(out), N, T, K, seed, int(r0), c, int(bool(point)), _stream()),
+              "sm3_signif_counts")
+
+
+def signif_placements(order, gs, ge, targets, colmap, out):
+    """out [K, N] int32, in case order = DeLong's placements times two of ONE model's own ranking (sm3_signif_placements): for a
+    positive case of column k 2 * (negatives ranked below) + tied negatives, for a negative one 2 * (positives ranked above) +
+    tied positives.  order, gs, ge [K, N] int32 as report.ranking forms them; targets [N, T] int32; colmap [K, 2] int32."""
+    for t, n in ((order, "order"), (gs, "gs"), (ge, "ge"), (targets, "targets"), (colmap, "colmap"), (out, "out")):
+        _chk(t, torch.int32, n)
+    if order.dim() != 2 or targets.dim() != 2 or out.dim() != 2:
+        raise ValueError("signif_placements: order [K, N], targets [N, T] and out [K, N]")
+    K, N = order.shape
+    T = targets.shape[1]
+    if not 1 <= N <= REPORT_MAX_CASES:
+        raise ValueError(f"signif_placements: {N} cases, 1 to {REPORT_MAX_CASES} are supported")
+    if tuple(gs.shape) != (K, N) or tuple(ge.shape) != (K, N) or tuple(targets.shape) != (N, T) or \
+            tuple(colmap.shape) != (K, 2) or tuple(out.shape) != (K, N):
+        raise ValueError("signif_placements: order, gs, ge, out [K, N], targets [N, T] and colmap [K, 2] do not match")
+    with _prof("signif_placements", 0.0, 4.0 * 4 * K * N):
+        check(_lib.load().sm3_signif_placements(_ptr(order), _ptr(gs), _ptr(ge), _ptr(targets), _ptr(colmap), _ptr(out), N, T, K,
+                                                _stream()), "sm3_signif_placements")
+
+
 def stem_wgrad_bn(dtype, x_nchw, dz, xo, mean, invstd, gamma, gsums, count, lsums, dgamma, dbeta, dw, views=1, slabs=None):
     """Stem weight gradient with bn1's backward apply fused into the operand load (sm3_stem_wgrad_bn; bf16 / fp16 / exact f32).
     slabs: fp32 workspace of STEM_WGRAD_SLABS * 64 * 147 floats -> fixed-order sum instead of float atomics."""

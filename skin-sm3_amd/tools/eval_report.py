@@ -36,6 +36,15 @@ PRED.pt: sens / spec / PPV / NPV at the transferred thresholds with their interv
 the DIAG head and the score of the annotated criteria; the rule "score >= k" at --checklist-thresholds; the agreement of the two
 scores) with the SAME bootstrap replicates, written to <name>_checklist.json / .csv, and with --against the paired difference
 (<name>_checklist_compare.json).
+
+    python tools/eval_report.py logs/finetune/val_predictions.pt --against logs/linear/val_predictions.pt --significance \
+        --permutations 10000 --permutation-seed 0
+
+--significance (needs --against) adds the significance tests of PRED against OTHER (sm3hip/significance.py): the paired
+randomisation test of every metric and column over --permutations swap replicates drawn from --permutation-seed, DeLong's test
+of the 24 class AUCs with its intervals at --confidence, McNemar's exact test of the argmax decisions per label, and the
+Holm-adjusted p-values; the table is printed and written to <name>_significance.json / .csv (long format).  Without the flag
+neither file is written.
 """
 import argparse
 import os
@@ -52,7 +61,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import eval_cli  # noqa: E402
-from sm3hip import calibration, checklist, operating, report, resample  # noqa: E402
+from sm3hip import calibration, checklist, operating, report, resample, significance  # noqa: E402
 
 
 def get_parser():
@@ -63,6 +72,11 @@ def get_parser():
     p.add_argument("--chunk", type=int, default=None, help="bootstrap replicates per launch (any value gives the same bits)")
     report.add_flags(p)
     eval_cli.add_report_flags(p)
+    p.add_argument("--significance", action="store_true",
+                   help="with --against: permutation, DeLong and McNemar tests of PRED against OTHER, Holm-adjusted")
+    p.add_argument("--permutations", type=int, default=significance.DEFAULT_PERMUTATIONS,
+                   help="swap replicates of the paired randomisation test")
+    p.add_argument("--permutation-seed", type=int, default=0, help="64-bit seed of the swap replicates")
     p.add_argument("--fit-on", metavar="OTHER.pt", default=None,
                    help="fit the temperatures on this predictions file; report PRED.pt at T = 1 and at the fitted T (implies --calibration)")
     return p
@@ -141,8 +155,27 @@ def check(args, preds, targets, kw, out, stem, dev):
     return result
 
 
+def signify(args, preds, targets, out, stem, dev):
+    """The --significance part: prints the table, writes the files, returns what it computed."""
+    other, other_targets = report.load_predictions(args.against, dev)
+    sig = significance.significance_report(preds, other, targets, permutations=args.permutations, seed=args.permutation_seed,
+                                           confidence=args.confidence, chunk=None, targets_b=other_targets)
+    print(f"significance of {args.pred} - {args.against}", flush=True)
+    print(significance.format_table(sig), flush=True)
+    significance.save(sig, out, stem + "_significance")
+    return {"significance": sig}
+
+
 def main(argv=None):
-    args = get_parser().parse_args(argv)
+    parser = get_parser()
+    args = parser.parse_args(argv)
+    if args.significance and not args.against:
+        parser.error("--significance compares two sets of predictions: it needs --against OTHER.pt")
+    if args.significance:
+        try:
+            significance.check_permutation_settings(args.permutations, args.permutation_seed, None, "--significance")
+        except ValueError as e:
+            parser.error(str(e))
     eval_cli.check_report_flags(args)
     out = args.out or os.path.dirname(os.path.abspath(args.pred))
     stem = os.path.splitext(os.path.basename(args.pred))[0]
@@ -162,6 +195,8 @@ def main(argv=None):
         print(report.format_compare(cmp), flush=True)
         resample.write_json(cmp, os.path.join(out, stem + "_compare.json"))
         result.update({"other": other, "compare": cmp})
+    if args.significance:
+        result.update(signify(args, preds, targets, out, stem, dev))
     if args.calibration or args.fit_on:
         result.update(calibrate(args, preds, targets, kw, out, stem, dev))
     if args.operating:
