@@ -947,6 +947,37 @@ int sm3_checklist_counts(const int* packed, const int* order, const int* gs, con
                          int64_t r0, int c, int point, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Conformal prediction-set report: split conformal thresholds from a calibration split, refitted in every bootstrap
+ * replicate, and the set counts of a test split under them (csrc/conformal.hip, sm3hip/conformal.py; ABI 9,
+ * additive).  Integers only.
+ *   cal_a [T][N_cal] int64 = the true-class score of a calibration case for label t; cal_order [T][N_cal] = the cases in
+ *   ascending cal_a, ties by case index (one stable sort per label); cal_y [N_cal][T], y [N][T] the classes; s [K][N] int64 the
+ *   score of column k = (label, class) = colmap[k], classes 0 .. 4; alpha: A levels (num, den) in HOST memory, the level is
+ *   num / den.  With multiplicities w on the calibration cases:
+ *     conditional 0 (marginal): n' = sum w = N_cal; conditional 1 (class): per class c of the label over the cases with y = c,
+ *       n' = sum w [y = c];
+ *     k = (n' + 1) - ((n' + 1) * num) / den in int64, integer division;
+ *     qhat = cal_a at the first position j of cal_order (of the class) with R_j + w_j >= k, R_j = the sum of w (of the class)
+ *       before j; qhat = 2^40, above any score, where k > n'.  The marginal qhat is the threshold of every class of the label.
+ *   With multiplicities m on the test cases, the set of case n is {c : s[col(t, c)][n] <= thr[c]} and the record of a (label,
+ *   level) is 24 int64: cov = sum m [true class in set], size = sum m |set|, single_hit = sum m [|set| = 1 and covered],
+ *   hist[0 .. 5] = sum m [|set| = k], then for c = 0 .. 4: n_c = sum m [y = c], cov_c = sum m [y = c][c in set], in_c = sum m
+ *   [c in set]; the slots of classes the label lacks are 0.  A y outside the label's classes counts in hist and size, is never
+ *   covered and belongs to no class.
+ * sm3_conformal_counts: counts [c][T][A][24] and thr [c][T][A][5] (the thresholds used; 0 in the slots of classes the label
+ *   lacks) for replicates r = r0 .. r0 + c - 1, one workgroup per (replicate, label).  point != 0: w = m = 1, c must be 1.
+ *   Otherwise m_r is the multiplicity vector of sm3_report_counts (counter (d / 4, r, 0, 2)) on N, and w_r follows the same
+ *   rule on N_cal with counter (d / 4, r, 0, 6), both with key = (seed low word, seed high word).  fixed_thr: NULL, or
+ *   [T][A][5] int64 thresholds used in every replicate instead of refitting (thr then repeats them).  1 <= N_cal, N <=
+ *   sm3_report_max_cases(), 1 <= T <= 64, 1 <= K <= 256, 1 <= A <= 8, every level with 0 < num < den, conditional 0 or 1,
+ *   c >= 1, 0 <= r0, r0 + c <= 2^32; SM3_EINVAL otherwise, before anything is launched.  Entries of cal_order are clamped to
+ *   N_cal - 1 and those of cal_y to the label's classes: no input can make an access leave its array.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_conformal_counts(const int64_t* cal_a, const int* cal_order, const int* cal_y, const int64_t* s, const int* y,
+                         const int* colmap, const int* alpha, const int64_t* fixed_thr, int64_t* counts, int64_t* thr, int N_cal,
+                         int N, int T, int K, int A, int conditional, uint64_t seed, int64_t r0, int c, int point, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Significance of a paired comparison: the integer counts behind the paired randomisation (permutation) test of two sets of
  * predictions of the same cases, and the integer placements behind DeLong's test (csrc/signif.hip, sm3hip/significance.py,
  * DESIGN.md 8.14; ABI 9, additive).

@@ -1,12 +1,13 @@
-// What the five bootstrap report kernels share (report.hip, calib.hip, operating.hip, retrieval.hip, checklist.hip: the
-// *_counts_kernel of each).
+// What the six bootstrap report kernels share (report.hip, calib.hip, operating.hip, retrieval.hip, checklist.hip,
+// conformal.hip: the *_counts_kernel of each).
 //
 // THE RESAMPLING RULE, stated here once for the device (sm3hip/resample.py states it for the host, DESIGN.md 8.10 in prose):
 // replicate r of N cases makes N draws; draw d hits case (w * N) >> 32 in 64-bit integers, w = word d % 4 of Philox4x32-10
 // (exact_f32.h) with key = the 64-bit seed (low word first) and counter (d / 4, r, 0, 2) -- the last word keeps the stream apart
 // from SmoothGrad's 0 and RISE's 1.  m_r[i] = the draws that hit case i; the point estimate has m = 1 and draws nothing.  m_r is
 // a function of (seed, r, N) alone, so with one seed replicate r resamples the same cases in every report: their intervals are
-// joint and their comparisons paired.
+// joint and their comparisons paired.  conformal.hip resamples a second split, the calibration cases, by the same rule with 6 as
+// the last counter word (0 to 5 are taken: sm3hip/resample.py, philox_words), so that one seed serves both splits.
 #pragma once
 #include "exact_f32.h"
 
@@ -20,10 +21,10 @@ constexpr int kMaxCases = 8192;            // sm3_report_max_cases(): m of a rep
 
 // m[0 .. N) in LDS = m_r of the rule above, counted by integer LDS atomics (`point`: all 1).  Whole workgroup; two barriers, the
 // second only when there were draws.  `also` runs before the first barrier: what it writes to LDS (retrieval.hip zeroes its
-// histogram there) is visible to every thread after the call.
+// histogram there) is visible to every thread after the call.  `word` is the last counter word: 2 for every report's own cases.
 template <typename Also>
 static __device__ __forceinline__ void resample_multiplicities(uint32_t* m, int N, uint32_t key0, uint32_t key1, uint32_t r,
-                                                               int point, Also also) {
+                                                               int point, uint32_t word, Also also) {
     const int tid = threadIdx.x;
     for (int i = tid; i < N; i += kThreads) m[i] = point ? 1u : 0u;
     also();
@@ -31,7 +32,7 @@ static __device__ __forceinline__ void resample_multiplicities(uint32_t* m, int 
     if (!point) {
         for (int q = tid; 4 * q < N; q += kThreads) {
             uint32_t w[4];
-            philox4x32_10((uint32_t)q, r, 0u, 2u, key0, key1, w);
+            philox4x32_10((uint32_t)q, r, 0u, word, key0, key1, w);
 #pragma unroll
             for (int l = 0; l < 4; ++l)
                 if (4 * q + l < N) atomicAdd(&m[(uint32_t)(((uint64_t)w[l] * (uint32_t)N) >> 32)], 1u);
@@ -40,9 +41,15 @@ static __device__ __forceinline__ void resample_multiplicities(uint32_t* m, int 
     }
 }
 
+template <typename Also>
+static __device__ __forceinline__ void resample_multiplicities(uint32_t* m, int N, uint32_t key0, uint32_t key1, uint32_t r,
+                                                               int point, Also also) {
+    resample_multiplicities(m, N, key0, key1, r, point, 2u, also);
+}
+
 static __device__ __forceinline__ void resample_multiplicities(uint32_t* m, int N, uint32_t key0, uint32_t key1, uint32_t r,
                                                                int point) {
-    resample_multiplicities(m, N, key0, key1, r, point, [] {});
+    resample_multiplicities(m, N, key0, key1, r, point, 2u, [] {});
 }
 
 static __device__ __forceinline__ int wave_sum(int v) {

@@ -1911,6 +1911,54 @@ def calib_counts(q, ev, order, slabel, xq, bins, sums, labels, binning, seed, r0
                                            _stream()), "sm3_calib_counts")
 
 
+CONFORMAL_MAX_LEVELS = 8
+CONFORMAL_MAX_CLASSES = 5
+CONFORMAL_RECORD = 24  # cov, size, single_hit, hist[0 .. 5], then (n_c, cov_c, in_c) of the classes 0 .. 4
+CONFORMAL_CONDITIONALS = ("marginal", "class")
+
+
+def conformal_counts(cal_a, cal_order, cal_y, s, y, colmap, alphas, counts, thr, conditional, seed, r0, point=False, fixed_thr=None):
+    """counts [c, T, A, 24] int64, the set counts of the test split, and thr [c, T, A, 5] int64, the thresholds they were counted
+    under, for bootstrap replicates r0 .. r0 + c - 1, or for the point estimate (point: c = 1, every case of both splits once)
+    (sm3_conformal_counts).  cal_a [T, N_cal] int64 = the true-class scores of the calibration cases, cal_order [T, N_cal] int32
+    = each label's cases in ascending cal_a (stable), cal_y [N_cal, T] int32; s [K, N] int64 = the scores of the test cases, y
+    [N, T] int32; colmap [K, 2] int32 = (label, class); alphas: A pairs of integers (num, den), the level num / den;
+    conditional: "marginal" or "class"; fixed_thr: None (thresholds refitted in every replicate) or [T, A, 5] int64."""
+    for t, n in ((cal_a, "cal_a"), (s, "s"), (counts, "counts"), (thr, "thr"), (fixed_thr, "fixed_thr")):
+        _chk(t, torch.int64, n)
+    for t, n in ((cal_order, "cal_order"), (cal_y, "cal_y"), (y, "y"), (colmap, "colmap")):
+        _chk(t, torch.int32, n)
+    if cal_a.dim() != 2 or s.dim() != 2 or counts.dim() != 4 or thr.dim() != 4:
+        raise ValueError("conformal_counts: cal_a [T, N_cal], s [K, N], counts [c, T, A, 24] and thr [c, T, A, 5]")
+    T, N_cal = cal_a.shape
+    K, N = s.shape
+    c, A = counts.shape[0], counts.shape[2]
+    for n, what in ((N_cal, "calibration"), (N, "test")):
+        if not 1 <= n <= REPORT_MAX_CASES:
+            raise ValueError(f"conformal_counts: {n} {what} cases, 1 to {REPORT_MAX_CASES} are supported")
+    if not 1 <= A <= CONFORMAL_MAX_LEVELS:
+        raise ValueError(f"conformal_counts: {A} levels, 1 to {CONFORMAL_MAX_LEVELS} are supported")
+    if tuple(cal_order.shape) != (T, N_cal) or tuple(cal_y.shape) != (N_cal, T) or tuple(y.shape) != (N, T) or \
+            tuple(colmap.shape) != (K, 2) or tuple(counts.shape) != (c, T, A, CONFORMAL_RECORD) or \
+            tuple(thr.shape) != (c, T, A, CONFORMAL_MAX_CLASSES) or \
+            (fixed_thr is not None and tuple(fixed_thr.shape) != (T, A, CONFORMAL_MAX_CLASSES)):
+        raise ValueError("conformal_counts: cal_a, cal_order [T, N_cal], cal_y [N_cal, T], s [K, N], y [N, T], colmap [K, 2], "
+                         "counts [c, T, A, 24], thr [c, T, A, 5] and fixed_thr [T, A, 5] do not match")
+    alphas = [tuple(a) for a in alphas]
+    if len(alphas) != A or not all(len(a) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in a)
+                                   and 0 < a[0] < a[1] < 2 ** 31 for a in alphas):
+        raise ValueError(f"conformal_counts: alphas must be {A} pairs of integers (num, den) with 0 < num < den < 2^31, got {alphas!r}")
+    if conditional not in CONFORMAL_CONDITIONALS:
+        raise ValueError(f"conformal_counts: conditional must be one of {CONFORMAL_CONDITIONALS}, got {conditional!r}")
+    _replicates_chk("conformal_counts", seed, point, c, one="record")
+    levels = (C.c_int * (2 * A))(*[v for a in alphas for v in a])
+    with _prof("conformal_counts", 0.0, (8.0 + 4 + 4) * N_cal * T * c + 8.0 * K * N * A * c):
+        check(_lib.load().sm3_conformal_counts(_ptr(cal_a), _ptr(cal_order), _ptr(cal_y), _ptr(s), _ptr(y), _ptr(colmap), levels,
+                                               _ptr(fixed_thr), _ptr(counts), _ptr(thr), N_cal, N, T, K, A,
+                                               CONFORMAL_CONDITIONALS.index(conditional), seed, int(r0), c, int(bool(point)),
+                                               _stream()), "sm3_conformal_counts")
+
+
 OPERATING_MAX_LEVELS = 32  # sm3_operating_max_levels(): entries of each of the two floor lists and of the fixed positions
 
 

@@ -45,6 +45,17 @@ randomisation test of every metric and column over --permutations swap replicate
 of the 24 class AUCs with its intervals at --confidence, McNemar's exact test of the argmax decisions per label, and the
 Holm-adjusted p-values; the table is printed and written to <name>_significance.json / .csv (long format).  Without the flag
 neither file is written.
+
+    python tools/eval_report.py logs/linear/test_predictions.pt --bootstrap 2000 --conformal --conformal-alpha 0.05 0.1 \
+        --conformal-conditional class --fit-on logs/linear/val_predictions.pt
+
+--conformal (needs --fit-on VAL.pt) adds the conformal prediction-set report (sm3hip/conformal.py): thresholds fitted on VAL.pt
+at the --conformal-alpha levels by --conformal-method lac|aps, one per label or (--conformal-conditional class) one per class;
+coverage, set size, empty and singleton sets and class-conditional coverage of PRED.pt.  The bootstrap resamples BOTH files and
+refits the thresholds in every replicate (--conformal-fixed: keeps the point thresholds); the test replicates are the SAME as
+every other report's.  --conformal-scaled divides the logits of both files by the temperatures fitted on VAL.pt.  Written to
+<name>_conformal.json / .csv, and with --against OTHER.pt plus --against-fit-on OTHER_VAL.pt (the same cases as VAL.pt) the
+paired difference to <name>_conformal_compare.json.
 """
 import argparse
 import os
@@ -61,7 +72,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import eval_cli  # noqa: E402
-from sm3hip import calibration, checklist, operating, report, resample, significance  # noqa: E402
+from sm3hip import calibration, checklist, conformal, operating, report, resample, significance  # noqa: E402
 
 
 def get_parser():
@@ -79,6 +90,9 @@ def get_parser():
     p.add_argument("--permutation-seed", type=int, default=0, help="64-bit seed of the swap replicates")
     p.add_argument("--fit-on", metavar="OTHER.pt", default=None,
                    help="fit the temperatures on this predictions file; report PRED.pt at T = 1 and at the fitted T (implies --calibration)")
+    conformal.add_flags(p)
+    p.add_argument("--against-fit-on", metavar="OTHER_VAL.pt", default=None,
+                   help="with --conformal and --against: the file OTHER.pt's thresholds are fitted on (the cases of --fit-on)")
     return p
 
 
@@ -155,6 +169,36 @@ def check(args, preds, targets, kw, out, stem, dev):
     return result
 
 
+def conform(args, preds, targets, kw, out, stem, dev, fit=None):
+    """The --conformal part: prints the tables, writes the files, returns what it computed.  fit: what calibrate() fitted on
+    --fit-on, when it ran."""
+    cal_preds, cal_targets = report.load_predictions(args.fit_on, dev)
+    if max(targets.shape[0], cal_targets.shape[0]) > report.MAX_CASES:
+        print(conformal.stats_line(None), flush=True)
+        return {}
+    ckw = dict(kw, **conformal.flag_settings(args))
+    if args.conformal_scaled:
+        fit = fit or calibration.fit_temperature(cal_preds, cal_targets)
+        ckw["temperature"] = fit["temperature"]
+    cfm = conformal.conformal_report(preds, targets, cal_preds, cal_targets, **ckw)
+    cfm["fit_on"] = args.fit_on
+    print(conformal.format_table(cfm), flush=True)
+    print(conformal.stats_line(cfm), flush=True)
+    conformal.save(cfm, out, stem + "_conformal")
+    result = {"conformal": cfm}
+    if args.against and args.against_fit_on:
+        other_cal = report.load_predictions(args.against_fit_on, dev)
+        if args.conformal_scaled:
+            ckw["temperature"] = calibration.fit_temperature(*other_cal)["temperature"]
+        other = conformal.conformal_report(*report.load_predictions(args.against, dev), *other_cal, **ckw)
+        cmp = conformal.compare(cfm, other)
+        print(f"{args.pred} - {args.against}", flush=True)
+        print(conformal.format_compare(cmp), flush=True)
+        resample.write_json(cmp, os.path.join(out, stem + "_conformal_compare.json"))
+        result.update({"conformal_other": other, "conformal_compare": cmp})
+    return result
+
+
 def signify(args, preds, targets, out, stem, dev):
     """The --significance part: prints the table, writes the files, returns what it computed."""
     other, other_targets = report.load_predictions(args.against, dev)
@@ -174,6 +218,13 @@ def main(argv=None):
     if args.significance:
         try:
             significance.check_permutation_settings(args.permutations, args.permutation_seed, None, "--significance")
+        except ValueError as e:
+            parser.error(str(e))
+    if args.conformal and not args.fit_on:
+        parser.error("--conformal fits its thresholds on a second split: it needs --fit-on VAL.pt")
+    if args.conformal:
+        try:
+            conformal.check_flags(args)
         except ValueError as e:
             parser.error(str(e))
     eval_cli.check_report_flags(args)
@@ -203,6 +254,8 @@ def main(argv=None):
         result.update(operate(args, preds, targets, kw, out, stem, dev))
     if args.checklist:
         result.update(check(args, preds, targets, kw, out, stem, dev))
+    if args.conformal:
+        result.update(conform(args, preds, targets, kw, out, stem, dev, result.get("fit")))
     return result
 
 
