@@ -1123,6 +1123,30 @@ int sm3_logreg_fit_lockstep(const float* X, const int32_t* targets, const double
                             int iters, double* ws, int64_t ws_doubles, double* coef, double* intercept, int32_t* info, double* res,
                             void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Test-time augmentation of the predictions (csrc/tta.hip, sm3hip/tta.py; ABI 9, additive).
+ * sm3_tta_dihedral: out [rows][n_g][3][H][W] f32 from x [rows][3][H][W] f32: copy e is element g = elements[e] (a HOST array of
+ *   n_g values 0 .. 7) of the dihedral group, g = fx | fy << 1 | tr << 2:
+ *     out[r][e][ch][y][x] = x[r][ch][y'][x'],  a = fy ? H - 1 - y : y,  b = fx ? W - 1 - x : x,  (y', x') = tr ? (b, a) : (a, b)
+ *   -- transpose the last two axes if tr, then reverse the rows if fy, then the columns if fx.  A pure copy (the bits of x).  Each
+ *   32 x 32 source tile is read once, into a 32 x 33 dword LDS tile (conflict-free by rows and by columns), and stored once per
+ *   element with every half-wave's store contiguous along the destination's x; edge tiles are clipped.  SM3_EINVAL, nothing
+ *   launched: a null pointer, rows / H / W < 1, n_g outside 1 .. 8, an element outside 0 .. 7, a transposing element with
+ *   H != W, more than 2^31 - 1 tiles.
+ * sm3_tta_reduce: logits [B][V][24] f32, the 24 columns the classes of the 8 labels in the order 5, 3, 2, 3, 3, 3, 3, 2.  Per
+ *   (case, view, label) in fp64: z = (double)logit, m = max z, e_c = exp(z_c - m), s = the sum of e_c in ascending c, p_c =
+ *   e_c / s, q_c = rint(p_c * 2^32) as int64 (Q32, round half to even) -> q [B][V][24].  Over the views of a case: sum_q, min_q,
+ *   max_q [B][24] int64.  view_class [B][V][8] int32: the lowest index of the maximum of the view's logits of the label;
+ *   agg_class [B][8] int32: the lowest index of the maximum of sum_q among the label's classes; disagree [B][8] int32: the
+ *   number of views with view_class != agg_class.  preds [B][24] f32 = (float)log((double)max(sum_q, 1) / (V * 2^32)): logits
+ *   whose softmax is the mean probability.  One wave per case, lane = view; everything that crosses lanes is an integer sum,
+ *   min, max or count, so no order of the views changes a bit.  The logits must be finite (the caller checks).  SM3_EINVAL: a
+ *   null pointer, B < 1, V outside 1 .. 64.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_tta_dihedral(const float* x, int rows, int H, int W, const int* elements, int n_g, float* out, void* stream);
+int sm3_tta_reduce(const float* logits, int B, int V, int64_t* q, int64_t* sum_q, int64_t* min_q, int64_t* max_q,
+                   int32_t* view_class, int32_t* agg_class, int32_t* disagree, float* preds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,8 @@ SIGNATURES = {
     "sm3_logreg_batch_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P, _P],
     "sm3_logreg_value_grad_lockstep": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P],
     "sm3_logreg_fit_lockstep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P],
+    "sm3_tta_dihedral": [_P, _I, _I, _I, _P, _I, _P, _P],
+    "sm3_tta_reduce": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -2445,3 +2445,49 @@ def knn_vote(S, n_valid, targets, class_offsets, k, temperature, scores, nbr_idx
     with _prof("knn_vote", 0.0, 4.0 * 4 * B * n_valid):  # bytes: the 4 select passes over S
         check(_lib.load().sm3_knn_vote(_ptr(S), B, n_valid, ld, _ptr(targets), L, off, int(k), float(temperature),
                                        _ptr(scores), _ptr(nbr_idx), _ptr(nbr_sim), _stream()), "sm3_knn_vote")
+
+
+# ------------------------------------------------------------------------------------------
+# test-time augmentation of the predictions (sm3hip/tta.py, csrc/tta.hip)
+# ------------------------------------------------------------------------------------------
+TTA_MAX_VIEWS = 64  # one wave of sm3_tta_reduce: lane = view
+TTA_COLUMNS = 24    # sum(metrics.NUM_CLASSES)
+
+
+def tta_dihedral(x, elements, out):
+    """out [rows, G, 3, H, W] fp32 = the G dihedral copies elements[e] (0 .. 7: fx | fy << 1 | tr << 2) of x [rows, 3, H, W]
+    (sm3_tta_dihedral): transpose if tr, then reverse the rows if fy, then the columns if fx.  Refused before the device is
+    touched: an element outside 0 .. 7, more than 8 of them, a transposing element with H != W."""
+    els = [int(g) for g in elements]
+    if not 1 <= len(els) <= 8 or any(not 0 <= g <= 7 for g in els):
+        raise ValueError(f"tta_dihedral: 1 to 8 elements in 0 .. 7, got {els}")
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 1 or x.shape[3] < 1:
+        raise ValueError("tta_dihedral: x must be [rows >= 1, 3, H, W]")
+    rows, _, H, W = x.shape
+    if H != W and any(g & 4 for g in els):
+        raise ValueError(f"tta_dihedral: a transposing element needs a square image, got {H} x {W}")
+    _chk(x, torch.float32, "x"); _chk(out, torch.float32, "out")
+    if tuple(out.shape) != (rows, len(els), 3, H, W):
+        raise ValueError(f"tta_dihedral: out must be [{rows}, {len(els)}, 3, {H}, {W}]")
+    arr = (C.c_int * len(els))(*els)
+    with _prof("tta_dihedral", 0.0, 4.0 * (x.numel() + out.numel())):
+        check(_lib.load().sm3_tta_dihedral(_ptr(x), rows, H, W, arr, len(els), _ptr(out), _stream()), "sm3_tta_dihedral")
+
+
+def tta_reduce(logits, q, sum_q, min_q, max_q, view_class, agg_class, disagree, preds):
+    """The view reduction of logits [B, V, 24] fp32 (sm3_tta_reduce): q [B, V, 24], sum_q / min_q / max_q [B, 24] int64;
+    view_class [B, V, 8], agg_class / disagree [B, 8] int32; preds [B, 24] fp32."""
+    if logits.dim() != 3 or logits.shape[0] < 1 or logits.shape[2] != TTA_COLUMNS or not 1 <= logits.shape[1] <= TTA_MAX_VIEWS:
+        raise ValueError(f"tta_reduce: logits must be [B >= 1, 1 <= V <= {TTA_MAX_VIEWS}, {TTA_COLUMNS}]")
+    B, V, K = logits.shape
+    _chk(logits, torch.float32, "logits"); _chk(preds, torch.float32, "preds")
+    for t, name, shape, dt in ((q, "q", (B, V, K), torch.int64), (sum_q, "sum_q", (B, K), torch.int64),
+                               (min_q, "min_q", (B, K), torch.int64), (max_q, "max_q", (B, K), torch.int64),
+                               (view_class, "view_class", (B, V, 8), torch.int32), (agg_class, "agg_class", (B, 8), torch.int32),
+                               (disagree, "disagree", (B, 8), torch.int32), (preds, "preds", (B, K), torch.float32)):
+        _chk(t, dt, name)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"tta_reduce: {name} must be {list(shape)}")
+    with _prof("tta_reduce", 0.0, 4.0 * logits.numel() + 8.0 * q.numel()):
+        check(_lib.load().sm3_tta_reduce(_ptr(logits), B, V, _ptr(q), _ptr(sum_q), _ptr(min_q), _ptr(max_q), _ptr(view_class),
+                                         _ptr(agg_class), _ptr(disagree), _ptr(preds), _stream()), "sm3_tta_reduce")

@@ -22,6 +22,11 @@ Any other value fine-tunes everything through the autograd bridge.
 (sm3hip/imagestore.py); training one pass over the train split per epoch with the reference's chain (backbone_eval.py:234-262:
 RandomResizedCrop(img_sz, scale=(0.5, 1)) -> flip -> Normalize) on the GPU, validation on the test split with Resize(img_sz)
 -> Normalize and its real labels; the validation predictions of the last epoch are saved as val_predictions.pt.
+--tta hflip|flips|d4 (sm3hip.tta) adds, after the last epoch's validation pass, one more pass over the same cases that averages the
+predicted probabilities over the group's views of every case (--tta-crops 5: of a centre and four corner crops of --tta-crop-scale
+each, real data only), prints its AUC_AVG and how much the predictions move across the views, and under real data saves
+val_predictions_tta.pt in val_predictions.pt's format: `eval_report.py val_predictions_tta.pt --against val_predictions.pt
+--significance` is the paired comparison.
 `--data-name synthetic`: random images and labels, --steps-per-epoch / --val-steps steps.
 """
 import argparse
@@ -41,13 +46,14 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
 import eval_cli  # noqa: E402
-from sm3hip import report  # noqa: E402
+from sm3hip import report, tta  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, auc_avg  # noqa: E402
 
 
-def get_parser(calibration_flags=True):
+def get_parser(calibration_flags=True, tta_flags=True):
     """src/utils/misc.py:get_parser + tools/backbone_eval.py:434-440 of the reference, then this build's own flags
-    (calibration_flags=False: without --calibration and its two settings, for backbone_knn, whose votes are not logits)."""
+    (calibration_flags=False: without --calibration and its two settings, for backbone_knn, whose votes are not logits;
+    tta_flags=False: without --tta and its two settings, for the tools on frozen features)."""
     from src.utils.misc import get_parser as base_parser
     p = base_parser("SM3 linear probe / fine-tune (MI355X)")
     p.add_argument("--arch-weights", type=str, default=None)
@@ -58,6 +64,8 @@ def get_parser(calibration_flags=True):
     p.add_argument("--val-steps", default=4, type=int)
     report.add_flags(p)
     eval_cli.add_report_flags(p, calibration=calibration_flags)
+    if tta_flags:
+        tta.add_flags(p)
     p.set_defaults(arch="resnet50", epochs=50, batch_size=128)
     return p
 
@@ -105,7 +113,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     eval_cli.check_report_flags(args)
     from src.utils.misc import amp_dtype
-    dev, gen, real = eval_cli.refuse_and_seed(args, parser, "backbone_eval")
+    dev, gen, real = eval_cli.refuse_and_seed(args, parser, "backbone_eval", check=lambda real: tta.check_flags(args, real))
     evaluator = eval_cli.baseline_subject(args, dev, freeze=args.finetune == "fc", eval_mode=False)
     args.scaler = torch.amp.GradScaler("cuda", enabled=amp_dtype(args) == torch.float16)  # backbone_eval.py:271
     params = [p for p in evaluator.parameters() if p.requires_grad]
@@ -136,6 +144,9 @@ def main(argv=None):
         print(f"epoch {epoch}: val {report.stats_line(va, rep)}", flush=True)
         if epoch == args.epochs - 1:  # val_calibration / val_operating / val_checklist .json / .csv next to val_report.*
             eval_cli.optional_reports(f"epoch {epoch}: val ", va["preds"], va["targets"], args, args.log_path)
+            if args.tta != "none":  # one more pass over the same validation cases, every view of each
+                eval_cli.tta_pass(f"epoch {epoch}: ", evaluator, args, epoch, dev, gen, store if real else None,
+                                  vsplit if real else None, args.img_sz)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG (backbone_eval.py:386,405-411)
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},

@@ -39,7 +39,7 @@ from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 
 
 def get_parser():
-    p = backbone_eval.get_parser(calibration_flags=False)
+    p = backbone_eval.get_parser(calibration_flags=False, tta_flags=False)
     p.description = "SM3 weighted kNN evaluation (MI355X)"
     p.add_argument("--knn-k", default=200, type=int, help="neighbours per query (1..1024, at most the bank size)")
     p.add_argument("--knn-t", default=0.07, type=float, help="temperature of the exp(s / T) weights")

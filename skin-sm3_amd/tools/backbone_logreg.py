@@ -52,7 +52,7 @@ TOOL = "backbone_logreg"
 
 
 def get_parser():
-    p = backbone_eval.get_parser()
+    p = backbone_eval.get_parser(tta_flags=False)
     p.description = "SM3 L-BFGS logistic-regression probe (MI355X)"
     p.add_argument("--logreg-c", type=float, nargs="+", default=list(logreg.DEFAULT_CS),
                    help="the grid of C (default: 16 values log-spaced over 1e-4 .. 1e4)")

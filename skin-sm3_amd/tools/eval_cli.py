@@ -131,6 +131,34 @@ def synthetic_batches(sizes, size, dev, gen):
     return (synthetic(bs, size, dev, gen) for bs in sizes)
 
 
+# ---- test-time augmentation ---------------------------------------------------------------------------------------------------
+def tta_pass(prefix, evaluator, args, epoch, dev, gen, store, split, size):
+    """One pass of sm3hip.tta over the validation cases -- the split of the image store, or --val-steps further synthetic
+    batches when store is None -- with the eval-mode model: prints prefix + "val-tta AUC_AVG ... | " + tta.stats_line and, with
+    a store, saves val_predictions_tta.pt (val_predictions.pt's keys plus "tta").  Returns the record."""
+    import os
+
+    from sm3hip import tta
+    from sm3hip.metrics import auc_avg
+    evaluator.eval()
+    if store is not None:
+        rec = tta.predict_split(evaluator, store, split, tuple(size), args.mean, args.std, args.tta, args.tta_crops,
+                                args.tta_crop_scale, args.batch_size)
+    else:
+        batches = list(synthetic_batches([args.batch_size] * args.val_steps, size, dev, gen))
+        rec = tta.predict(evaluator, torch.cat([b[0] for b in batches]), torch.cat([b[1] for b in batches]), args.tta,
+                          chunk=args.batch_size)
+        rec["targets"] = torch.cat([b[2] for b in batches])
+    _, avg = auc_avg(rec["preds"], rec["targets"])
+    rec["AUC_AVG"] = float(avg)
+    if store is not None:
+        torch.save({"epoch": epoch + 1, "preds": [p.cpu() for p in rec["preds"]], "targets": rec["targets"].cpu(),
+                    "AUC_AVG": rec["AUC_AVG"], "tta": tta.tool_record(rec, args.tta_crop_scale)},
+                   os.path.join(args.log_path, "val_predictions_tta.pt"))
+    print(f"{prefix}val-tta AUC_AVG {rec['AUC_AVG']:.4f} | {tta.stats_line(rec)}", flush=True)
+    return rec
+
+
 # ---- features ---------------------------------------------------------------------------------------------------------------
 def encode(evaluator, batches, normalize=False):
     """cat(derm_f, clinic_f) as float32 -- normalize=True: as unit rows (sm3hip.knn.normalize) -- and the labels of every

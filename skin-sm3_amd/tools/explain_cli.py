@@ -24,7 +24,7 @@ FAITH_METHODS = ("cam", "ig", "smoothgrad", "random", "rise")
 # ---- parsers ----------------------------------------------------------------------------------------------------------------
 def backbone_parser(description):
     """backbone_eval's command line plus --linear-path."""
-    p = backbone_eval.get_parser()
+    p = backbone_eval.get_parser(tta_flags=False)
     p.description = description
     p.add_argument("--linear-path", type=str, default=None,
                    help="backbone_eval's best_linear.pth (a Baseline state_dict); required with real data")
@@ -34,7 +34,7 @@ def backbone_parser(description):
 def mlc_parser(description, log_path):
     """mlc_eval's command line plus --checkpoint, with the tool's own --log-path default."""
     import mlc_eval
-    p = mlc_eval.get_parser()
+    p = mlc_eval.get_parser(tta_flags=False)
     p.description = description
     p.add_argument("--checkpoint", type=str, default=None,
                    help="a checkpoint inference.py loads (best_linear.pth / best_finetune.pth); required with real data")

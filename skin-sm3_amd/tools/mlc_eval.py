@@ -7,6 +7,9 @@ val_report.json / val_report.csv (--bootstrap B: with intervals) and, under real
 --calibration adds val_calibration.json / .csv of that pass at T = 1 (sm3hip.calibration; --calib-bins, --calib-binning).
 --operating adds val_operating.json / .csv of that pass (sm3hip.operating; --operating-spec, --operating-sens, --operating-decision).
 --checklist adds val_checklist.json / .csv of that pass (sm3hip.checklist; --checklist-thresholds).
+--tta hflip|flips|d4 adds one more pass over the same cases after the last epoch, averaged over the group's views of every case
+(sm3hip.tta; --tta-crops, --tta-crop-scale): its AUC_AVG, the stability of the predictions across views and, under real data,
+val_predictions_tta.pt.
 
     python tools/mlc_eval.py --data-name synthetic -a resnet50 -b 128 -lr 1e-3 --epochs 2 --mlc-proj v4 \
         --mlc-proj-dim 512 --num-heads 1 --sa-dim-ff 128 --sa-dropout 0.1 --finetune projector \
@@ -40,7 +43,7 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
 import eval_cli  # noqa: E402
-from sm3hip import report  # noqa: E402
+from sm3hip import report, tta  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.projector import build_mlc_projectors  # noqa: E402
 from src.models.simclr import SimCLRSkinV32  # noqa: E402
@@ -72,8 +75,9 @@ class Model(nn.Module):
         return mlc.heads_forward(self, feats)[1]
 
 
-def get_parser():
-    """src/utils/misc.py:get_parser + tools/mlc_eval.py:509-524 of the reference, then this build's own flags."""
+def get_parser(tta_flags=True):
+    """src/utils/misc.py:get_parser + tools/mlc_eval.py:509-524 of the reference, then this build's own flags (tta_flags=False:
+    without --tta and its two settings, for the explanation tools)."""
     from src.utils.misc import get_parser as base_parser
     p = base_parser("SM3 multi-label eval / fine-tune (MI355X)")
     p.add_argument("--mlc-proj", type=str, default="v4")
@@ -94,8 +98,25 @@ def get_parser():
     p.add_argument("--val-steps", type=int, default=4)
     report.add_flags(p)
     eval_cli.add_report_flags(p)
+    if tta_flags:
+        tta.add_flags(p)
     p.set_defaults(arch="resnet50", batch_size=128, finetune="projector", pretrain_path="", log_path="./logs/mlc_eval")
     return p
+
+
+def inference_twin(evaluator, args, dev):
+    """inference.py's Model with the evaluator's weights, as inference.py loads a best_finetune.pth ("encoder." dropped from the
+    keys, strict), its encoders in the evaluator's arithmetic mode, in eval mode: the form of the model that sm3hip.tta takes."""
+    import inference
+    from src.utils.misc import amp_dtype
+    ext = inference.Extractor(args.arch)
+    twin = inference.Model(ext, build_mlc_projectors(args.mlc_proj, ext.derm_feat_dim + ext.clinic_feat_dim, args.mlc_proj_dim,
+                                                     args.num_labels),
+                           args.mlc_proj_dim, args.l2_norm, args.num_heads, args.sa_dim_ff, args.sa_dropout)
+    twin.load_state_dict({k.replace("encoder.", ""): v for k, v in evaluator.state_dict().items()}, strict=True)
+    for b in (ext.derm_backbone, ext.clinic_backbone):
+        b.sm3_dtype = amp_dtype(args)
+    return twin.to(dev).eval()
 
 
 def set_requires_grad(module, flag):
@@ -160,6 +181,8 @@ def main(argv=None):
     require_mlc_arch(args.arch, "mlc_eval")
     require_mlc_proj(args, "mlc_eval")
     real = require_data(args, "mlc_eval")
+    val_sz = (args.test_sz, args.test_sz) if real else tuple(args.img_sz)
+    tta.check_flags(args, real, val_sz)
     if real:  # unlike the linear-probe tools (eval_cli.refuse_and_seed), no notice under synthetic data: kept as it was
         eval_cli.ignored_notice(args, parser, real)
     torch.manual_seed(args.seed)
@@ -224,6 +247,9 @@ def main(argv=None):
         print(f"epoch {epoch}: val {report.stats_line(va, rep)}", flush=True)
         if epoch == args.epochs - 1:  # val_calibration / val_operating / val_checklist .json / .csv next to val_report.*
             eval_cli.optional_reports(f"epoch {epoch}: val ", kept["preds"], kept["targets"], args, args.log_path)
+            if args.tta != "none":  # one more pass over the same validation cases, every view of each
+                eval_cli.tta_pass(f"epoch {epoch}: ", inference_twin(evaluator, args, dev), args, epoch, dev, gen,
+                                  store if real else None, vsplit if real else None, val_sz)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},
