@@ -54,6 +54,33 @@ def need_f32(t, what):
     assert bool(torch.isfinite(t).all()) and torch.equal(t.float().double(), t), f"{what}: not exact in fp32"
 
 
+def ep_affine_exact(gamma, beta, rm, rv, eps, what):
+    """ep_affine (csrc/conv_common.h) step by step in fp64, every intermediate asserted to be an fp32 value (so that the fp32
+    operation that produces it is exact, contracted into an fma or not): rv + eps, its square root, the reciprocal,
+    g * invstd, rm * g, that times invstd, and the subtraction.  gamma / beta None: 1 / 0.  -> (scale, shift), fp64."""
+    var = rv + eps
+    need_f32(var, f"{what}: rv + eps")
+    sd = var.sqrt()
+    need_f32(sd, f"{what}: sqrt(rv + eps)")
+    assert torch.equal(sd * sd, var), f"{what}: sqrt(rv + eps) is not exact"
+    invstd = 1.0 / sd
+    need_f32(invstd, f"{what}: 1 / sqrt(rv + eps)")
+    assert torch.equal(invstd * sd, torch.ones_like(sd)), f"{what}: the reciprocal is not exact"
+    g = torch.ones_like(rv) if gamma is None else gamma
+    b = torch.zeros_like(rv) if beta is None else beta
+    for t, nm in ((g, "gamma"), (b, "beta"), (rm, "running_mean"), (rv, "running_var")):
+        need_f32(t, f"{what}: {nm}")
+    scale = g * invstd
+    need_f32(scale, f"{what}: g * invstd")
+    t = rm * g
+    need_f32(t, f"{what}: rm * g")
+    t = t * invstd
+    need_f32(t, f"{what}: rm * g * invstd")
+    shift = b - t
+    need_f32(shift, f"{what}: b - rm * g * invstd")
+    return scale, shift
+
+
 def need_exact64(abs_sum, q, what):
     """need_exact for an fp64 accumulation: below 2^53 quanta."""
     worst = float(abs_sum.max()) / q if abs_sum.numel() else 0.0

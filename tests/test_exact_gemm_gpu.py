@@ -16,12 +16,18 @@ Contracts pinned here besides the values: the ReLU bits are `stored y > 0` (stri
 rows of a forward launch are the sums of the rounded GEMM result (before an addend); a fused BN-backward launch without x
 writes 0 into the sum(dz * xhat) slot; outputs are compared with +0 and -0 identified.  Every output is a slice of a larger
 buffer filled with a sentinel, and the bytes around it must come back unchanged.
+
+sm3_conv_bn_eval -- the one launch of every frozen-encoder forward, scale / shift derived per output channel in the epilogue
+(ep_affine, csrc/conv_common.h) -- runs the whole forward table next to sm3_conv_bn_act_eval: BatchNorm tensors with
+running_var a power of four and eps = 0 make every step of the derivation exact (bn_operands), so its outputs equal fp64
+and the other entry point's bits; on real values the two are compared bit for bit over the same table.
 """
 import pytest
 import torch
 import torch.nn.functional as F
 
-from exact_inputs import SENTINEL, Guarded, _dev, draw, env, mask_bytes, need_exact, need_repr, quantum, same
+from exact_inputs import (SENTINEL, Guarded, _dev, draw, env, ep_affine_exact, mask_bytes, need_exact, need_repr, pick,
+                          quantum, same)
 
 F32, BF16, F16 = torch.float32, torch.bfloat16, torch.float16
 DTYPES = [F32, BF16, F16]
@@ -102,6 +108,8 @@ VIEW2_CASES = [("v2_1x1", 2, 8, 16, 192, 24, 1, 1, 0), ("v2_3x3", 4, 8, 8, 64, 1
                ("v2_3x3_72", 2, 16, 16, 320, 72, 3, 1, 1)]
 # the deep K loop's threshold: 256 and 257 blocks of 128 x 64
 DEEP_CASES = [("deep256", 2, 128, 128, 64, 64, 3, 1, 1), ("deep257", 1, 257, 128, 64, 64, 3, 1, 1)]
+# the case on which sm3_conv_bn_eval's gamma-alone and beta-alone forms are pinned (Co tail in a 128-column tile, M = 30)
+HALF_AFFINE_CASE = FWD_CASES[8]
 # weight-gradient channel counts (multiples of 8)
 WGRAD_CH = [(8, 8), (24, 40), (40, 24), (8, 136)]
 
@@ -150,7 +158,51 @@ def fwd_case(dt, case, regime, seed, views=1):
     for t, nm in ((y + res, "y + addend"), (aff, "affine"), (aff + res, "affine + residual")):
         need_repr(t, dt, f"{name}: {nm}")
         need_repr(t, F32, f"{name}: {nm} (fp32)")
+    if views == 1:  # (drawn last: the operands above are those of the earlier forms, value for value)
+        bn_operands(c, g)
     return c
+
+
+RV_VALUES = (0.25, 1.0, 4.0, 16.0)  # powers of four: sqrtf and the reciprocal are exact
+
+
+def bn_operands(c, g):
+    """BatchNorm tensors of sm3_conv_bn_eval for the forward case c (one view, eps = 0), in two sets.
+    Affine: gamma, beta, rm, rv from which ep_affine derives exactly the case's dyadic scale / shift (so `aff` is its reference
+    too): rv a power of four, gamma = scale * sqrt(rv), rm a small integer, beta = shift + rm * scale.
+    No affine (gamma = beta = NULL): scale_na = 1 / sqrt(rv), shift_na = -rm / sqrt(rv), reference aff_na.
+    gamma alone / beta alone (the header: the missing one is 1 / 0): references aff_g / aff_b, checked where a test uses them
+    (half_affine_refs)."""
+    name, dt, Co, y = c["name"], c["dt"], c["Co"], c["y"]
+    scale, shift = c["scale"][0], c["shift"][0]
+    rv = pick(g, torch.tensor(RV_VALUES, dtype=torch.float64), (Co,))
+    rm = draw(g, (Co,), 3, 0.8, 0)
+    gamma = scale * rv.sqrt()
+    beta = shift + rm * scale
+    sc, sh = ep_affine_exact(gamma, beta, rm, rv, 0.0, f"{name}: BatchNorm operands")
+    assert torch.equal(sc, scale) and torch.equal(sh, shift), f"{name}: the BatchNorm operands do not give scale / shift back"
+    scale_na, shift_na = ep_affine_exact(None, None, rm, rv, 0.0, f"{name}: BatchNorm operands, no affine")
+    assert torch.equal(scale_na, 1.0 / rv.sqrt()) and torch.equal(shift_na, -rm / rv.sqrt())
+    aff_na = (y.reshape(-1, Co) * scale_na + shift_na).reshape(y.shape)
+    for t, nm in ((aff_na, "no-affine BatchNorm"), (aff_na + c["res"], "no-affine BatchNorm + residual")):
+        need_repr(t, dt, f"{name}: {nm}")
+        need_repr(t, F32, f"{name}: {nm} (fp32)")
+    c.update(gamma=gamma, beta=beta, rm=rm, rv=rv, scale_na=scale_na, shift_na=shift_na, aff_na=aff_na)
+
+
+def half_affine_refs(c):
+    """gamma given with beta NULL, and the reverse, on the operands of bn_operands: (aff_g, aff_b), each representable with and
+    without the residual."""
+    Co, y = c["Co"], c["y"]
+    out = []
+    for gam, bet, nm in ((c["gamma"], None, "gamma alone"), (None, c["beta"], "beta alone")):
+        sc, sh = ep_affine_exact(gam, bet, c["rm"], c["rv"], 0.0, f"{c['name']}: {nm}")
+        a = (y.reshape(-1, Co) * sc + sh).reshape(y.shape)
+        for t in (a, a + c["res"]):
+            need_repr(t, c["dt"], f"{c['name']}: {nm}")
+            need_repr(t, F32, f"{c['name']}: {nm} (fp32)")
+        out.append(a)
+    return out
 
 
 def seg_case(dt, M, Ci, Ci1, Co, views, seed):
@@ -467,6 +519,30 @@ def test_case_table_preconditions():
     # zeros are common enough to exercise the strict ReLU bit
     c = fwd_case(BF16, FWD_CASES[10], "repr", 101)
     assert int((c["aff"] + c["res"] == 0).sum()) > 100
+    # the BatchNorm operand sets of sm3_conv_bn_eval: built (and checked, bn_operands) for every case of the table in every
+    # dtype, through the plan the GPU test walks; every variance value and both signs of the mean occur, and the no-affine
+    # form is another function than the affine one
+    n_bn, seen_rv = 0, set()
+    for dt in DTYPES:
+        planned = {case[0]: (case, seed) for case, regime, seed, views, _, parts in fwd_plan(dt)
+                   if regime == "repr" and views == 1 and parts == "all"}
+        assert list(planned) == [case[0] for case in FWD_CASES]
+        for case, seed in planned.values():
+            c = fwd_case(dt, case, "repr", seed)
+            assert all(c[k].shape == (c["Co"],) for k in ("gamma", "beta", "rm", "rv")), case[0]
+            assert bool((c["rv"] > 0).all()) and not torch.equal(c["aff_na"], c["aff"]), case[0]
+            assert bool((c["rm"] != 0).any()), case[0]
+            seen_rv |= set(c["rv"].tolist())
+            n_bn += 1
+        half_affine_refs(fwd_case(dt, HALF_AFFINE_CASE, "repr", 100 + DTYPES.index(dt)))
+    assert n_bn == 3 * len(FWD_CASES) and seen_rv == set(RV_VALUES)
+    # a neighbouring channel's statistics give another result in every case: a launch that derived its scale / shift from
+    # channel c ^ 1 cannot pass
+    for case in FWD_CASES:
+        c = fwd_case(F16, case, "repr", 102)
+        sw = torch.arange(c["Co"]) ^ 1
+        wrong = c["y"].reshape(-1, c["Co"]) * c["scale_na"][sw] + c["shift_na"][sw]
+        assert not torch.equal(wrong.reshape(c["y"].shape).clamp_min(0), c["aff_na"].clamp_min(0)), case[0]
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -518,12 +594,15 @@ def run_plain(c, envs, with_partials):
 
 
 def run_fwd_epilogues(c, envs, views=1):
-    """Addend with partials; conv_bn_act_fused (views); conv_bn_act_eval (with / without residual, relu)."""
+    """Addend with partials; conv_bn_act_fused (views); conv_bn_act_eval (with / without residual, relu) and, next to each
+    of its launches, conv_bn_eval on BatchNorm tensors that derive the same scale / shift (same bits wanted) and with
+    gamma = beta = NULL."""
     o, dt, Co = ops(), c["dt"], c["Co"]
     d = desc_of(c)
     x, w = _g(c["x"], dt), _g(c["w"], dt)
     res = _g(c["res"], dt)
     sc, sh = _g(c["scale"], F32), _g(c["shift"], F32)
+    bn = [_g(c[k], F32) for k in ("gamma", "beta", "rm", "rv")] if views == 1 else None
     y_rows = c["y"].reshape(-1, Co)
     prow = o.conv_partial_rows(d)
     n = c["y"].numel()
@@ -551,12 +630,26 @@ def run_fwd_epilogues(c, envs, views=1):
                 assert torch.equal(mk.t.cpu(), mask_bytes(pre > 0, EPC[dt])), tag + f" fused mask res={residual}"
                 assert y.guards() and mk.guards(), tag + ": fused launch wrote outside its outputs"
                 if views == 1:
+                    pre_na = c["aff_na"] + (c["res"] if residual else 0)
                     for relu in (True, False):
                         y = Guarded(n, dt)
                         launch(o.conv_bn_act_eval, d, x, w, sc, sh, res if residual else None, relu, y.t)
                         torch.cuda.synchronize()
                         same(y.t, pre.clamp_min(0) if relu else pre, tag + f" eval res={residual} relu={relu}")
                         assert y.guards(), tag + ": eval launch wrote outside y"
+                        # the same launch with scale / shift derived in the epilogue from the BatchNorm's tensors, and its
+                        # gamma = beta = NULL form
+                        yb = Guarded(n, dt)
+                        launch(o.conv_bn_eval, d, x, w, bn[0], bn[1], bn[2], bn[3], 0.0, res if residual else None, relu, yb.t)
+                        torch.cuda.synchronize()
+                        same(yb.t, pre.clamp_min(0) if relu else pre, tag + f" bn_eval res={residual} relu={relu}")
+                        assert yb.guards(), tag + ": bn_eval launch wrote outside y"
+                        assert torch.equal(yb.t, y.t), tag + f" bn_eval != conv_bn_act_eval res={residual} relu={relu}"
+                        yb = Guarded(n, dt)
+                        launch(o.conv_bn_eval, d, x, w, None, None, bn[2], bn[3], 0.0, res if residual else None, relu, yb.t)
+                        torch.cuda.synchronize()
+                        same(yb.t, pre_na.clamp_min(0) if relu else pre_na, tag + f" bn_eval no affine res={residual} relu={relu}")
+                        assert yb.guards(), tag + ": bn_eval launch (no affine) wrote outside y"
 
 
 def run_fwd_plan(dt, plan):
@@ -583,6 +676,70 @@ def test_forward_grids_and_deep_threshold(dt):
     LAUNCHES[0] = 0
     run_fwd_plan(dt, grid_plan)
     print(f"grids {dt}: {LAUNCHES[0]} launches checked")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", DTYPES, ids=IDS)
+def test_conv_bn_eval_same_bits_as_scale_shift_then_conv_bn_act_eval(dt):
+    """The identity include/sm3_hip.h states for sm3_conv_bn_eval, on real values (random x, w, BatchNorm tensors, eps = 1e-5)
+    over the whole edge table under the default switches: the same bits as sm3_bn_eval_scale_shift followed by
+    sm3_conv_bn_act_eval, with and without a residual, gamma / beta, and the ReLU.  (Two entry points of the code under test:
+    the identity is the documented contract, and sm3_bn_eval_scale_shift is held to fp64 in test_exact_bn_gpu.py.)"""
+    o = ops()
+    LAUNCHES[0] = 0
+    bits = torch.int32 if dt == F32 else torch.int16
+    for i, case in enumerate(FWD_CASES):
+        name, N, H, W, ci16, Co, k, s, p = case
+        Ci = ci_for(dt, ci16)
+        g = torch.Generator().manual_seed(1000 + i)
+        d = o.fwd_desc(o.dtype_code(dt), N, H, W, Ci, Co, k, s, p)
+        n = N * d.Ho * d.Wo * Co
+        x = _g(torch.randn(N, H, W, Ci, generator=g), dt)
+        w = _g(torch.randn(Co, k, k, Ci, generator=g) / (k * k * Ci) ** 0.5, dt)
+        res = _g(torch.randn(n, generator=g), dt)
+        gamma, beta = _g(torch.rand(Co, generator=g) + 0.5, F32), _g(torch.randn(Co, generator=g), F32)
+        rm, rv = _g(torch.randn(Co, generator=g), F32), _g(torch.rand(Co, generator=g) + 0.1, F32)
+        for affine in (True, False):
+            ga, be = (gamma, beta) if affine else (None, None)
+            sc, sh = Guarded(Co, F32), Guarded(Co, F32)
+            launch(o.bn_eval_scale_shift, ga, be, rm, rv, 1e-5, Co, sc.t, sh.t)
+            for residual in (True, False):
+                for relu in (True, False):
+                    tag = f"{name} {dt} affine={affine} res={residual} relu={relu}"
+                    y0, y1 = Guarded(n, dt), Guarded(n, dt)
+                    launch(o.conv_bn_act_eval, d, x, w, sc.t, sh.t, res if residual else None, relu, y0.t)
+                    launch(o.conv_bn_eval, d, x, w, ga, be, rm, rv, 1e-5, res if residual else None, relu, y1.t)
+                    torch.cuda.synchronize()
+                    assert bool(torch.isfinite(y0.t).all()), tag + ": the two-launch form is not finite"
+                    assert torch.equal(y1.t.view(bits), y0.t.view(bits)), tag + ": bits differ"
+                    assert y0.guards() and y1.guards(), tag + ": wrote outside y"
+            assert sc.guards() and sh.guards(), f"{name}: bn_eval_scale_shift wrote outside scale / shift"
+    print(f"bn_eval identity {dt}: {LAUNCHES[0]} launches checked")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", DTYPES, ids=IDS)
+def test_conv_bn_eval_with_gamma_or_beta_alone(dt):
+    """gamma given with beta NULL takes beta = 0, beta given with gamma NULL takes gamma = 1 (include/sm3_hip.h): fp64 on one
+    small case, every switch setting, with and without the residual and the ReLU."""
+    o = ops()
+    c = fwd_case(dt, HALF_AFFINE_CASE, "repr", 100 + DTYPES.index(dt))
+    aff_g, aff_b = half_affine_refs(c)
+    d = desc_of(c)
+    x, w, res = _g(c["x"], dt), _g(c["w"], dt), _g(c["res"], dt)
+    gamma, beta, rm, rv = (_g(c[k], F32) for k in ("gamma", "beta", "rm", "rv"))
+    for e in CONV_ENVS:
+        with env(e):
+            for ga, be, ref, nm in ((gamma, None, aff_g, "gamma alone"), (None, beta, aff_b, "beta alone")):
+                for residual in (True, False):
+                    pre = ref + (c["res"] if residual else 0)
+                    for relu in (True, False):
+                        y = Guarded(pre.numel(), dt)
+                        o.conv_bn_eval(d, x, w, ga, be, rm, rv, 0.0, res if residual else None, relu, y.t)
+                        torch.cuda.synchronize()
+                        tag = f"{c['name']} {dt} {nm} res={residual} relu={relu} {e}"
+                        same(y.t, pre.clamp_min(0) if relu else pre, tag)
+                        assert y.guards(), tag + ": wrote outside y"
 
 
 @pytest.mark.gpu
@@ -921,6 +1078,32 @@ def test_rejected_shapes_leave_outputs_untouched():
                                           o._stream())
     torch.cuda.synchronize()
     assert rc != 0 and y.untouched()
+    # sm3_conv_bn_eval needs both running statistics and an eps that is a number >= 0: through the wrapper, and through the
+    # C ABI when the wrapper is bypassed
+    byref, lib = __import__("ctypes").byref, _lib.load()
+    for dt in DTYPES:
+        code = o.dtype_code(dt)
+        d = o.fwd_desc(code, 1, 4, 4, KCH[dt], 64, 1, 1, 0)
+        x = torch.ones(16 * KCH[dt], dtype=dt, device=_dev())
+        w = torch.ones(64 * KCH[dt], dtype=dt, device=_dev())
+        v = torch.ones(64, device=_dev())
+        for rm, rv, eps, what in ((None, v, 0.0, "NULL running_mean"), (v, None, 0.0, "NULL running_var"),
+                                  (v, v, -1e-5, "eps < 0"), (v, v, float("nan"), "eps = NaN")):
+            y = Guarded(16 * 64, dt)
+            with pytest.raises(errors):
+                o.conv_bn_eval(d, x, w, v, v, rm, rv, eps, None, True, y.t)
+            torch.cuda.synchronize()
+            assert y.untouched(), f"{dt} {what}: the wrapper's refusal wrote y"
+            rc = lib.sm3_conv_bn_eval(byref(d), o._ptr(x), o._ptr(w), o._ptr(v), o._ptr(v), o._ptr(rm), o._ptr(rv), eps,
+                                      o._ptr(None), 1, o._ptr(y.t), o._stream())
+            torch.cuda.synchronize()
+            assert rc != 0 and y.untouched(), f"{dt} {what}: rc {rc}"
+        # (the same call with every operand in place is accepted: the refusals above are those of the operands named)
+        y = Guarded(16 * 64, dt)
+        o.conv_bn_eval(d, x, w, v, v, v, v, 0.0, None, True, y.t)
+        torch.cuda.synchronize()
+        same(y.t, torch.full((16 * 64,), float(KCH[dt])), f"{dt}: accepted control launch")
+        assert y.guards()
 
 
 @pytest.mark.gpu

@@ -13,7 +13,8 @@ the total // V and per_view offsets of the partial rows) and any swapped (h, w) 
     paired (2 x 128 at A: pair_ok holds, so view tiles and the fused stride-2 join run on odd maps), and ResNeXt-50's first
     teacher-forced check at 224 x 224.  Per unit the output, the running statistics, every parameter gradient and the input
     gradient, each with limit = max(BOUNDS[mode], 3 x the mode restatement's own value on that unit);
-  * eval mode, whole encoder: features and x.grad (which must have the image's shape) against an fp64 restatement;
+  * eval mode, whole encoder: features and x.grad (which must have the image's shape) against an fp64 restatement; and the
+    features of the same encoders under no_grad, where every dense unit is one sm3_conv_bn_eval launch (counted);
   * the whole SM3 model in f32 at A: logits and loss of the compat forward and of one fused trainer step against the oracle.
 """
 import math
@@ -112,6 +113,70 @@ def test_eval_mode_features_and_input_gradient_against_fp64(arch, geo, mode):
     H.measure_line({"case": f"eval-{arch}-{mode}-{geo}", "engine": {"feat_rel": ef, "xgrad_rel": eg},
                     "limit": {"feat_rel": lim_f, "xgrad_rel": lim_g}})
     assert ef <= lim_f and eg <= lim_g, (ef, lim_f, eg, lim_g)
+
+
+# what every tool runs: the same encoders under no_grad, where conv_bn takes the one-launch form (sm3_conv_bn_eval); C for
+# resnet18 alone, in f32: a final map of 1 x 1, M = N rows, the smallest launch an encoder hands to that kernel
+NOGRAD_CASES = [(arch, geo, mode) for arch in ("resnet50", "resnet18", "resnext50_32x4d") for geo in ("A", "B")
+                for mode in ("f32", "bf16", "f16")] + [("resnet18", "C", "f32")]
+
+
+def _count_calls(monkeypatch, names):
+    """{name: calls of sm3hip.ops.<name> from now on}, through wrappers that pass every call on."""
+    from sm3hip import ops
+    counts = {n: 0 for n in names}
+
+    def wrap(n, real):
+        def counted(*a, **k):
+            counts[n] += 1
+            return real(*a, **k)
+        return counted
+    for n in names:
+        monkeypatch.setattr(ops, n, wrap(n, getattr(ops, n)))
+    return counts
+
+
+@pytest.mark.parametrize("arch,geo,mode", NOGRAD_CASES, ids=["-".join(c) for c in NOGRAD_CASES])
+def test_eval_mode_features_without_autograd_against_fp64(arch, geo, mode, monkeypatch):
+    """The frozen encoder under torch.no_grad(): every non-grouped unit is ONE launch (convolution, running-statistics
+    BatchNorm, residual, ReLU; scale / shift derived in the epilogue), where the test above -- an image that requires a
+    gradient -- runs the two-pass form.  Features against the fp64 restatement; f32: 2e-3, the bound of the test above; 16-bit:
+    3 x the 16-bit restatement's own error on the same input (it rounds the pre-BatchNorm tensor, which this form never
+    stores).  In f32 the distance to the two-pass form's features is recorded as well."""
+    h, w = H.GEOMETRIES[geo]
+    dt = H.DTYPE[mode]
+    m = _frozen_encoder(arch)
+    x = H.images(3, h, w, "eval").to(DEV)
+    with torch.no_grad():
+        f_ref = H.restated_features(m, x.double())
+        lim = 2e-3 if mode == "f32" else H.MARGIN * H.rel(H.restated_features(m, x.double(), dt), f_ref)
+    m.sm3_dtype = dt
+    counts = _count_calls(monkeypatch, ("conv_bn_eval", "bn_eval_scale_shift"))
+    with torch.no_grad():
+        f = m(x)
+    torch.cuda.synchronize()
+    ran = dict(counts)
+    # the one-launch branch ran for every dense unit but the stem (whose BatchNorm is applied inside the pooling pass); the
+    # stem and a ResNeXt's grouped 3x3 units computed their scale / shift first: counted on the plan's own unit list
+    units = list(m.__dict__["_sm3_engine"].branches["main"][0].conv_units())
+    two_pass = [u for u in units if u.stem or u.groups > 1]
+    assert len(two_pass) == 1 + (sum(u.k == 3 for u in units) if arch.startswith("resnext") else 0), len(two_pass)
+    assert ran == {"conv_bn_eval": len(units) - len(two_pass), "bn_eval_scale_shift": len(two_pass)}, (ran, len(units))
+    assert ran["conv_bn_eval"] > 0 and not f.requires_grad and f.dtype == torch.float32 and f.shape == f_ref.shape
+    ef = H.rel(f.double(), f_ref)
+    rec = {"case": f"eval-nograd-{arch}-{mode}-{geo}", "engine": {"feat_rel": ef}, "limit": {"feat_rel": lim},
+           "launches": ran}
+    line = f"\n{arch} {geo} {mode} eval, no_grad: features {ef:.3e} (limit {lim:.3e}), launches {ran}"
+    if mode == "f32":  # how far the one-launch and the two-pass form are apart (recorded, not bounded beyond the limit above)
+        f2 = m(x.clone().requires_grad_())
+        torch.cuda.synchronize()
+        assert counts["conv_bn_eval"] == ran["conv_bn_eval"], "the autograd forward took the one-launch form"
+        e2, ef2 = H.rel(f.double(), f2.detach().double()), H.rel(f2.detach().double(), f_ref)
+        rec["engine"].update(two_pass_rel=e2, two_pass_feat_rel=ef2)
+        line += f"; against the two-pass form {e2:.3e} (two-pass against fp64 {ef2:.3e})"
+    print(line)
+    H.measure_line(rec)
+    assert ef <= lim, (ef, lim)
 
 
 # ---- the whole model -----------------------------------------------------------------------------------------------------
