@@ -1147,6 +1147,36 @@ int sm3_tta_dihedral(const float* x, int rows, int H, int W, const int* elements
 int sm3_tta_reduce(const float* logits, int B, int V, int64_t* q, int64_t* sum_q, int64_t* min_q, int64_t* max_q,
                    int32_t* view_class, int32_t* agg_class, int32_t* disagree, float* preds, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Image corruptions of the robustness report (csrc/corrupt.hip, sm3hip/corrupt.py, whose module text is the specification;
+ * ABI 9, additive).  x, out: [B][3][H][W] f32 in [0, 1] on the device, the resampled image before Normalize; x != out.  Every
+ * output element is a function of (image, operation, parameter, seed, case id, modality) alone.  Everything is checked before
+ * anything is launched (SM3_EINVAL: a null pointer, B / H / W < 1, 3 H W > 2^31 - 1, and what each entry names).
+ * sm3_corrupt_pointwise: op 0 gaussian_noise, out = clamp01(fadd(x, fmul((float)param, z))); op 1 impulse_noise, param = T as an
+ *   integer in 0 .. 2^31: 0 where the element's word w < T, 1 where w >= 2^32 - T, else x; op 10 colour_cast, out =
+ *   clamp01(fmul(x, g[ch])), g = (1 + c, 1, 1 - c) in f32, c = (float)param, reversed where the case word is odd.  ids: DEVICE
+ *   int32 [B], the case's position in its split.  Philox4x32-10, key = seed (low word first); element e of a case's [3][H][W]
+ *   image takes word e % 4 of counter (e / 4, id, modality << 16 | op << 8 | severity, 7), normals by sm3_attr_noise's rule;
+ *   the case word is word 0 of counter (0xFFFFFFFF, id, op << 8 | severity, 7).  SM3_EINVAL: another op, severity outside
+ *   1 .. 5, modality outside 0 .. 1, param outside [0, 1] (op 1: not an integer in 0 .. 2^31).
+ * sm3_corrupt_taps: out[y][x] = (the sum over t < counts[k] of x[clamp(y + dy_t)][clamp(x + dx_t)], added in table order, every
+ *   add rounded to f32) / counts[k], k = table_index[b].  tables: HOST int16 [n_tables][max_taps][2] (dy, dx), counts: HOST int32
+ *   [n_tables], table_index: HOST int32 [B].  SM3_EINVAL: n_tables outside 1 .. 8, a count outside 1 .. max_taps, more than 336
+ *   taps in all, an offset beyond +-10, a table index outside 0 .. n_tables - 1.
+ * sm3_corrupt_pixelate: every pixel -> the mean of its f x f block (anchored at (0, 0); the in-image pixels added row-major,
+ *   every add rounded, one division by their number).  SM3_EINVAL: f outside 1 .. 32, B > 65535.
+ * sm3_corrupt_jpeg: a 4:4:4 baseline JPEG round trip in integers on 8 x 8 blocks of the edge-replicated image, with the HOST
+ *   quantisation tables qt_luma, qt_chroma (int32 [64], [vertical][horizontal] frequency, as scaled for `quality`).
+ *   SM3_EINVAL: quality outside 1 .. 100, a table entry outside 1 .. 255.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_corrupt_pointwise(const float* x, int B, int H, int W, const int32_t* ids, int op, int severity, double param,
+                          uint64_t seed, int modality, float* out, void* stream);
+int sm3_corrupt_taps(const float* x, int B, int H, int W, const int16_t* tables, const int32_t* counts, int n_tables, int max_taps,
+                     const int32_t* table_index, float* out, void* stream);
+int sm3_corrupt_pixelate(const float* x, int B, int H, int W, int f, float* out, void* stream);
+int sm3_corrupt_jpeg(const float* x, int B, int H, int W, int quality, const int32_t* qt_luma, const int32_t* qt_chroma, float* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,14 +47,6 @@ __global__ void __launch_bounds__(kThreads) attr_path_kernel(const float4* __res
     out[i] = make_float4(blend(v.x, b.x, alpha), blend(v.y, b.y, alpha), blend(v.z, b.z, alpha), blend(v.w, b.w, alpha));
 }
 
-__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& z0, float& z1) {
-    const double ua = ((double)wa + 0.5) * 0x1p-32, ub = ((double)wb + 0.5) * 0x1p-32;
-    const double r = sqrt(-2.0 * log(ua));
-    double s, co;
-    sincospi(2.0 * ub, &s, &co);
-    z0 = (float)(r * co), z1 = (float)(r * s);
-}
-
 __global__ void __launch_bounds__(kThreads) attr_noise_kernel(const float4* __restrict__ x, const float* __restrict__ sigma,
                                                               float4* __restrict__ out, int64_t NE4, int64_t E4, int k0, int c,
                                                               int stride, uint32_t key0, uint32_t key1) {

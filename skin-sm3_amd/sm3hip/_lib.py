@@ -215,6 +215,10 @@ SIGNATURES = {
     "sm3_logreg_fit_lockstep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P],
     "sm3_tta_dihedral": [_P, _I, _I, _I, _P, _I, _P, _P],
     "sm3_tta_reduce": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "sm3_corrupt_pointwise": [_P, _I, _I, _I, _P, _I, _I, _D, C.c_uint64, _I, _P, _P],
+    "sm3_corrupt_taps": [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P],
+    "sm3_corrupt_pixelate": [_P, _I, _I, _I, _I, _P, _P],
+    "sm3_corrupt_jpeg": [_P, _I, _I, _I, _I, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -56,6 +56,18 @@ def resized_crop_params(B, Hs, Ws, scale, ratio, gen):
     return box
 
 
+def colour_ops(img, ops_host, opsd, facd):
+    """ColorJitter's positions that any sample uses (ops_host [4, B] on the host; opsd, facd: its and the factors' device copies),
+    in place on img [B, 3, H, W] in [0, 1]: torchvision's brightness / contrast / saturation / hue arithmetic."""
+    lib, st = _lib.load(), ops._stream()
+    B, _, H, W = img.shape
+    gm = torch.empty(B, dtype=torch.float32, device=img.device)
+    for pos in range(4):
+        if bool((ops_host[pos] != 0).any()):
+            _lib.check(lib.sm3_aug_color_op(ops._ptr(img), B, H, W, ops._ptr(opsd[pos]), ops._ptr(facd[pos]), ops._ptr(gm), st),
+                       "sm3_aug_color_op")
+
+
 class SimCLRAugment:
     def __init__(self, size, mean, std, scale=(0.5, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), jitter=(0.8, 0.8, 0.8, 0.2),
                  p_jitter=0.8, p_gray=0.2, p_flip=0.5, p_blur=0.5, sigma=(0.1, 2.0)):
@@ -135,11 +147,7 @@ class SimCLRAugment:
         """ColorJitter's positions that any sample uses, then grayscale / blur / Normalize, on img [B, 3, H, W] in [0, 1]."""
         lib, st = _lib.load(), ops._stream()
         B, _, H, W = img.shape
-        gm = torch.empty(B, dtype=torch.float32, device=img.device)
-        for pos in range(4):
-            if bool((params.ops[pos] != 0).any()):
-                _lib.check(lib.sm3_aug_color_op(ops._ptr(img), B, H, W, ops._ptr(opsd[pos]), ops._ptr(facd[pos]), ops._ptr(gm),
-                                                st), "sm3_aug_color_op")
+        colour_ops(img, params.ops, opsd, facd)
         out = torch.empty_like(img)
         m3, s3 = (C.c_float * 3)(*self.mean), (C.c_float * 3)(*self.std)
         _lib.check(lib.sm3_aug_finish(ops._ptr(img), B, H, W, ops._ptr(gray), ops._ptr(sigma), m3, s3, ops._ptr(out), st),
@@ -151,6 +159,12 @@ class SimCLRAugment:
         reads image index[b] (host int32 [B]); offset / img_h / img_w: host int64 / int32 / int32 per image.  The crop
         boxes are checked against each sample's own image by the library before anything is launched.
         -> [B, 3, H, W] fp32 normalised."""
+        img, on_device = self.resample_ragged(arena, offset, img_h, img_w, index, params)
+        return self._colour_finish(img, params, *on_device)
+
+    def resample_ragged(self, arena, offset, img_h, img_w, index, params):
+        """The first half of apply_ragged: the resample alone.  -> (img [B, 3, H, W] fp32 in [0, 1], the device copies (ops,
+        factors, gray, sigma) of the parameters that _colour_finish takes).  sm3hip.corrupt works on img between the two."""
         if not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1:
             raise ValueError("the arena must be a 1-D uint8 CUDA tensor")
         index = torch.as_tensor(index, dtype=torch.int32).contiguous()
@@ -173,7 +187,7 @@ class SimCLRAugment:
                                                    img_w.data_ptr(), offset.numel(), index.data_ptr(), box.data_ptr(),
                                                    flip.data_ptr(), B, ops._ptr(img), H, W, st),
                    "sm3_aug_resized_crop_ragged")
-        return self._colour_finish(img, params, opsd, facd, gray, sigma)
+        return img, (opsd, facd, gray, sigma)
 
     def __call__(self, src, gen=None, n_views=2):
         """NViewsTransform(self, n_views): independent parameters per view (functional.py:43-49)."""

@@ -5,6 +5,7 @@ checks on the host that shapes/dtypes/devices match what the kernel's grid assum
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2491,3 +2492,60 @@ def tta_reduce(logits, q, sum_q, min_q, max_q, view_class, agg_class, disagree, 
     with _prof("tta_reduce", 0.0, 4.0 * logits.numel() + 8.0 * q.numel()):
         check(_lib.load().sm3_tta_reduce(_ptr(logits), B, V, _ptr(q), _ptr(sum_q), _ptr(min_q), _ptr(max_q), _ptr(view_class),
                                          _ptr(agg_class), _ptr(disagree), _ptr(preds), _stream()), "sm3_tta_reduce")
+
+
+# ------------------------------------------------------------------------------------------
+# image corruptions of the robustness report (sm3hip/corrupt.py, csrc/corrupt.hip)
+# ------------------------------------------------------------------------------------------
+def _corrupt_images(x, out, who):
+    if x.dim() != 4 or x.shape[1] != 3 or min(x.shape) < 1:
+        raise ValueError(f"{who}: x must be [B >= 1, 3, H >= 1, W >= 1]")
+    _chk(x, torch.float32, "x"); _chk(out, torch.float32, "out")
+    if out.shape != x.shape or out.data_ptr() == x.data_ptr():
+        raise ValueError(f"{who}: out must be another tensor of x's shape")
+    return x.shape[0], x.shape[2], x.shape[3]
+
+
+def corrupt_pointwise(x, ids, op, severity, param, seed, modality, out):
+    """gaussian_noise (op 0, param sigma), impulse_noise (op 1, param T = int(p * 2^31)) or colour_cast (op 10, param c) of
+    x [B, 3, H, W] fp32 in [0, 1] (sm3_corrupt_pointwise); ids: int32 [B] on the GPU, the cases' positions in their split."""
+    B, H, W = _corrupt_images(x, out, "corrupt_pointwise")
+    _chk(ids, torch.int32, "ids")
+    if ids.numel() != B:
+        raise ValueError("corrupt_pointwise: ids must be int32 [B]")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("corrupt_pointwise: seed must fit 64 bits")
+    with _prof("corrupt_pointwise", 2.0 * x.numel(), 8.0 * x.numel()):
+        check(_lib.load().sm3_corrupt_pointwise(_ptr(x), B, H, W, _ptr(ids), op, severity, float(param), seed, modality, _ptr(out),
+                                                _stream()), "sm3_corrupt_pointwise")
+
+
+def corrupt_taps(x, tables, counts, table_index, out):
+    """The mean of x over a tap table per case (sm3_corrupt_taps): tables int16 [n_tables, max_taps, 2] (dy, dx), counts int32
+    [n_tables], table_index int32 [B], numpy arrays on the host."""
+    B, H, W = _corrupt_images(x, out, "corrupt_taps")
+    tables, counts = np.ascontiguousarray(tables, dtype=np.int16), np.ascontiguousarray(counts, dtype=np.int32)
+    table_index = np.ascontiguousarray(table_index, dtype=np.int32)
+    if tables.ndim != 3 or tables.shape[2] != 2 or counts.shape != tables.shape[:1] or table_index.shape != (B,):
+        raise ValueError("corrupt_taps: tables [n_tables, max_taps, 2], counts [n_tables], table_index [B]")
+    with _prof("corrupt_taps", float(counts.max()) * x.numel(), 8.0 * x.numel()):
+        check(_lib.load().sm3_corrupt_taps(_ptr(x), B, H, W, tables.ctypes.data, counts.ctypes.data, tables.shape[0],
+                                           tables.shape[1], table_index.ctypes.data, _ptr(out), _stream()), "sm3_corrupt_taps")
+
+
+def corrupt_pixelate(x, f, out):
+    """Every pixel of x [B, 3, H, W] -> the mean of its f x f block (sm3_corrupt_pixelate)."""
+    B, H, W = _corrupt_images(x, out, "corrupt_pixelate")
+    with _prof("corrupt_pixelate", 1.0 * x.numel(), 8.0 * x.numel()):
+        check(_lib.load().sm3_corrupt_pixelate(_ptr(x), B, H, W, int(f), _ptr(out), _stream()), "sm3_corrupt_pixelate")
+
+
+def corrupt_jpeg(x, quality, qt_luma, qt_chroma, out):
+    """The integer JPEG round trip of x [B, 3, H, W] (sm3_corrupt_jpeg); qt_luma, qt_chroma: int32 [64] numpy arrays."""
+    B, H, W = _corrupt_images(x, out, "corrupt_jpeg")
+    ql, qc = np.ascontiguousarray(qt_luma, dtype=np.int32).reshape(-1), np.ascontiguousarray(qt_chroma, dtype=np.int32).reshape(-1)
+    if ql.size != 64 or qc.size != 64:
+        raise ValueError("corrupt_jpeg: two quantisation tables of 64 entries")
+    with _prof("corrupt_jpeg", 0.0, 8.0 * x.numel()):
+        check(_lib.load().sm3_corrupt_jpeg(_ptr(x), B, H, W, int(quality), ql.ctypes.data, qc.ctypes.data, _ptr(out), _stream()),
+              "sm3_corrupt_jpeg")

@@ -83,7 +83,7 @@ def philox_words(n, seed, r, stream):
     """n 32-bit words (uint64 array): word d is word d % 4 of the call with key = the 64-bit seed (low word first) and counter
     (d / 4, r, 0, stream).  Streams in use: 0 SmoothGrad, 1 RISE, 2 the bootstrap draws above, 3 and 4 sm3hip/logreg.py,
     5 the swap bits of sm3hip/significance.py, 6 the bootstrap draws of the calibration split of sm3hip/conformal.py (the rule
-    above on N_cal cases)."""
+    above on N_cal cases), 7 the case and element words of sm3hip/corrupt.py (its own counters: see that module's text)."""
     q = np.arange((n + 3) // 4, dtype=np.uint64)
     w = philox4x32_10(q, np.uint64(r), np.uint64(0), np.uint64(stream), seed & 0xFFFFFFFF, seed >> 32)
     return np.stack(w, axis=1).reshape(-1)[:n]

@@ -27,6 +27,10 @@ predicted probabilities over the group's views of every case (--tta-crops 5: of 
 each, real data only), prints its AUC_AVG and how much the predictions move across the views, and under real data saves
 val_predictions_tta.pt in val_predictions.pt's format: `eval_report.py val_predictions_tta.pt --against val_predictions.pt
 --significance` is the paired comparison.
+--corrupt NAME [NAME ...] | all (sm3hip.corrupt; real data only) adds, after the last epoch's validation pass, one pass over the same
+cases per image corruption and --corrupt-severity (default 1 .. 5; --corrupt-modality both|derm|clinic, --corrupt-seed): it saves
+val_predictions_corrupt/<name>_<s>.pt in val_predictions.pt's format and val_robustness.json / .csv (the paired AUC differences with
+the bootstrap's intervals, the flip rate and the mean |delta p| of every corruption), and prints one line per corruption.
 `--data-name synthetic`: random images and labels, --steps-per-epoch / --val-steps steps.
 """
 import argparse
@@ -46,14 +50,14 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
 import eval_cli  # noqa: E402
-from sm3hip import report, tta  # noqa: E402
+from sm3hip import corrupt, report, tta  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, auc_avg  # noqa: E402
 
 
 def get_parser(calibration_flags=True, tta_flags=True):
     """src/utils/misc.py:get_parser + tools/backbone_eval.py:434-440 of the reference, then this build's own flags
     (calibration_flags=False: without --calibration and its two settings, for backbone_knn, whose votes are not logits;
-    tta_flags=False: without --tta and its two settings, for the tools on frozen features)."""
+    tta_flags=False: without --tta and its two settings and without the --corrupt flags, for the tools on frozen features)."""
     from src.utils.misc import get_parser as base_parser
     p = base_parser("SM3 linear probe / fine-tune (MI355X)")
     p.add_argument("--arch-weights", type=str, default=None)
@@ -66,6 +70,7 @@ def get_parser(calibration_flags=True, tta_flags=True):
     eval_cli.add_report_flags(p, calibration=calibration_flags)
     if tta_flags:
         tta.add_flags(p)
+        corrupt.add_flags(p)
     p.set_defaults(arch="resnet50", epochs=50, batch_size=128)
     return p
 
@@ -113,7 +118,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     eval_cli.check_report_flags(args)
     from src.utils.misc import amp_dtype
-    dev, gen, real = eval_cli.refuse_and_seed(args, parser, "backbone_eval", check=lambda real: tta.check_flags(args, real))
+    dev, gen, real = eval_cli.refuse_and_seed(args, parser, "backbone_eval", check=lambda real: (tta.check_flags(args, real),
+                                                                                                  corrupt.check_flags(args, real)))
     evaluator = eval_cli.baseline_subject(args, dev, freeze=args.finetune == "fc", eval_mode=False)
     args.scaler = torch.amp.GradScaler("cuda", enabled=amp_dtype(args) == torch.float16)  # backbone_eval.py:271
     params = [p for p in evaluator.parameters() if p.requires_grad]
@@ -147,6 +153,8 @@ def main(argv=None):
             if args.tta != "none":  # one more pass over the same validation cases, every view of each
                 eval_cli.tta_pass(f"epoch {epoch}: ", evaluator, args, epoch, dev, gen, store if real else None,
                                   vsplit if real else None, args.img_sz)
+            if args.corrupt is not None:  # one more pass per corruption and severity (real data: check_flags)
+                eval_cli.corrupt_pass(f"epoch {epoch}: ", evaluator, args, epoch, store, vsplit, args.img_sz)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG (backbone_eval.py:386,405-411)
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},

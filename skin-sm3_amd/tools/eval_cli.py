@@ -159,6 +159,30 @@ def tta_pass(prefix, evaluator, args, epoch, dev, gen, store, split, size):
     return rec
 
 
+# ---- robustness under image corruptions ---------------------------------------------------------------------------------------
+def corrupt_pass(prefix, evaluator, args, epoch, store, split, size):
+    """One pass of sm3hip.corrupt over the validation split of the image store per (--corrupt name, --corrupt-severity) with the
+    eval-mode model: saves val_predictions_corrupt/<name>_<s>.pt (val_predictions.pt's keys plus "corrupt") and
+    val_robustness.json / .csv under --log-path, prints prefix + one line per corruption and the summary.  Returns the report."""
+    from sm3hip import corrupt
+    from sm3hip.metrics import auc_avg
+    evaluator.eval()
+    rec = corrupt.predict_split(evaluator, store, split, tuple(size), args.mean, args.std, args.corrupt, args.corrupt_severity,
+                                args.corrupt_modality, args.corrupt_seed, args.batch_size)
+    out_dir = os.path.join(args.log_path, "val_predictions_corrupt")
+    os.makedirs(out_dir, exist_ok=True)
+    for (name, s), preds in rec["preds"].items():
+        _, avg = auc_avg(preds, rec["targets"])
+        torch.save({"epoch": epoch + 1, "preds": [p.cpu() for p in preds], "targets": rec["targets"].cpu(), "AUC_AVG": float(avg),
+                    "corrupt": {"name": name, "severity": s, "modality": rec["modality"], "seed": rec["seed"]}},
+                   os.path.join(out_dir, f"{name}_{s}.pt"))
+    rep = corrupt.robustness_report(rec, bootstrap=args.bootstrap, confidence=args.confidence, seed=args.bootstrap_seed)
+    corrupt.save(rep, args.log_path)
+    for line in corrupt.stats_lines(rep) + [corrupt.stats_line(rep)]:
+        print(prefix + "val-" + line, flush=True)
+    return rep
+
+
 # ---- features ---------------------------------------------------------------------------------------------------------------
 def encode(evaluator, batches, normalize=False):
     """cat(derm_f, clinic_f) as float32 -- normalize=True: as unit rows (sm3hip.knn.normalize) -- and the labels of every

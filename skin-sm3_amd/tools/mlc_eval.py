@@ -10,6 +10,8 @@ val_report.json / val_report.csv (--bootstrap B: with intervals) and, under real
 --tta hflip|flips|d4 adds one more pass over the same cases after the last epoch, averaged over the group's views of every case
 (sm3hip.tta; --tta-crops, --tta-crop-scale): its AUC_AVG, the stability of the predictions across views and, under real data,
 val_predictions_tta.pt.
+--corrupt NAME [NAME ...] | all adds one pass per image corruption and --corrupt-severity over the same cases (sm3hip.corrupt;
+--corrupt-modality, --corrupt-seed; real data only): val_predictions_corrupt/<name>_<s>.pt and val_robustness.json / .csv.
 
     python tools/mlc_eval.py --data-name synthetic -a resnet50 -b 128 -lr 1e-3 --epochs 2 --mlc-proj v4 \
         --mlc-proj-dim 512 --num-heads 1 --sa-dim-ff 128 --sa-dropout 0.1 --finetune projector \
@@ -43,7 +45,7 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
 import eval_cli  # noqa: E402
-from sm3hip import report, tta  # noqa: E402
+from sm3hip import corrupt, report, tta  # noqa: E402
 from sm3hip.metrics import CLASSES_NAME, NUM_CLASSES, auc_avg  # noqa: E402
 from src.models.projector import build_mlc_projectors  # noqa: E402
 from src.models.simclr import SimCLRSkinV32  # noqa: E402
@@ -100,6 +102,7 @@ def get_parser(tta_flags=True):
     eval_cli.add_report_flags(p)
     if tta_flags:
         tta.add_flags(p)
+        corrupt.add_flags(p)
     p.set_defaults(arch="resnet50", batch_size=128, finetune="projector", pretrain_path="", log_path="./logs/mlc_eval")
     return p
 
@@ -183,6 +186,7 @@ def main(argv=None):
     real = require_data(args, "mlc_eval")
     val_sz = (args.test_sz, args.test_sz) if real else tuple(args.img_sz)
     tta.check_flags(args, real, val_sz)
+    corrupt.check_flags(args, real)
     if real:  # unlike the linear-probe tools (eval_cli.refuse_and_seed), no notice under synthetic data: kept as it was
         eval_cli.ignored_notice(args, parser, real)
     torch.manual_seed(args.seed)
@@ -250,6 +254,8 @@ def main(argv=None):
             if args.tta != "none":  # one more pass over the same validation cases, every view of each
                 eval_cli.tta_pass(f"epoch {epoch}: ", inference_twin(evaluator, args, dev), args, epoch, dev, gen,
                                   store if real else None, vsplit if real else None, val_sz)
+            if args.corrupt is not None:  # one more pass per corruption and severity (real data: check_flags)
+                eval_cli.corrupt_pass(f"epoch {epoch}: ", inference_twin(evaluator, args, dev), args, epoch, store, vsplit, val_sz)
         if va["AUC_AVG"] > best:  # best by val/AUC_AVG
             best = va["AUC_AVG"]
             torch.save({"epoch": epoch + 1, "state_dict": evaluator.state_dict(), "optimizer": optimizer.state_dict()},
