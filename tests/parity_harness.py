@@ -17,8 +17,13 @@ test_geometry_parity_gpu.py, test_parity_harness_cpu.py): every unit of an encod
     (cosine: min(BOUNDS cos, 1 - 3 (1 - cos_restated))).  BOUNDS is test_block_parity_gpu.py's table, measured at the
     benchmarked shapes; the second term comes from the reference alone.  No limit is derived from what the engine returned.
 
-Not a conftest; changes no pytest setting.  SM3_GEOMETRY_MEASURE=<file>: check_run appends one JSON line per case with the
-worst engine and restatement value of every metric (profiles/geometry_parity_measure.md is made from such a run)."""
+The second half of the file does the same for the HEAD of a training step -- everything past the layer4 tap: pool, projectors,
+NT-Xent terms and dz, projector backward, the joins of the pooled-feature gradient, the metadata branch
+(test_head_parity_gpu.py, test_head_parity_cpu.py; see the comment above HEAD_CASES).
+
+Not a conftest; changes no pytest setting.  SM3_GEOMETRY_MEASURE=<file>: check_run and check_head append one JSON line per
+case with the worst engine and restatement value of every metric (profiles/geometry_parity_measure.md and
+profiles/head_parity_measure.md are made from such runs)."""
 import json
 import os
 
@@ -610,3 +615,610 @@ def report(case, rep):
     print(f"{case}: by class, worst rel / worst |norm ratio - 1|: "
           + "; ".join(f"{s}: " + ", ".join(f"{c} {r[c + '_rel'][0]:.2e} ({r[c + '_rel'][1]}) / {r[c + '_ratio'][0]:.2e} ({r[c + '_ratio'][1]})"
                                          for c in ("conv", "bn", "in") if c + "_rel" in r) for s, r in rep.items()))
+
+
+# ======================================================================================================================
+# The head: everything past the layer4 tap of a training step, pinned to fp64 by teacher forcing
+# ======================================================================================================================
+# average pool -> in-modal projector over 2B rows -> cross-modal projectors over B rows, one pass per pair -> NT-Xent terms
+# with the weights 1 / 0.5 / 0.25 and the loss scale inside dz -> projector backward -> the into= / addend= accumulations
+# that make up the pooled-feature gradient -> the pool's backward; and the metadata branch.
+#
+#   * head_engine_run(): one train-mode step through SM3Trainer.step with the engine's bound methods wrapped on the
+#     instance (nothing of the engine changes): the return of forward, the dz handed to backward, the dfeat of every
+#     encoder_backward call, the layer4 taps.  kind "simclr" has no trainer (SM3Trainer drives the two-branch models): its
+#     step is forward -> sm3_ntxent_fused (the trainer's per-term launch) -> backward, without AdamW;
+#   * head_standin_run(): the same record from the reference alone on synthetic layer4 maps, with seeded defects;
+#   * head_tensors(): every compared tensor recomputed from the run's own INPUT to that step, in fp64 (q = _ident), as the
+#     mode restatement (q = rounder(dt)), or in float32.  The restatement's rounding points are read off the engine's code:
+#       - conv_bn: `xo` (the Linear output before its BatchNorm) is stored in the type and the batch statistics are those
+#         of the stored tensor; `y_out` (BatchNorm + ReLU) is stored in the type; bn7 writes fp32 (out_f32): not rounded;
+#       - the NT-Xent kernel stores dz in the type AFTER the multiplication by the loss scale (csrc/ntxent.hip, k = weight *
+#         dz_scale / (T R)); the trainer's `dz["cross0"][rows] += dd[:Bm]` is one more store per addend;
+#       - bn_backward writes the Linear-output gradient in the type (dxo = dy, in place); conv_backward writes the data
+#         gradient in the type, masked by the previous unit's ReLU in its epilogue (fuse=);
+#       - conv_backward(into=) is conv_gemm(..., into, into): accumulator + addend, ONE store per addend;
+#       - the pool writes its fp32 and 16-bit features from one accumulator, and dfeat / (h w) in the type;
+#       - weight gradients are fp32 sums in the flat buffer: not rounded;
+#   * check_head(): per tensor, limit = limits(BOUNDS[mode], the restatement's value on the same inputs) -- the rule of
+#     check_run, nothing else.  The loss is held to the tolerance tests/test_ntxent_edges_gpu.py holds the fused kernel to
+#     (edge_inputs.loss_limit, per term), the 16-bit pooled features to equality with the rounded fp32 ones, and
+#     num_batches_tracked to equality.
+#   * the pooled-feature gradient is compared per branch, over the rows of both views (the dfeat of every encoder_backward
+#     call, put back in view order): its norm ratio is a sum over elements and is sharper on 2B rows than on B.
+HEAD_T = 0.1
+META_PAD = 64
+# Both f16 cases carry the loss scale 1024.  (The trainer's default, GradScaler's 65536, is a starting point the scaler backs
+# off from whenever a step overflows; whether the first step at these shapes does was not measured, and a skipped step has
+# no gradient to compare.)
+HEAD_CASES = [  # id, kind, arch, style, mode, B, image side, proj_dim, metadata_dim, initial loss scale (f16)
+    dict(id="1-r18-v32s0-bf16-B64", kind="v32", arch="resnet18", style=0, mode="bf16", B=64, size=32, proj=128, meta=None,
+         scale=None),
+    dict(id="2-r18-v32s2-f16-B72", kind="v32", arch="resnet18", style=2, mode="f16", B=72, size=32, proj=128, meta=None,
+         scale=1024.0),
+    dict(id="3-r18-v32s1-p64-bf16-B40", kind="v32", arch="resnet18", style=1, mode="bf16", B=40, size=32, proj=64, meta=None,
+         scale=None, seed=1),
+    dict(id="4-r50-v32s0-bf16-B256", kind="v32", arch="resnet50", style=0, mode="bf16", B=256, size=32, proj=128, meta=None,
+         scale=None),
+    dict(id="5-r50-v3s2-f16-B64", kind="v3", arch="resnet50", style=2, mode="f16", B=64, size=32, proj=128, meta=None,
+         scale=1024.0),
+    dict(id="6-r18-v32s0-f32-B8", kind="v32", arch="resnet18", style=0, mode="f32", B=8, size=32, proj=128, meta=None,
+         scale=None, seed=1),
+    dict(id="7-r18-v32s0-meta20-bf16-B64", kind="v32", arch="resnet18", style=0, mode="bf16", B=64, size=32, proj=128,
+         meta=20, scale=None),
+    dict(id="8-r18-simclr-64px-bf16-B64", kind="simclr", arch="resnet18", style=0, mode="bf16", B=64, size=64, proj=128,
+         meta=None, scale=None),
+]
+# seed: of the stand-in's synthetic maps alone (head_standin_run; default 0).  Cases 3 and 6 take 1: the restatement's own norm
+# ratio of the pooled-feature gradient in bf16 -- 80 x 512 and 16 x 512 elements -- is 1.9e-4 .. 1.2e-3 over the seeds 0 .. 5
+# of case 3 and 8.1e-4 .. 2.3e-3 of case 6 (which no GPU case runs in 16 bit), and tests/test_head_parity_cpu.py keeps 3 x
+# that value <= 3e-3 so that the limit rule stays sharp.
+DEFAULT_INIT_SCALE = 65536.0  # SM3Trainer's (GradScaler's) default
+FEAT_DIM = {"resnet18": 512, "resnet50": 2048}
+
+
+def head_scale(case, dt):
+    """The loss scale of a case in the type dt: the case's own, or the trainer's default, in f16; none otherwise."""
+    return (case["scale"] or DEFAULT_INIT_SCALE) if dt == torch.float16 else 1.0
+
+
+def cross_pairs(style):
+    """The pair table of oracle.sm3_oracle.sm3_v32_projections (tests/test_head_parity_cpu.py holds it to that function)."""
+    return {0: [(0, 0), (1, 1)], 1: [(0, 1), (1, 0)], 2: [(0, 0), (0, 1), (1, 0), (1, 1)]}[style]
+
+
+def cross_weight(style):
+    """The weight of a cross term in oracle.sm3_oracle.sm3_loss (held to it by the same test)."""
+    return 0.25 if style == 2 else 0.5
+
+
+def valround(dt):
+    """A VALUE stored in the type (no autograd): the accumulations the engine does outside a differentiated chain."""
+    return (lambda x: x.to(dt).to(x.dtype)) if dt in (torch.bfloat16, torch.float16) else _ident
+
+
+def head_calls(kind, style, B, meta, pairs=None):
+    """The projector passes of a step in the reference's order (SimCLR.forward per branch, then _cal_logits per pair: derm
+    projector, clinic projector; then the metadata projector): dicts with the name of the z they write and its rows, the
+    parameter prefix, the branch whose pooled features they read and the rows of those."""
+    full, out = slice(0, 2 * B), []
+    if kind == "simclr":
+        return [dict(z="main", zrows=full, prefix="projector.", key="main", frows=full)]
+    for key in ("derm", "clinic"):
+        out.append(dict(z=key, zrows=full, prefix=f"{key}_backbone.projector.", key=key, frows=full))
+    cp = ("cross_proj.", "cross_proj.") if kind == "v3" else ("cross_proj.0.", "cross_proj.1.")
+    for ci, ab in enumerate(cross_pairs(style) if pairs is None else pairs):
+        for side, key in enumerate(("derm", "clinic")):
+            out.append(dict(z=f"cross{ci}", zrows=slice(side * B, (side + 1) * B), prefix=cp[side], key=key,
+                            frows=slice(ab[side] * B, (ab[side] + 1) * B)))
+    if meta:
+        out.append(dict(z="meta", zrows=slice(0, B), prefix="meta_proj.", key=None, frows=slice(0, B)))
+    return out
+
+
+def proj_ref(x, P, B, prefix, q=_ident, bn7=None):
+    """oracle.sm3_oracle.projector with the stores of a mode: q after every Linear and every BatchNorm + ReLU; the last
+    BatchNorm (affine=False) writes fp32.  bn7 (a seeded defect): (gamma, beta) of an affine it does not have."""
+    from oracle import sm3_oracle as O
+    h = q(F.linear(x, P[prefix + "0.weight"]))
+    h = q(F.relu(O.batchnorm(h, P, B, prefix + "1", True)))
+    h = q(F.linear(h, P[prefix + "3.weight"]))
+    h = q(F.relu(O.batchnorm(h, P, B, prefix + "4", True)))
+    h = q(F.linear(h, P[prefix + "6.weight"]))
+    if bn7 is not None:
+        Pd = {prefix + "7.weight": bn7[0].to(h.dtype), prefix + "7.bias": bn7[1].to(h.dtype)}
+        return O.batchnorm(h, Pd, B, prefix + "7", True, True)
+    return O.batchnorm(h, P, B, prefix + "7", True, False)
+
+
+def _proj_forward(calls, feats, meta_x, P, B, q, order=None, widen=False, once=False, bn7=None):
+    """Every projector pass of `calls` on the rows it reads -> [(call, leaf input, rows of the leaf the pass is about, z)],
+    the buffers B advancing in the order `order` (default: the order of calls).
+    Seeded defects: widen -- a cross pass normalises over all 2B rows of its modality; once -- a cross projector's running
+    statistics advance on its first pass only; bn7 -- {prefix: (gamma, beta)}."""
+    out = [None] * len(calls)
+    seen = set()
+    for i in (range(len(calls)) if order is None else order):
+        c = calls[i]
+        src = meta_x if c["key"] is None else feats[c["key"]]
+        cross = c["z"].startswith("cross")
+        rows = slice(0, src.shape[0]) if (widen and cross) else c["frows"]
+        x = src[rows].detach().clone().requires_grad_(True)
+        Bc = B
+        if once and cross and c["prefix"] in seen:
+            Bc = {k: v.clone() for k, v in B.items()}
+        seen.add(c["prefix"])
+        z = proj_ref(x, P, Bc, c["prefix"], q, (bn7 or {}).get(c["prefix"]))
+        take = c["frows"] if (widen and cross) else slice(0, x.shape[0])
+        out[i] = (c, x, take, z[take])
+    return out
+
+
+def _assemble_z(fw, B, proj):
+    zs = {}
+    for c, _, _, z in fw:
+        n = B if c["z"] == "meta" else 2 * B
+        zs.setdefault(c["z"], torch.zeros(n, proj, dtype=z.dtype, device=z.device))[c["zrows"]] = z.detach()
+    return zs
+
+
+def _head_loss(zs, style, B, T, wc=None):
+    """fp64 (or float32) NT-Xent of the projections with the weights of sm3_loss, and the trainer's two metadata terms.
+    -> (terms [(name, weighted loss)], pieces [(name, rows, d(term) / d(z[name][rows]), first)] in the order the trainer
+    stores / adds them: the first piece of a name is the kernel's store of the whole tensor, the others are `+=`)."""
+    from oracle import sm3_oracle as O
+    wc = cross_weight(style) if wc is None else wc
+    dev = next(iter(zs.values())).device  # the oracle's closed form builds its masks on the CPU: a few hundred rows, run there
+    leaf = {n: z.detach().cpu().clone().requires_grad_(True) for n, z in zs.items()}
+    terms, pieces = [], []
+    for n in leaf:
+        if n == "meta":
+            continue
+        t = (wc if n.startswith("cross") else 1.0) * O.ntxent_loss_closed_form(leaf[n], T)
+        terms.append((n, t.detach().to(dev)))
+        pieces.append((n, slice(0, 2 * B), torch.autograd.grad(t, leaf[n])[0].to(dev), True))
+    if "meta" in leaf:
+        for half in (0, 1):
+            rows = slice(half * B, (half + 1) * B)
+            t = 0.5 * O.ntxent_loss_closed_form(torch.cat([leaf["cross0"][rows], leaf["meta"]], 0), T)
+            gc, gm = torch.autograd.grad(t, [leaf["cross0"], leaf["meta"]])
+            terms.append((f"meta{half}", t.detach().to(dev)))
+            pieces.append(("cross0", rows, gc[rows].to(dev), False))
+            pieces.append(("meta", slice(0, B), gm.to(dev), half == 0))
+    return terms, pieces
+
+
+def _assemble_dz(pieces, scale, qv, skip=()):
+    """dz as the step leaves it: the kernel's store qv(scale * g) of every piece, `+=` pieces added in the type."""
+    dz = {}
+    for name, rows, g, first in pieces:
+        s = qv(scale * g)
+        if first:
+            dz[name] = s.clone()
+        elif name not in skip:
+            dz[name][rows] = qv(dz[name][rows] + s)
+    return dz
+
+
+def _proj_backward(fw, dz, dtype):
+    """Backward of every pass from its rows of dz: parameter gradients accumulate in the leaves of P, the input gradient of
+    a pass is its x.grad."""
+    for c, x, take, z in fw:
+        z.backward(dz[c["z"]][c["zrows"]].to(dtype))
+
+
+def _join(fw, B, qv, drop=None, view0_only=False):
+    """The pooled-feature gradient of every branch as _backward assembles it: the in-modal projector's data gradient
+    (conv_backward(addend=None): one store), then one conv_backward(into=) per cross pass in pair order: a store per addend.
+    Seeded defects: drop -- (branch, index of the addend left out); view0_only -- the in-modal gradient reaches view 0 only."""
+    dfe, n_add = {}, {}
+    for c, x, take, _ in fw:
+        key, g = c["key"], x.grad[take]
+        if key is None:
+            continue
+        if not c["z"].startswith("cross"):
+            dfe[key] = qv(g.clone())
+            if view0_only:
+                dfe[key][B:] = 0
+            continue
+        i = n_add[key] = n_add.get(key, -1) + 1
+        if drop == (key, i):
+            continue
+        dfe[key][c["frows"]] = qv(dfe[key][c["frows"]] + g)
+    return dfe
+
+
+def _pool_expand(df, hw, qv):
+    """avgpool_bwd: dfeat / (h w) at every pixel, stored in the type -> [N * hw, C]."""
+    return qv(df / hw).unsqueeze(1).expand(-1, hw, -1).reshape(df.shape[0] * hw, df.shape[1])
+
+
+def head_names(P):
+    return [n for n in P if "projector." in n or n.startswith(("cross_proj.", "meta_proj."))]
+
+
+def head_tensors(run, dtype, q, qv):
+    """Every compared tensor of the head, each from the run's own input to its step, in `dtype` with the stores q / qv.
+    Reads of the run: tap_x (-> pool), ft and meta_x (-> projectors, buffers), zs (-> loss, dz), dz and ft (-> projector
+    backward, joins, parameter gradients), dfeat (-> pool gradient); never f32, tap_g, bufs, grads or loss.
+    -> {name: (class, tensor)}; classes: out, stat, count, loss, dz, in, w, bn."""
+    B, hw, style, scale, kind = run["B"], run["hw"], run["style"], run["scale"], run["kind"]
+    out = {}
+    for key in run["branches"]:
+        x = run["tap_x"][key].to(dtype)
+        out[f"pool:{key}"] = ("out", x.view(2 * B, hw, -1).mean(1))
+        g = _pool_expand(run["dfeat"][key].to(dtype), hw, qv)
+        if run["g_pre_relu"][key]:
+            g = g * (run["tap_x"][key] > 0)
+        out[f"poolgrad:{key}"] = ("in", g / scale)
+    # projectors forward, the buffers' update sequence, and the backward from the run's own dz
+    names = head_names(run["P"])
+    P = {n: run["P"][n].to(dtype).clone().requires_grad_(True) for n in names}
+    Bf = {k: (v.to(dtype).clone() if v.is_floating_point() else v.clone()) for k, v in run["buf0"].items()
+          if any(k.startswith(c["prefix"]) for c in run["calls"])}
+    feats = {k: run["ft"][k].to(dtype) for k in run["branches"]}
+    meta_x = run["meta_x"].to(dtype) if run["meta_x"] is not None else None
+    fw = _proj_forward(run["calls"], feats, meta_x, P, Bf, q)
+    for n, z in _assemble_z(fw, B, run["proj"]).items():
+        out[f"z:{n}"] = ("out", z)
+    for k, v in Bf.items():
+        out[f"buf:{k}"] = ("count" if k.endswith("num_batches_tracked") else "stat", v)
+    _proj_backward(fw, {n: d.to(dtype) for n, d in run["dz"].items()}, dtype)
+    for key, d in _join(fw, B, qv).items():  # both views' rows: the norm concentrates better on 2B rows than on B
+        out[f"dfeat:{key}"] = ("in", d / scale)
+    for n in names:
+        out[f"grad:{n}"] = ("w" if P[n].dim() == 2 else "bn", P[n].grad / scale)
+    # loss and dz from the run's own projections
+    terms, pieces = _head_loss({n: z.to(dtype) for n, z in run["zs"].items()}, style, B, run["T"])
+    out["loss"] = ("loss", torch.stack([t for _, t in terms]))
+    for n, d in _assemble_dz(pieces, scale, qv).items():
+        out[f"dz:{n}"] = ("dz", d / scale)
+    return {k: (c, t.detach()) for k, (c, t) in out.items()}
+
+
+def head_got(run):
+    """The run's own tensors under the names of head_tensors."""
+    s, B, out = run["scale"], run["B"], {}
+    for key in run["branches"]:
+        out[f"pool:{key}"] = run["f32"][key]
+        out[f"poolgrad:{key}"] = run["tap_g"][key].double() / s
+        out[f"dfeat:{key}"] = run["dfeat"][key].double() / s
+    for n, z in run["zs"].items():
+        out[f"z:{n}"] = z
+    for k, v in run["bufs"].items():
+        out[f"buf:{k}"] = v
+    for n, d in run["dz"].items():
+        out[f"dz:{n}"] = d.double() / s
+    for n in head_names(run["P"]):
+        out[f"grad:{n}"] = run["grads"][n].double() / s
+    return out
+
+
+_CLASS_METRICS = {"out": ("out_rel", "out_max"), "stat": ("stat_rel",), "dz": ("cos", "rel"), "in": ("cos", "rel", "in_ratio"),
+                  "w": ("cos", "rel", "conv_ratio"), "bn": ("cos", "rel", "bn_ratio")}
+
+
+def head_metrics(cls, got, ref):
+    got, ref = got.double(), ref.double()
+    ratio = abs(float(got.norm() / (ref.norm() + 1e-300)) - 1)
+    vals = {"out_rel": rel(got, ref), "out_max": maxrel(got, ref), "stat_rel": rel(got, ref), "cos": cos(got, ref),
+            "rel": rel(got, ref), "in_ratio": ratio, "conv_ratio": ratio, "bn_ratio": ratio}
+    return {m: vals[m] for m in _CLASS_METRICS[cls]}
+
+
+def within(m, v, lim):
+    """NaN is outside every limit."""
+    return (v >= lim[m]) if m == "cos" else (v <= lim[m])
+
+
+def head_limits(run, base=None):
+    """-> (ref, restated values, limits) per tensor name: the fp64 tensors, the mode restatement's metrics against them, and
+    limits(BOUNDS[mode], those).  A function of the inputs head_tensors reads, and of nothing the run returned for that
+    step."""
+    dt = run["dt"]
+    base = base or bounds(DTNAME[dt])
+    rdt, q, qv = (torch.float32, _ident, _ident) if dt == torch.float32 else (torch.float64, rounder(dt), valround(dt))
+    ref = head_tensors(run, torch.float64, _ident, _ident)
+    rst = head_tensors(run, rdt, q, qv)
+    vals, lims = {}, {}
+    for name, (cls, t) in ref.items():
+        if cls in _CLASS_METRICS:
+            vals[name] = head_metrics(cls, rst[name][1], t)
+            lims[name] = limits({m: base[m] for m in _CLASS_METRICS[cls]}, vals[name])
+    return ref, vals, lims
+
+
+def nbt_expected(run):
+    """num_batches_tracked after the step: the pre-step count + the passes of that projector (+1 in-modal and metadata,
+    +len(pairs) per cross projector, +2 len(pairs) for v3's shared one)."""
+    out = {}
+    for c in run["calls"]:
+        for i in (1, 4, 7):
+            k = f"{c['prefix']}{i}.num_batches_tracked"
+            out[k] = out.get(k, int(run["buf0"][k])) + 1
+    return out
+
+
+def check_head(run, case, base=None):
+    """Teacher forcing over the head of `run` -> (rep, rest, fails, lims): the worst value per stage and metric of the run and
+    of the restatement against fp64, the tensors over their limit (name first), and the limits applied per tensor."""
+    from edge_inputs import loss_limit
+    dt = run["dt"]
+    ref, vals, lims = head_limits(run, base)
+    got = head_got(run)
+    rep, rest, fails = {}, {}, []
+    worse = lambda m: (lambda a, b: a < b) if m == "cos" else (lambda a, b: a > b)
+    for name, (cls, t) in ref.items():
+        stage = name.split(":")[0]
+        if cls == "count":
+            k = name[len("buf:"):]
+            if not (int(got[name]) == int(t) == nbt_expected(run)[k]):
+                fails.append((name, "num_batches_tracked", int(got[name]), int(t), nbt_expected(run)[k]))
+            continue
+        if cls == "loss":
+            lim = sum(loss_limit(float(x)) for x in t)
+            err = abs(run["loss"] - float(t.sum()))
+            record(rep, stage, "loss_err", name, err, lambda a, b: a > b)
+            record(rep, stage, "loss_lim", name, lim, lambda a, b: a > b)
+            if not err <= lim:
+                fails.append((name, "loss", run["loss"], float(t.sum()), lim))
+            continue
+        mine = head_metrics(cls, got[name], t)
+        for m, v in mine.items():
+            record(rep, stage, _REP_KEY[m], name, v, worse(m))
+            record(rest, stage, _REP_KEY[m], name, vals[name][m], worse(m))
+        bad = [m for m, v in mine.items() if not within(m, v, lims[name])]
+        if bad:
+            fails.append((name, cls, {m: (mine[m], lims[name][m]) for m in bad}))
+    for key in run["branches"]:  # one rounding of the pool's accumulator: the 16-bit features ARE the fp32 ones, rounded
+        if not torch.equal(run["ft"][key], run["f32"][key].to(dt)):
+            fails.append((f"pool:{key}:ft", "is not the fp32 feature rounded to the type",
+                          int((run["ft"][key] != run["f32"][key].to(dt)).sum())))
+    applied = {}
+    for name, lim in lims.items():
+        for m, v in lim.items():
+            applied[m] = min(applied.get(m, v), v) if m == "cos" else max(applied.get(m, v), v)
+    measure_line({"case": case, "engine": worst(rep), "restated": worst(rest), "limit": applied,
+                  "loss": {"err": rep["loss"]["loss_err"][0], "limit": rep["loss"]["loss_lim"][0]}})
+    return rep, rest, fails, lims
+
+
+def head_report(case, rep, rest, lims):
+    we, wr = worst(rep), worst(rest)
+    print(f"\n{case}: worst over the head's tensors, run / restatement: "
+          + ", ".join(f"{m} {we[m]:.3g} / {wr[m]:.3g}" for m in METRICS if m in we)
+          + f"; loss error {rep['loss']['loss_err'][0]:.2e} (limit {rep['loss']['loss_lim'][0]:.2e})")
+    print(f"{case}: per stage, worst tensor: "
+          + "; ".join(f"{s}: " + ", ".join(f"{k} {v:.3g} ({n})" for k, (v, n) in r.items()) for s, r in rep.items()))
+
+
+# ---- the runs -------------------------------------------------------------------------------------------------------
+def _perturb_head(named_modules, seed=13):
+    """Seeded, non-trivial affine parameters and running statistics for the projectors' BatchNorms (the fresh-module state
+    -- gamma 1, beta 0, mean 0, var 1 -- hides a wrong gamma or a skipped update)."""
+    g = torch.Generator().manual_seed(seed)
+    u = lambda t, a, b: t.copy_(torch.rand(t.shape, generator=g) * (b - a) + a)
+    with torch.no_grad():
+        for name, mod in named_modules:
+            if isinstance(mod, torch.nn.BatchNorm1d):
+                u(mod.running_mean, -0.1, 0.1)
+                u(mod.running_var, 0.5, 1.5)
+                if mod.affine:
+                    u(mod.weight, 0.5, 1.5)
+                    u(mod.bias, -0.2, 0.2)
+
+
+def head_metadata(B, d):
+    return torch.randn(B, d, generator=torch.Generator().manual_seed(41))
+
+
+def _meta_input(B, d, dt):
+    """The metadata projector's input as forward() makes it: zero-padded to META_PAD columns, cast to the type."""
+    x = torch.zeros(B, META_PAD)
+    x[:, :d] = head_metadata(B, d)
+    return x.to(dt)
+
+
+def head_setup(case, dt, dev, lanes=None):
+    """A fresh model, trainer (None for kind "simclr") and engine for a case, and the step's inputs."""
+    from sm3hip.bridge import sm3_engine_for
+    from sm3hip.trainer import SM3Trainer
+    from src.models.simclr import SimCLR, SimCLRSkinV3, SimCLRSkinV32
+    kind, B, size = case["kind"], case["B"], case["size"]
+    torch.manual_seed(5)
+    if kind == "v32":
+        model = SimCLRSkinV32(case["arch"], None, case["proj"], HEAD_T, metadata_dim=case["meta"])
+    elif kind == "v3":
+        model = SimCLRSkinV3(case["arch"], None, case["proj"], HEAD_T)
+    else:
+        model = SimCLR(case["arch"], None, case["proj"], HEAD_T)
+    _perturb_head([(n, m) for n, m in model.named_modules() if "projector" in n or n.startswith(("cross_proj", "meta_proj"))])
+    model.sm3_dtype = dt
+    model.to(dev).train()
+    tr = None
+    if kind != "simclr":
+        tr = SM3Trainer(model, lr=1e-3, weight_decay=5e-2, eps=1e-5, style=case["style"], init_scale=head_scale(case, dt))
+    eng = sm3_engine_for(model, kind)
+    if lanes is not None:
+        eng.two_streams, eng.lane_cross = lanes[0], lanes[1] and eng.lane_cross  # v3 keeps its lane_cross off
+    eng.prepare(torch.device(dev))
+    if kind == "simclr":
+        imgs = {"main": [images(B, size, size, f"main{v}").to(dev) for v in (0, 1)]}
+    else:
+        imgs = {k: [images(B, size, size, f"{k}{v}").to(dev) for v in (0, 1)] for k in ("derm", "clinic")}
+    meta = head_metadata(B, case["meta"]).to(dev) if case["meta"] else None
+    return model, tr, eng, imgs, meta
+
+
+def head_step(case, tr, eng, imgs, meta):
+    """One step -> the loss (a float).  kind "simclr": forward, the trainer's per-term NT-Xent launch, backward."""
+    from sm3hip import ops
+    if tr is not None:
+        return float(tr.step(imgs["derm"], imgs["clinic"], metadata=meta))
+    eng.store.flat_g.zero_()
+    zs, _, saved = eng.forward(imgs, 0, True, True)
+    z = zs["main"]
+    loss = torch.zeros(1, dtype=torch.float32, device=z.device)
+    dz = torch.empty(z.shape, dtype=eng.tdt, device=z.device)
+    ws = eng._work("ntxent_ws", ops.ntxent_workspace_floats(*z.shape))
+    ops.ntxent_fused(eng.dtype, z, HEAD_T, 1.0, ws, loss, dz, dz_scale=None)
+    eng.backward(saved, {"main": dz})
+    return float(loss)
+
+
+def head_engine_run(case, dt=None, dev="cuda:0", lanes=None):
+    """One train-mode step of a HEAD_CASES entry on the engine -> the record check_head reads."""
+    dt = dt or DTYPE[case["mode"]]
+    B, size = case["B"], case["size"]
+    model, tr, eng, imgs, meta = head_setup(case, dt, dev, lanes)
+    st = eng.store
+    wdt = dt if dt != torch.float32 else torch.float64
+    P = {n: st._view(st.flat_p, n).detach().clone() for n in st.names}
+    P = {n: (w.to(wdt).double() if w.dim() >= 2 else w.double()) for n, w in P.items()}  # Linear weights are filter banks
+    buf0 = {k: b.detach().clone() for k, b in model.named_buffers()}
+    cap = dict(taps={}, order=[], dfeat=[], scale=1.0)
+    real = dict(forward=eng.forward, backward=eng.backward, ef=eng.encoder_forward, eb=eng.encoder_backward)
+
+    def encoder_forward(plan, x, train, feat_f32, feat_t, save=None, **kw):
+        taps = {}
+        real["ef"](plan, x, train, feat_f32, feat_t, save, taps=taps, **kw)
+        cap["taps"][id(save[-1])] = (plan.prefix, kw.get("views", 1), taps, save[-1])
+
+    def encoder_backward(ctx, dfeat, *a, **kw):
+        taps = cap["taps"][id(ctx)][2]
+        cap["dfeat"].append((id(ctx), dfeat.clone()))
+        return real["eb"](ctx, dfeat, *a, taps=taps, **kw)
+
+    def forward(*a, **kw):
+        out = real["forward"](*a, **kw)
+        cap["fwd"] = (dict(out[0]), out[1])  # a copy of the dict: the trainer pops "meta" from its own
+        return out
+
+    def backward(saved, dz, *a, **kw):
+        cap["dz"] = {n: d.clone() for n, d in dz.items()}
+        if tr is not None and tr._scaler is not None:
+            cap["scale"] = tr._scaler["scale"].clone()  # no host read inside the step
+        out = real["backward"](saved, dz, *a, **kw)
+        cap["grads"] = st.flat_g.clone()  # as the backward pass left them (an AdamW launch may follow)
+        return out
+
+    eng.forward, eng.backward, eng.encoder_forward, eng.encoder_backward = forward, backward, encoder_forward, encoder_backward
+    try:
+        loss = head_step(case, tr, eng, imgs, meta)
+        torch.cuda.synchronize()
+    finally:
+        for k in ("forward", "backward", "encoder_forward", "encoder_backward"):
+            delattr(eng, k)
+    zs, feats = cap["fwd"]
+    branches = list(eng.branches)
+    hw_ = maps_of(size, size)[4]
+    hw = hw_[0] * hw_[1]
+    # the encoder passes of a branch, in forward order: one pair pass, or view 0 then view 1
+    passes = {k: [] for k in branches}
+    for cid, (prefix, views, taps, ctx) in cap["taps"].items():
+        key = next(k for k in branches if eng.branches[k][0].prefix == prefix)
+        passes[key].append((cid, views, taps))
+    dfe = dict(cap["dfeat"])
+    tap_x, tap_g, pre, dfeat = {}, {}, {}, {}
+    for key, ps in passes.items():
+        assert [v for _, v, _ in ps] in ([2], [1, 1]), ps
+        tap_x[key] = torch.cat([t["x"][-1] for _, _, t in ps], 0)
+        tap_g[key] = torch.cat([t["g"][-1] for _, _, t in ps], 0)
+        pre[key] = any(t["g_pre_relu"][-1] for _, _, t in ps)
+        dfeat[key] = torch.cat([dfe[cid] for cid, _, _ in ps], 0)
+        assert tap_x[key].shape[0] == 2 * B * hw
+    grads = {n: st._view(cap["grads"], n) for n in st.names}
+    meta_x = _meta_input(B, case["meta"], dt).to(dev) if case["meta"] else None
+    return dict(kind=case["kind"], style=case["style"], dt=dt, B=B, hw=hw, proj=case["proj"], T=HEAD_T,
+                scale=float(cap["scale"]), branches=branches, calls=head_calls(case["kind"], case["style"], B, case["meta"]),
+                P=P, buf0=buf0, bufs=dict(model.named_buffers()), tap_x=tap_x, tap_g=tap_g, g_pre_relu=pre,
+                f32={k: feats[k][0] for k in branches}, ft={k: feats[k][1] for k in branches}, zs=dict(zs), dz=cap["dz"],
+                dfeat=dfeat, grads=grads, loss=loss, meta_x=meta_x,
+                paired={k: len(ps) == 1 for k, ps in passes.items()}, eng=eng, trainer=tr, model=model)
+
+
+def _head_modules(case):
+    """The projectors of a case's model alone (no encoders), under the names the model gives them."""
+    from src.models.simclr import make_projector
+    C, proj = FEAT_DIM[case["arch"]], case["proj"]
+    torch.manual_seed(5)
+    if case["kind"] == "simclr":
+        return {"projector.": make_projector(C, proj)}
+    mods = {f"{k}_backbone.projector.": make_projector(C, proj) for k in ("derm", "clinic")}
+    if case["kind"] == "v3":
+        mods["cross_proj."] = make_projector(C, proj)
+    else:
+        mods["cross_proj.0."], mods["cross_proj.1."] = make_projector(C, proj), make_projector(C, proj)
+    if case["meta"]:
+        mods["meta_proj."] = make_projector(META_PAD, proj)
+    return mods
+
+
+HEAD_DEFECTS = ("pairs_style0", "cross_weight_half", "cross_bn_2B", "cross_stats_once", "v3_order", "bn7_affine", "drop_into",
+                "addend_view0", "dz_scaled", "meta_not_added", "pool_twice")
+
+
+def head_standin_run(case, dt, defects=(), dev="cpu"):
+    """The record head_engine_run returns, from the reference alone: the mode restatement of the head chained from seeded
+    synthetic layer4 maps (ReLU of a Gaussian with per-channel scales, stored in the type) through the pool, the projectors,
+    the loss, dz, the projector backward, the joins and the pool's backward, with autograd inside every piece.
+    defects: names of HEAD_DEFECTS seeded into the chain (never into the record's description of the step)."""
+    defects = set(defects)
+    assert defects <= set(HEAD_DEFECTS), defects
+    kind, style, B, proj = case["kind"], case["style"], case["B"], case["proj"]
+    C = FEAT_DIM[case["arch"]]
+    hw_ = maps_of(case["size"], case["size"])[4]
+    hw = hw_[0] * hw_[1]
+    edt = torch.float32 if dt == torch.float32 else torch.float64
+    q, qv = rounder(dt), valround(dt)
+    wdt = dt if dt != torch.float32 else torch.float64
+    scale = head_scale(case, dt)
+    mods = _head_modules(case)
+    _perturb_head([(p, m) for p, seq in mods.items() for m in seq])
+    P, buf0 = {}, {}
+    for p, seq in mods.items():
+        for n, w in seq.named_parameters():
+            P[p + n] = (w.detach().to(wdt).double() if w.dim() >= 2 else w.detach().double()).to(dev)
+        for n, b in seq.named_buffers():
+            buf0[p + n] = b.detach().clone().to(dev)
+    Pl = {n: w.to(edt).clone().requires_grad_(True) for n, w in P.items()}
+    Bl = {k: (v.to(edt).clone() if v.is_floating_point() else v.clone()) for k, v in buf0.items()}
+    branches = ["main"] if kind == "simclr" else ["derm", "clinic"]
+    tap_x, f32, ft = {}, {}, {}
+    for i, key in enumerate(branches):
+        g = torch.Generator().manual_seed(101 + i + 1000 * case.get("seed", 0))
+        scales = torch.exp(0.5 * torch.randn(C, generator=g))
+        tap_x[key] = F.relu(torch.randn(2 * B * hw, C, generator=g) * scales).to(dt).to(dev)
+        f32[key] = tap_x[key].to(edt).view(2 * B, hw, C).mean(1).float()
+        ft[key] = f32[key].to(dt)
+    meta_x = _meta_input(B, case["meta"], dt).to(dev) if case["meta"] else None
+    calls = head_calls(kind, style, B, case["meta"])
+    mine = head_calls(kind, style, B, case["meta"], pairs=cross_pairs(0)) if "pairs_style0" in defects else calls
+    order = None
+    if "v3_order" in defects:  # all derm passes of the shared projector, then all clinic ones
+        cross = [i for i, c in enumerate(mine) if c["z"].startswith("cross")]
+        rest = [i for i in range(len(mine)) if i not in cross]
+        order = [i for i in rest if mine[i]["key"] is not None] + [i for i in cross if mine[i]["key"] == "derm"] \
+            + [i for i in cross if mine[i]["key"] == "clinic"] + [i for i in rest if mine[i]["key"] is None]
+    bn7 = None
+    if "bn7_affine" in defects:
+        g = torch.Generator().manual_seed(3)
+        bn7 = {p: (1 + 0.1 * torch.randn(proj, generator=g), 0.1 * torch.randn(proj, generator=g)) for p in mods}
+    fw = _proj_forward(mine, {k: ft[k].to(edt) for k in branches}, None if meta_x is None else meta_x.to(edt), Pl, Bl, q,
+                       order=order, widen="cross_bn_2B" in defects, once="cross_stats_once" in defects, bn7=bn7)
+    zs = {n: z.float() for n, z in _assemble_z(fw, B, proj).items()}
+    terms, pieces = _head_loss({n: z.to(edt) for n, z in zs.items()}, style, B, HEAD_T,
+                               wc=0.5 if "cross_weight_half" in defects else None)
+    loss = float(sum(float(t) for _, t in terms))
+    dz = _assemble_dz(pieces, scale * (scale if "dz_scaled" in defects else 1.0), qv,
+                      skip=("cross0",) if "meta_not_added" in defects else ())
+    dz = {n: d.to(dt) for n, d in dz.items()}
+    _proj_backward(fw, dz, edt)
+    dfe = _join(fw, B, qv, drop=("derm", len(cross_pairs(style)) - 1) if "drop_into" in defects else None,
+                view0_only="addend_view0" in defects)
+    dfeat = {k: d.to(dt) for k, d in dfe.items()}
+    tap_g = {k: _pool_expand(dfeat[k].to(edt) / (hw if "pool_twice" in defects else 1), hw, qv).to(dt) for k in branches}
+    grads = {n: (w.grad if w.grad is not None else torch.zeros_like(w)) for n, w in Pl.items()}
+    return dict(kind=kind, style=style, dt=dt, B=B, hw=hw, proj=proj, T=HEAD_T, scale=scale, branches=branches, calls=calls,
+                P=P, buf0=buf0, bufs=Bl, tap_x=tap_x, tap_g=tap_g, g_pre_relu={k: False for k in branches}, f32=f32, ft=ft,
+                zs=zs, dz=dz, dfeat=dfeat, grads=grads, loss=loss, meta_x=meta_x)
