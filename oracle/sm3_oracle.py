@@ -43,7 +43,7 @@ def batchnorm(x, P, B, prefix, training, affine=True, stat_reduce=None):
     shape = [1, c] + [1] * (x.dim() - 2)
     if training:
         n = x.numel() // c
-        cnt = torch.tensor([float(n)], dtype=x.dtype)
+        cnt = torch.tensor([float(n)], dtype=x.dtype, device=x.device)
         if stat_reduce is not None:
             # SyncBatchNorm: statistics of the global batch from summed (sum x, sum x^2, count)
             packed = stat_reduce(torch.cat([x.sum(dim=dims), (x * x).sum(dim=dims), cnt]))

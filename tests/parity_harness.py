@@ -16,6 +16,8 @@ test_geometry_parity_gpu.py, test_parity_harness_cpu.py): every unit of an encod
         limit = max(BOUNDS[mode][metric], 3 x the restatement's value on that same unit, same inputs, same upstream gradient)
     (cosine: min(BOUNDS cos, 1 - 3 (1 - cos_restated))).  BOUNDS is test_block_parity_gpu.py's table, measured at the
     benchmarked shapes; the second term comes from the reference alone.  No limit is derived from what the engine returned.
+  * ranks (test_dp_parity_gpu.py, test_dp_parity_cpu.py): engine_run / standin_run as rank r of a data-parallel step with
+    synchronised BatchNorm, check_run(stat_reduce=all_reduce_sum) as its fp64 reference, seeded defects of the exchange.
 
 The second half of the file does the same for the HEAD of a training step -- everything past the layer4 tap: pool, projectors,
 NT-Xent terms and dz, projector backward, the joins of the pooled-feature gradient, the metadata branch
@@ -26,6 +28,7 @@ case with the worst engine and restatement value of every metric (profiles/geome
 profiles/head_parity_measure.md are made from such runs)."""
 import json
 import os
+import sys
 
 import torch
 import torch.nn.functional as F
@@ -144,11 +147,88 @@ class Conv(torch.autograd.Function):
         return dx, dw, None, None, None
 
 
-def bn(t, P, B, name, V):
-    """Train-mode BatchNorm of an NHWC map whose V views lie back to back: the oracle once per view, in view order."""
+def bn(t, P, B, name, V, stat_reduce=None):
+    """Train-mode BatchNorm of an NHWC map whose V views lie back to back: the oracle once per view, in view order.
+    stat_reduce (SyncBatchNorm): sums the oracle's packed [sum x, sum x^2, count] over the ranks (all_reduce_sum).
+    The float32 restatement hands the oracle its map in fp64 then and takes the result back in float32: the packed sums are
+    the one-pass form (sum x^2 / n - mean^2), which in float32 cancels where ATen's two-pass form of the single-rank call
+    does not, and the exchange format of the project is fp64 sums.  Measured on resnet50 f32, 2 ranks x 16 at 73 x 37: the
+    restatement's running statistics at 3.7e-7 with float32 sums (limit 1.1e-6, above BOUNDS' 5e-7), 8.6e-8 with fp64 ones."""
     from oracle import sm3_oracle as O
-    outs = [O.batchnorm(c.permute(0, 3, 1, 2), P, B, name, True).permute(0, 2, 3, 1) for c in t.chunk(V, 0)]
-    return outs[0] if V == 1 else torch.cat(outs, 0)
+    up = stat_reduce is not None and t.dtype == torch.float32
+    outs = [O.batchnorm((c.double() if up else c).permute(0, 3, 1, 2), P, B, name, True, True, stat_reduce).permute(0, 2, 3, 1)
+            for c in t.chunk(V, 0)]
+    out = outs[0] if V == 1 else torch.cat(outs, 0)
+    return out.to(t.dtype) if up else out
+
+
+# ---- ranks: the exchange of SyncBatchNorm, and seeded defects of it (stand-in only) ---------------------------------------
+class AllReduceSum(torch.autograd.Function):
+    """Sum over the ranks of the default process group, forward and of the gradient backward: with it as a BatchNorm's
+    stat_reduce the fp64 gradient on a rank is SyncBatchNorm's -- the global sums of dz and dz * xhat over the global count.
+    Works on fp64 CUDA tensors over gloo (through host memory, as the engine's own stat_sync does)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        import torch.distributed as dist
+        y = x.clone()
+        dist.all_reduce(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        import torch.distributed as dist
+        g = g.clone()
+        dist.all_reduce(g)
+        return g
+
+
+all_reduce_sum = AllReduceSum.apply
+
+
+class _ForwardOnlyReduce(torch.autograd.Function):
+    """Seeded defect: the backward exchange dropped.  Forward the sum over ranks; backward the same collective, its result
+    discarded (the ranks stay in step) and the gradient of the packed sums kept local."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return AllReduceSum.forward(ctx, x)
+
+    @staticmethod
+    def backward(ctx, g):
+        AllReduceSum.backward(ctx, g)
+        return g
+
+
+class _NoReduce(torch.autograd.Function):
+    """Seeded defect: statistics left local.  Both collectives of a clean reducer are issued and their results discarded."""
+
+    @staticmethod
+    def forward(ctx, x):
+        AllReduceSum.forward(ctx, x)
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        AllReduceSum.backward(ctx, g)
+        return g
+
+
+def reduce_local_count(t):
+    """Seeded defect: the summed sums over the LOCAL count (the last element of the oracle's packed vector)."""
+    return torch.cat([all_reduce_sum(t)[:-1], t[-1:]])
+
+
+reduce_forward_only = _ForwardOnlyReduce.apply
+reduce_nothing = _NoReduce.apply
+
+
+def _reducer(defect, name, stat_reduce):
+    """The reducer of the BatchNorm `name` ("bn1" ... "downsample.1") of a unit: the run's, unless a defect names that
+    BatchNorm under "reduce" ({BatchNorm name: reducer}).  A single-rank run has none, seeded or not."""
+    if stat_reduce is None:
+        return None
+    return (defect or {}).get("reduce", {}).get(name, stat_reduce)
 
 
 # ---- the roundings of a mode, and seeded defects (stand-in only) --------------------------------------------------------
@@ -188,49 +268,53 @@ def rounder(dt):
 
 
 # ---- the units: fp64 with q = identity, the 16-bit restatement with q = rounder(dt), f32 by float32 tensors ------------
-def block_ref(x, P, B, p, stride, V, groups=1, q=_ident, defect=None):
+def block_ref(x, P, B, p, stride, V, groups=1, q=_ident, defect=None, stat_reduce=None):
     """Bottleneck.forward (src/models/resnet.py:154-174) -> (pre-ReLU sum out + identity, block output)."""
     d = defect or {}
+    sr = lambda name: _reducer(d, name, stat_reduce)
     x = q(x)
     out = Conv.apply(x, P[p + "conv1.weight"], 1, 0)
-    out = q(F.relu(bn(d.get("bn1", _ident)(q(out)), P, B, p + "bn1", V)))
-    out = q(F.relu(bn(q(Conv.apply(out, P[p + "conv2.weight"], stride, 1, groups)), P, B, p + "bn2", V)))
-    out = q(bn(q(Conv.apply(out, P[p + "conv3.weight"], 1, 0)), P, B, p + "bn3", V))
+    out = q(F.relu(bn(d.get("bn1", _ident)(q(out)), P, B, p + "bn1", V, sr("bn1"))))
+    out = q(F.relu(bn(q(Conv.apply(out, P[p + "conv2.weight"], stride, 1, groups)), P, B, p + "bn2", V, sr("bn2"))))
+    out = q(bn(q(Conv.apply(out, P[p + "conv3.weight"], 1, 0)), P, B, p + "bn3", V, sr("bn3")))
     if p + "downsample.0.weight" in P:
-        idn = q(bn(q(Conv.apply(d.get("idn", _ident)(x), P[p + "downsample.0.weight"], stride, 0)), P, B, p + "downsample.1", V))
+        idn = q(bn(q(Conv.apply(d.get("idn", _ident)(x), P[p + "downsample.0.weight"], stride, 0)), P, B, p + "downsample.1", V,
+                   sr("downsample.1")))
     else:
         idn = d.get("idn", _ident)(x)
     pre = q(out + idn)
     return pre, F.relu(pre)
 
 
-def basic_ref(x, P, B, p, stride, V, q=_ident, defect=None):
+def basic_ref(x, P, B, p, stride, V, q=_ident, defect=None, stat_reduce=None):
     """BasicBlock.forward (src/models/resnet.py:91-106) on NHWC maps -> (pre-ReLU sum, block output)."""
     d = defect or {}
+    sr = lambda name: _reducer(d, name, stat_reduce)
     x = q(x)
     out = Conv.apply(x, P[p + "conv1.weight"], stride, 1)
-    out = q(F.relu(bn(d.get("bn1", _ident)(q(out)), P, B, p + "bn1", V)))
-    out = q(bn(q(Conv.apply(out, P[p + "conv2.weight"], 1, 1)), P, B, p + "bn2", V))
+    out = q(F.relu(bn(d.get("bn1", _ident)(q(out)), P, B, p + "bn1", V, sr("bn1"))))
+    out = q(bn(q(Conv.apply(out, P[p + "conv2.weight"], 1, 1)), P, B, p + "bn2", V, sr("bn2")))
     if p + "downsample.0.weight" in P:
-        idn = q(bn(q(Conv.apply(d.get("idn", _ident)(x), P[p + "downsample.0.weight"], stride, 0)), P, B, p + "downsample.1", V))
+        idn = q(bn(q(Conv.apply(d.get("idn", _ident)(x), P[p + "downsample.0.weight"], stride, 0)), P, B, p + "downsample.1", V,
+                   sr("downsample.1")))
     else:
         idn = d.get("idn", _ident)(x)
     pre = q(out + idn)
     return pre, F.relu(pre)
 
 
-def stem_ref(img, P, B, V, q=_ident):
+def stem_ref(img, P, B, V, q=_ident, stat_reduce=None):
     """conv1 7x7/2 -> bn1 -> ReLU -> max-pool 3x3/2 (src/models/resnet.py:292-297) on NCHW images -> NHWC map."""
     x = img.permute(0, 2, 3, 1)
-    y = q(F.relu(bn(q(Conv.apply(x, P["conv1.weight"], 2, 3)), P, B, "bn1", V)))
+    y = q(F.relu(bn(q(Conv.apply(x, P["conv1.weight"], 2, 3)), P, B, "bn1", V, stat_reduce)))
     return q(F.max_pool2d(y.permute(0, 3, 1, 2), kernel_size=3, stride=2, padding=1).permute(0, 2, 3, 1))
 
 
-def unit_ref(x, P, B, blk, V, q=_ident, defect=None):
+def unit_ref(x, P, B, blk, V, q=_ident, defect=None, stat_reduce=None):
     """The block `blk` of a run's unit list -> (pre, out)."""
     if blk["basic"]:
-        return basic_ref(x, P, B, blk["prefix"], blk["stride"], V, q, defect)
-    return block_ref(x, P, B, blk["prefix"], blk["stride"], V, blk["groups"], q, defect)
+        return basic_ref(x, P, B, blk["prefix"], blk["stride"], V, q, defect, stat_reduce)
+    return block_ref(x, P, B, blk["prefix"], blk["stride"], V, blk["groups"], q, defect, stat_reduce)
 
 
 # ---- metrics ----------------------------------------------------------------------------------------------------------
@@ -360,19 +444,32 @@ def describe_units(P, prefixes):
     return units
 
 
-def engine_run(arch, dt, N, V, H, W, dev="cuda:0"):
-    """One train-mode forward + backward of an encoder-only engine with taps.  Returns what the reference needs."""
+def rank_inputs(N, V, H, W, out_dim, rank=0):
+    """What rank `rank` feeds a run: ([one batch of N // V images per view], the gradient of the pooled features [N, out_dim]).
+    The ranks' shards differ clearly -- other procedural images (a rank suffix on the tag), another seed of the gradient --
+    and rank 0 gets the tensors a single-rank run always got."""
+    sfx = f"-rank{rank}" if rank else ""
+    imgs = [images(N // V, H, W, f"view{v}{sfx}") for v in range(V)]
+    return imgs, torch.randn(N, out_dim, generator=torch.Generator().manual_seed(29 + rank))
+
+
+def engine_run(arch, dt, N, V, H, W, dev="cuda:0", rank=0, world=1, stat_sync=None):
+    """One train-mode forward + backward of an encoder-only engine with taps.  Returns what the reference needs.
+    world > 1: the step of rank `rank` of a data-parallel run over N images PER RANK -- the same weights on every rank,
+    rank_inputs' shard, and stat_sync (a callable that sums an fp64 CUDA tensor over the ranks in place) installed as a
+    trainer installs it."""
     from sm3hip.engine import SM3Engine
     m = _encoder(arch)
     m.to(dev).train()
     eng = SM3Engine(m, dtype=dt, kind="encoder")
+    if world > 1:
+        assert stat_sync is not None
+        eng.stat_sync, eng.world_size, eng._explicit_sync = stat_sync, world, True
     eng.prepare(torch.device(dev))
     eng.refresh_weights()
     plan = eng.branches["main"][0]
-    B = N // V
-    imgs = [images(B, H, W, f"view{v}").to(dev) for v in range(V)]
-    g = torch.Generator().manual_seed(29)
-    dfeat = torch.randn(N, plan.out_dim, generator=g).to(dev)
+    imgs, dfeat = rank_inputs(N, V, H, W, plan.out_dim, rank)
+    imgs, dfeat = [t.to(dev) for t in imgs], dfeat.to(dev)
     buf0 = {k: b.detach().clone() for k, b in m.named_buffers()}  # the running statistics before the step
     feats = torch.empty(N, plan.out_dim, device=dev)
     ctx, taps = [], {}
@@ -400,10 +497,15 @@ def engine_run(arch, dt, N, V, H, W, dev="cuda:0"):
                 views_ran=views_ran, N=N, V=V, maps=maps_of(H, W), dt=dt)
 
 
-def standin_run(arch, dt, N, V, H, W, dev="cpu", defects=None):
+def standin_run(arch, dt, N, V, H, W, dev="cpu", defects=None, rank=0, world=1, stat_reduce=None, shards=None):
     """The record engine_run returns, from the reference alone: the mode restatement of every unit chained into a whole
     encoder, one train-mode forward + backward under autograd.  Every boundary gradient is with respect to the block's
-    output (g_pre_relu False).  defects: {unit prefix: {"bn1" | "idn": function}} seeded into those units."""
+    output (g_pre_relu False).  defects: {unit prefix: {"bn1" | "idn": function, "reduce": {BatchNorm name: reducer}}}
+    seeded into those units.
+    world > 1: rank `rank` of a data-parallel run over N images per rank; stat_reduce (all_reduce_sum) goes to every
+    BatchNorm.  shards (one view): the ranks whose inputs, back to back, make up this run's batch of N images -- the
+    single-process full batch that a sharded run is compared with."""
+    assert world == 1 or stat_reduce is not None
     m = _encoder(arch).train()
     edt = torch.float32 if dt == torch.float32 else torch.float64
     q = rounder(dt)
@@ -413,18 +515,23 @@ def standin_run(arch, dt, N, V, H, W, dev="cpu", defects=None):
     units = describe_units(P, _units(P))
     Pl = {n: w.to(edt).clone().requires_grad_(True) for n, w in P.items()}
     Bl = {k: (v.to(edt).clone() if v.is_floating_point() else v.clone()) for k, v in buf0.items()}
-    B = N // V
-    img = torch.cat([images(B, H, W, f"view{v}") for v in range(V)], 0).to(dev)
+    out_dim = P[units[-1]["prefix"] + ("bn2" if units[-1]["basic"] else "bn3") + ".weight"].shape[0]
+    if shards is None:
+        imgs, dfeat = rank_inputs(N, V, H, W, out_dim, rank)
+    else:
+        assert V == 1 and N % len(shards) == 0
+        parts = [rank_inputs(N // len(shards), 1, H, W, out_dim, r) for r in shards]
+        imgs, dfeat = [torch.cat([p[0][0] for p in parts], 0)], torch.cat([p[1] for p in parts], 0)
+    img, dfeat = torch.cat(imgs, 0).to(dev), dfeat.to(dev)
     if dt != torch.float32:
         img = img.to(dt)
-    xs = [stem_ref(img.to(edt), Pl, Bl, V, q)]
+    xs = [stem_ref(img.to(edt), Pl, Bl, V, q, stat_reduce)]
     for u in units:
         x = xs[-1]
         x.retain_grad()
-        xs.append(unit_ref(x, Pl, Bl, u, V, q, (defects or {}).get(u["prefix"]))[1])
+        xs.append(unit_ref(x, Pl, Bl, u, V, q, (defects or {}).get(u["prefix"]), stat_reduce)[1])
     xs[-1].retain_grad()
-    out_dim = xs[-1].shape[-1]
-    dfeat = torch.randn(N, out_dim, generator=torch.Generator().manual_seed(29)).to(dev)
+    assert xs[-1].shape[-1] == out_dim
     if dt != torch.float32:
         dfeat = dfeat.to(dt)
     xs[-1].mean(dim=(1, 2)).backward(dfeat.to(edt))
@@ -435,14 +542,14 @@ def standin_run(arch, dt, N, V, H, W, dev="cpu", defects=None):
 
 
 # ---- every unit of a run against fp64, limits by the rule ------------------------------------------------------------
-def _unit_pass(run, ui, dtype, q):
+def _unit_pass(run, ui, dtype, q, stat_reduce=None):
     """Unit ui (0: the stem) recomputed from the run's own input and upstream gradient, in `dtype` with the stores `q`.
     -> (names, P, B, output, input gradient or None), the gradient masked as the run's boundary gradient is."""
     N, V, maps, taps = run["N"], run["V"], run["maps"], run["taps"]
     if ui == 0:
         names = ["conv1.weight", "bn1.weight", "bn1.bias"]
         P, B = ref_params(run, "bn1.", names, dtype)
-        out = stem_ref(run["img"].to(dtype), P, B, V, q)
+        out = stem_ref(run["img"].to(dtype), P, B, V, q, stat_reduce)
         out.backward(hwc(taps["g"][0], N, maps[1]).to(dtype))
         return names, P, B, out.detach(), None
     blk = run["units"][ui - 1]
@@ -451,7 +558,7 @@ def _unit_pass(run, ui, dtype, q):
     P, B = ref_params(run, prefix, names, dtype)
     x = hwc(taps["x"][ui - 1], N, stage_map(maps, run["units"][ui - 2]["prefix"] if ui > 1 else "")).to(dtype)
     x.requires_grad_(True)
-    pre, out = unit_ref(x, P, B, blk, V, q)
+    pre, out = unit_ref(x, P, B, blk, V, q, None, stat_reduce)
     gup = hwc(taps["g"][ui], N, stage_map(maps, prefix)).to(dtype)
     (pre if taps["g_pre_relu"][ui] else out).backward(gup)
     dx = x.grad
@@ -460,11 +567,15 @@ def _unit_pass(run, ui, dtype, q):
     return names, P, B, out.detach(), dx
 
 
-def check_run(run, case, base=None, restate=True):
+def check_run(run, case, base=None, restate=True, stat_reduce=None):
     """Teacher forcing over every unit of `run`.  -> (rep, rest, fails): the per-stage record of the run against fp64, the
     same record of the mode restatement against fp64, and the tensors over their limit.
     base: the mode's bounds (default: BOUNDS of the run's dtype); restate=False: those bounds alone (the cases that
-    test_block_parity_gpu.py holds at the benchmarked shapes)."""
+    test_block_parity_gpu.py holds at the benchmarked shapes).
+    stat_reduce (the run is one rank of a data-parallel step): handed to every BatchNorm of the fp64 pass and of the
+    restatement, so a unit's reference is SyncBatchNorm's on this rank's shard: global batch statistics and running
+    statistics, local parameter gradients.  Every rank must call this with the same unit list: each BatchNorm is a
+    collective, so the loop below never skips a unit or ends early on one rank."""
     dt, N, V, maps, taps = run["dt"], run["N"], run["V"], run["maps"], run["taps"]
     base = base or bounds(DTNAME[dt])
     assert len(taps["x"]) == len(taps["g"]) == len(run["units"]) + 1
@@ -473,10 +584,10 @@ def check_run(run, case, base=None, restate=True):
     for ui in range(len(run["units"]) + 1):
         prefix = run["units"][ui - 1]["prefix"] if ui else ""
         stage = stage_of(prefix)
-        names, P, B, out, dx = _unit_pass(run, ui, torch.float64, _ident)
+        names, P, B, out, dx = _unit_pass(run, ui, torch.float64, _ident, stat_reduce)
         lim = base
         if restate:
-            _, Pq, Bq, outq, dxq = _unit_pass(run, ui, rdt, q)
+            _, Pq, Bq, outq, dxq = _unit_pass(run, ui, rdt, q, stat_reduce)
             mine = dict(bufs=Bq, buf0=run["buf0"], grads={n: Pq[n].grad for n in names})
             one, bad = {}, []
             compare_unit(mine, dt, prefix, "u", names, out, outq.double(), dx, None if dxq is None else dxq.double(),
@@ -615,6 +726,76 @@ def report(case, rep):
     print(f"{case}: by class, worst rel / worst |norm ratio - 1|: "
           + "; ".join(f"{s}: " + ", ".join(f"{c} {r[c + '_rel'][0]:.2e} ({r[c + '_rel'][1]}) / {r[c + '_ratio'][0]:.2e} ({r[c + '_ratio'][1]})"
                                          for c in ("conv", "bn", "in") if c + "_rel" in r) for s, r in rep.items()))
+
+
+# ---- ranks as processes: one gloo group per world size, its cases one after the other -----------------------------------
+def _rank_entry(fn, rank, world, port, q, cases, collective_s, threads):
+    """Process `rank` of a group: fn(rank, world, case) for every case, in order -> q.put((rank, case index, True, payload));
+    an exception ends the process with (rank, None, False, traceback).  Payloads are plain Python values."""
+    import datetime
+    import traceback
+    import torch.distributed as dist
+    try:
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        for p in (root, os.path.join(root, "skin-sm3_amd"), os.path.join(root, "tests")):
+            if p not in sys.path:
+                sys.path.insert(0, p)
+        torch.set_num_threads(threads)
+        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world,
+                                timeout=datetime.timedelta(seconds=collective_s))
+        for i, case in enumerate(cases):
+            q.put((rank, i, True, fn(rank, world, case)))
+        dist.all_reduce(torch.zeros(1))  # (not barrier(): on a CPU-only group it would open the GPU, see test_dp_gloo.py)
+        dist.destroy_process_group()
+    except Exception:
+        q.put((rank, None, False, traceback.format_exc()))
+
+
+def run_rank_group(fn, world, cases, start_s, case_s, collective_s=120, threads=4):
+    """`world` processes over gloo, spawned ONCE; each runs fn(rank, world, case) over `cases`.  fn must be a module-level
+    function.  -> {"results": [{rank: payload} per case, complete ones only], "error": None or the report every remaining
+    case fails with}.  Every wait has a limit: a collective collective_s, the first result start_s + case_s, each later one
+    case_s.  After a reported exception or a result that does not come, nothing more is fetched, the group is terminated,
+    and nothing is retried."""
+    import queue
+    import socket
+    import torch.multiprocessing as mp
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_rank_entry, args=(fn, r, world, port, q, cases, collective_s, threads)) for r in range(world)]
+    for p in procs:
+        p.start()
+    results, error = [dict() for _ in cases], None
+    wait = start_s + case_s
+    for _ in range(world * len(cases)):
+        try:
+            rank, i, ok, payload = q.get(timeout=wait)
+        except queue.Empty:
+            error = f"no result within {wait} s; complete cases so far: {[len(r) == world for r in results]}"
+            break
+        if not ok:
+            error = f"rank {rank} failed:\n{payload}"
+            break
+        results[i][rank] = payload
+        wait = case_s
+    for p in procs:
+        if error is None:
+            p.join(timeout=30)
+        if p.is_alive():
+            p.terminate()
+            p.join(timeout=10)
+    return {"results": [r if len(r) == world else None for r in results], "error": error}
+
+
+def group_case(group, i):
+    """{rank: payload} of case i of a run_rank_group record; fails with the group's report when the case did not complete."""
+    res = group["results"][i]
+    assert res is not None, group["error"]
+    return res
 
 
 # ======================================================================================================================
