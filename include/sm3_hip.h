@@ -978,6 +978,37 @@ int sm3_conformal_counts(const int64_t* cal_a, const int* cal_order, const int* 
                          int N, int T, int K, int A, int conditional, uint64_t seed, int64_t r0, int c, int point, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Selective-prediction report: the integer counts behind the risk-coverage curve of "answer the confident cases, refer the
+ * rest" -- its area, the 2 x 2 counts at fixed coverages, the largest coverage within a risk level, the counts at fixed
+ * positions -- for the point estimate and for case-resampling bootstrap replicates (csrc/selective.hip, sm3hip/selective.py,
+ * DESIGN.md 8.18; ABI 9, additive).  Integers only.
+ *   8 labels, N cases.  order [8][N] int32 = per label the cases ranked ONCE by the host, most confident first.  packed [8][N]
+ *   int32 = the flags of case n for label t: 1 err (the prediction is wrong), 2 pos (the case is of the selected class), 4 call
+ *   (the selected class is predicted), 8 last (the case's sorted position ends a tie group of the primary key); higher bits are
+ *   ignored.  table [N + 1] int64 = PH of the harmonic tails: PH[0] = 0, PH[r] - PH[r - 1] = round(2^32 * sum_{k = r .. N} 1 / k).
+ *   kcuts [G] int32 in 1 .. N; risks [H][2] int32 = (a, b), the level a / b, 0 <= a <= b, 1 <= b; pcuts [8][Pc] int32 in 0 .. N.
+ *   With integer case multiplicities m[n] >= 0, sum m = N, the case at sorted position j owns the copy ranks C_j + 1 .. C_j +
+ *   m_j, C_j = the copies before j; E_j, TP_j, FP_j, FN_j = the err / call & pos / call & !pos / !call & pos copies before j.
+ *   The record of a (replicate, label), sm3_selective_record(G, H, Pc) = 3 + 4 G + 2 H + 5 Pc int64:
+ *     A = the sum over the err positions j of table[C_j + m_j] - table[C_j];  E = the err copies;  P = the pos copies;
+ *     G x (err, TP, FP, FN) among the first k copies (the position that straddles k gives k - C_j of its copies);
+ *     H x (the largest C_{j+1} over the positions j with `last`, C_{j+1} >= 1 and E_{j+1} * b <= a * C_{j+1}; the E_{j+1} there),
+ *         (0, 0) where no position qualifies;
+ *     Pc x (C_p, E_p, TP_p, FP_p, FN_p), p = N: the totals.
+ * sm3_selective_counts: out [c][8][record] for replicates r = r0 .. r0 + c - 1, one workgroup per (replicate, label); every entry
+ *   of every record is written.  point != 0: m = 1 everywhere, c must be 1, no random words.  Otherwise m_r is the multiplicity
+ *   vector of sm3_report_counts, exactly (counter (d / 4, r, 0, 2)): with one seed, replicate r of every report resamples the same
+ *   cases.  1 <= N <= sm3_report_max_cases(), 1 <= G <= 16, 0 <= H <= 8, 0 <= Pc <= 8, c >= 1, 0 <= r0, r0 + c <= 2^32, no null
+ *   pointer (risks / pcuts may be null where H / Pc is 0); SM3_EINVAL otherwise, before anything is launched; table and out
+ *   8-byte aligned (SM3_EALIGN).  Entries of order are clamped to N - 1 and the cuts and levels to the ranges above: no input can
+ *   make an access leave its array.  No float anywhere, no global atomics: a record is a function of (inputs, seed, r, N) alone.
+ * ------------------------------------------------------------------------------------------ */
+int sm3_selective_record(int G, int H, int Pc);
+int sm3_selective_counts(const int* packed, const int* order, const int64_t* table, const int* kcuts, const int* pcuts,
+                         const int* risks, int64_t* out, int N, int G, int H, int Pc, uint64_t seed, int64_t r0, int c, int point,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Significance of a paired comparison: the integer counts behind the paired randomisation (permutation) test of two sets of
  * predictions of the same cases, and the integer placements behind DeLong's test (csrc/signif.hip, sm3hip/significance.py,
  * DESIGN.md 8.14; ABI 9, additive).

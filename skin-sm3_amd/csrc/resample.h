@@ -1,5 +1,5 @@
-// What the six bootstrap report kernels share (report.hip, calib.hip, operating.hip, retrieval.hip, checklist.hip,
-// conformal.hip: the *_counts_kernel of each).
+// What the seven bootstrap report kernels share (report.hip, calib.hip, operating.hip, retrieval.hip, checklist.hip,
+// conformal.hip, selective.hip: the *_counts_kernel of each).
 //
 // THE RESAMPLING RULE, stated here once for the device (sm3hip/resample.py states it for the host, DESIGN.md 8.10 in prose):
 // replicate r of N cases makes N draws; draw d hits case (w * N) >> 32 in 64-bit integers, w = word d % 4 of Philox4x32-10

@@ -192,6 +192,8 @@ SIGNATURES = {
     "sm3_checklist_record": [],
     "sm3_checklist_counts": [_P, _P, _P, _P, _P, _I, C.c_uint64, _L, _I, _I, _P],
     "sm3_conformal_counts": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
+    "sm3_selective_record": [_I, _I, _I],
+    "sm3_selective_counts": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
     "sm3_signif_counts": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_uint64, _L, _I, _I, _P],
     "sm3_signif_placements": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "sm3_tsne_max_points": [],

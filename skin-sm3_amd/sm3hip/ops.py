@@ -1960,6 +1960,48 @@ def conformal_counts(cal_a, cal_order, cal_y, s, y, colmap, alphas, counts, thr,
                                                _stream()), "sm3_conformal_counts")
 
 
+SELECTIVE_MAX_COVERAGES = 16
+SELECTIVE_MAX_RISKS = 8
+SELECTIVE_MAX_THRESHOLDS = 8
+SELECTIVE_LABELS = 8
+
+
+def selective_record(G, H, Pc):
+    """int64 entries of one (replicate, label) record of sm3_selective_counts (sm3_selective_record)."""
+    return 3 + 4 * G + 2 * H + 5 * Pc
+
+
+def selective_counts(packed, order, table, kcuts, pcuts, risks, out, seed, r0, point=False):
+    """out [c, 8, 3 + 4 G + 2 H + 5 Pc] int64 = (A, E, P, G x (err, TP, FP, FN) among the first k copies, H x (the largest cut
+    within the risk level, its errors), Pc x (C, E, TP, FP, FN) at a fixed position) of the 8 labels for bootstrap replicates
+    r0 .. r0 + c - 1, or for the point estimate (point: c = 1, every case once) (sm3_selective_counts).  packed [8, N] int32 = err
+    | pos << 1 | call << 2 | last << 3 per (label, case); order [8, N] int32 = the cases, most confident first; table [N + 1]
+    int64 = selective.harmonic_table(N); kcuts [G] int32 in [1, N]; pcuts [8, Pc] int32 in [0, N]; risks [H, 2] int32 = (a, b)
+    with 0 <= a <= b, 1 <= b; pcuts and risks may be empty."""
+    for t, n in ((packed, "packed"), (order, "order"), (kcuts, "kcuts"), (pcuts, "pcuts"), (risks, "risks")):
+        _chk(t, torch.int32, n)
+    for t, n in ((table, "table"), (out, "out")):
+        _chk(t, torch.int64, n)
+    if packed.dim() != 2 or table.dim() != 1 or kcuts.dim() != 1 or pcuts.dim() != 2 or risks.dim() != 2 or out.dim() != 3:
+        raise ValueError("selective_counts: packed, order [8, N], table [N + 1], kcuts [G], pcuts [8, Pc], risks [H, 2] and out [c, 8, R]")
+    L, N = packed.shape
+    G, Pc, H, c = kcuts.shape[0], pcuts.shape[1], risks.shape[0], out.shape[0]
+    if not 1 <= N <= REPORT_MAX_CASES:
+        raise ValueError(f"selective_counts: {N} cases, 1 to {REPORT_MAX_CASES} are supported")
+    if not 1 <= G <= SELECTIVE_MAX_COVERAGES or H > SELECTIVE_MAX_RISKS or Pc > SELECTIVE_MAX_THRESHOLDS:
+        raise ValueError(f"selective_counts: {G} coverage cuts, {H} risk levels, {Pc} position cuts; 1 to {SELECTIVE_MAX_COVERAGES}, "
+                         f"at most {SELECTIVE_MAX_RISKS} and at most {SELECTIVE_MAX_THRESHOLDS} are supported")
+    if L != SELECTIVE_LABELS or tuple(order.shape) != (L, N) or tuple(table.shape) != (N + 1,) or tuple(pcuts.shape) != (L, Pc) or \
+            tuple(risks.shape) != (H, 2) or tuple(out.shape) != (c, L, selective_record(G, H, Pc)):
+        raise ValueError("selective_counts: packed, order [8, N], table [N + 1], kcuts [G], pcuts [8, Pc], risks [H, 2] and out [c, 8, "
+                         "3 + 4 G + 2 H + 5 Pc] do not match")
+    _replicates_chk("selective_counts", seed, point, c, "record")
+    with _prof("selective_counts", 0.0, 4.0 * 2 * L * N * c):
+        check(_lib.load().sm3_selective_counts(_ptr(packed), _ptr(order), _ptr(table), _ptr(kcuts), _ptr(pcuts) if Pc else None,
+                                               _ptr(risks) if H else None, _ptr(out), N, G, H, Pc, seed, int(r0), c,
+                                               int(bool(point)), _stream()), "sm3_selective_counts")
+
+
 OPERATING_MAX_LEVELS = 32  # sm3_operating_max_levels(): entries of each of the two floor lists and of the fixed positions
 
 

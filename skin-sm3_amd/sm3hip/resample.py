@@ -1,5 +1,5 @@
-"""What the five case-resampling bootstrap reports share: report.py (evaluation), calibration.py, operating.py, retrieval.py,
-checklist.py.
+"""What the case-resampling bootstrap reports share: report.py (evaluation), calibration.py, operating.py, retrieval.py,
+checklist.py, conformal.py, selective.py.
 
 THE RESAMPLING RULE (csrc/resample.h states it for the device, DESIGN.md 8.10 in prose; the five modules point here).  Integer
 case multiplicities m[n] >= 0 with sum m = N weigh every count of a report; the point estimate has m = 1.  Replicate r makes N

@@ -56,6 +56,18 @@ refits the thresholds in every replicate (--conformal-fixed: keeps the point thr
 every other report's.  --conformal-scaled divides the logits of both files by the temperatures fitted on VAL.pt.  Written to
 <name>_conformal.json / .csv, and with --against OTHER.pt plus --against-fit-on OTHER_VAL.pt (the same cases as VAL.pt) the
 paired difference to <name>_conformal_compare.json.
+
+    python tools/eval_report.py logs/linear/test_predictions.pt --bootstrap 2000 --selective --selective-score margin \
+        --selective-risk 0.05 0.1 --fit-on logs/linear/val_predictions.pt
+
+--selective adds the selective-prediction report (sm3hip/selective.py: the cases ranked by --selective-score msp|margin|entropy|
+tta-range, the area under the risk-coverage curve, selective risk and sens / spec / PPV / NPV of the retained cases and the
+share of referred positives at the --selective-coverage levels, the largest coverage within each --selective-risk level) with
+the SAME bootstrap replicates, written to <name>_selective.json / .csv.  tta-range ranks by the range of the test-time
+augmentation views and needs PRED.pt to carry the "tta" record, as val_predictions_tta.pt does.  With --fit-on VAL.pt the
+thresholds of the risk level --selective-rule (default 0.1) are fitted on VAL.pt and PRED.pt is also reported at them, in the
+same files; with --against OTHER.pt the paired difference goes to <name>_selective_compare.json.  Without the flag nothing of
+this is computed, printed or written.
 """
 import argparse
 import os
@@ -72,7 +84,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 import eval_cli  # noqa: E402
-from sm3hip import calibration, checklist, conformal, operating, report, resample, significance  # noqa: E402
+from sm3hip import calibration, checklist, conformal, operating, report, resample, selective, significance  # noqa: E402
 
 
 def get_parser():
@@ -93,6 +105,7 @@ def get_parser():
     conformal.add_flags(p)
     p.add_argument("--against-fit-on", metavar="OTHER_VAL.pt", default=None,
                    help="with --conformal and --against: the file OTHER.pt's thresholds are fitted on (the cases of --fit-on)")
+    selective.add_flags(p)
     return p
 
 
@@ -199,6 +212,47 @@ def conform(args, preds, targets, kw, out, stem, dev, fit=None):
     return result
 
 
+def _selective_score(args, path, preds, dev):
+    """What --selective-score asks for of the predictions in `path`: a name, or the tensor of tta-range."""
+    if args.selective_score != "tta-range":
+        return args.selective_score
+    return selective.tta_range_score(preds, torch.load(path, map_location=dev, weights_only=False).get("tta"))
+
+
+def select(args, preds, targets, kw, out, stem, dev):
+    """The --selective part: prints the tables, writes the files, returns what it computed."""
+    if targets.shape[0] > report.MAX_CASES:
+        print(selective.stats_line(None), flush=True)
+        return {}
+    skw = dict(kw, **selective.flag_settings(args))
+    score = _selective_score(args, args.pred, preds, dev)
+    thr = None
+    if args.fit_on:
+        fit_preds, fit_targets = report.load_predictions(args.fit_on, dev)
+        thr = selective.fit_thresholds(fit_preds, fit_targets, args.selective_rule,
+                                       _selective_score(args, args.fit_on, fit_preds, dev))
+        print(f"thresholds fitted on {args.fit_on} at risk {args.selective_rule}: " + " ".join(
+            f"{n} {float(v):.4f}" for n, v in zip(selective.CLASSES_NAME, thr)), flush=True)
+    sel = selective.selective_report(preds, targets, **dict(skw, score=score, thresholds=thr))
+    sel["score"] = args.selective_score
+    if args.fit_on:
+        sel.update({"rule": args.selective_rule, "fit_on": args.fit_on})
+    print(selective.format_table(sel), flush=True)
+    print(selective.stats_line(sel), flush=True)
+    selective.save(sel, out, stem + "_selective")
+    result = {"selective": sel}
+    if args.against:
+        other_preds, other_targets = report.load_predictions(args.against, dev)
+        other = selective.selective_report(other_preds, other_targets,
+                                           **dict(skw, score=_selective_score(args, args.against, other_preds, dev)))
+        cmp = selective.compare(sel, other)
+        print(f"{args.pred} - {args.against}", flush=True)
+        print(selective.format_compare(cmp), flush=True)
+        resample.write_json(cmp, os.path.join(out, stem + "_selective_compare.json"))
+        result.update({"selective_other": other, "selective_compare": cmp})
+    return result
+
+
 def signify(args, preds, targets, out, stem, dev):
     """The --significance part: prints the table, writes the files, returns what it computed."""
     other, other_targets = report.load_predictions(args.against, dev)
@@ -225,6 +279,11 @@ def main(argv=None):
     if args.conformal:
         try:
             conformal.check_flags(args)
+        except ValueError as e:
+            parser.error(str(e))
+    if args.selective:
+        try:
+            selective.check_flags(args)
         except ValueError as e:
             parser.error(str(e))
     eval_cli.check_report_flags(args)
@@ -256,6 +315,8 @@ def main(argv=None):
         result.update(check(args, preds, targets, kw, out, stem, dev))
     if args.conformal:
         result.update(conform(args, preds, targets, kw, out, stem, dev, result.get("fit")))
+    if args.selective:
+        result.update(select(args, preds, targets, kw, out, stem, dev))
     return result
 
 
