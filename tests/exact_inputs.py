@@ -1,5 +1,5 @@
 """Test helper: exact-input generation and the checks of the bit-exact kernel suites (test_exact_gemm_gpu.py,
-test_exact_bn_gpu.py).
+test_exact_bn_gpu.py, test_exact_stem_dgrad_gpu.py).
 
 Every operand is a small integer times a power of two.  A product of such operands is exact in fp32, and so is every
 partial sum whose magnitude stays below 2^24 quanta, whatever the summation order.  need_exact / need_repr assert those
@@ -95,6 +95,36 @@ def stored(v, dt):
 def pick(gen, vals, shape):
     """Elements of the 1-D tensor vals drawn uniformly."""
     return vals[torch.randint(0, len(vals), shape, generator=gen)]
+
+
+def stem_wgrad_case(dt, N, H, W, views, seed):
+    """Stem weight gradient with bn1's backward apply on the operand path: dw = conv2d_weight(x, dxo) with
+    dxo = gamma * invstd * (dz - gs0 / count - xhat * gs1 / count), xhat = (xo - mean) * invstd, per view.  Dyadic inputs and a
+    power-of-two count keep dxo exact in fp32 and representable in dt (the kernel rounds it to dt before the MFMA)."""
+    g = torch.Generator().manual_seed(seed)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    M = N * Ho * Wo
+    x = draw(g, (N, 3, H, W), 3, 0.6, -1)
+    dz = draw(g, (M, 64), 3, 0.6, 0)
+    xo = draw(g, (M, 64), 2, 0.9, 0)
+    mean = draw(g, (views, 64), 1, 0.8, -1)
+    invstd = torch.tensor([0.5, 1.0])[torch.randint(0, 2, (views, 64), generator=g)].double()
+    gamma = torch.tensor([0.5, 1.0])[torch.randint(0, 2, (64,), generator=g)].double()
+    count = 1024.0
+    gs = torch.cat([draw(g, (views, 64), 2, 0.8, -1), draw(g, (views, 64), 1, 0.8, -1)], 1) * count
+    ls = draw(g, (views, 128), 9, 0.9, 0)
+    v = torch.arange(M) // (M // views)
+    xh = (xo - mean[v]) * invstd[v]
+    dxo = gamma * invstd[v] * (dz - gs[v, :64] / count - xh * gs[v, 64:] / count)
+    need_repr(dxo, dt, "stem dxo")
+    dxo_n = dxo.reshape(N, Ho, Wo, 64).permute(0, 3, 1, 2)
+    dw = torch.nn.grad.conv2d_weight(x, (64, 3, 7, 7), dxo_n, stride=2, padding=3).permute(0, 2, 3, 1).reshape(64, 147)
+    dwa = torch.nn.grad.conv2d_weight(x.abs(), (64, 3, 7, 7), dxo_n.abs(), stride=2, padding=3)
+    need_exact(dwa, quantum(x) * quantum(dxo), "stem dw")
+    for t, nm in ((dz, "dz"), (xo, "xo")):
+        need_repr(t, dt, f"stem {nm}")
+    return dict(x=x, dz=dz, xo=xo, mean=mean, invstd=invstd, gamma=gamma, count=count, gs=gs, ls=ls, dw=dw,
+                dgamma=ls[:, 64:].sum(0), dbeta=ls[:, :64].sum(0))
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -27,7 +27,7 @@ import torch
 import torch.nn.functional as F
 
 from exact_inputs import (SENTINEL, Guarded, _dev, draw, env, ep_affine_exact, mask_bytes, need_exact, need_repr, pick,
-                          quantum, same)
+                          quantum, same, stem_wgrad_case)
 
 F32, BF16, F16 = torch.float32, torch.bfloat16, torch.float16
 DTYPES = [F32, BF16, F16]
@@ -1168,8 +1168,9 @@ def test_f16_relu_bits_at_the_underflow_threshold():
 # ------------------------------------------------------------------------------------------------------------------------
 # direct stem (7x7 / 2 / 3, 64 output channels)
 # ------------------------------------------------------------------------------------------------------------------------
-# N, H, W, BatchNorm views: odd sizes, an image wider than one 128-pixel tile, two views
-STEM_GEOMS = [(2, 32, 32, 2), (1, 13, 7, 1), (3, 9, 70, 1), (1, 1, 1, 1), (4, 10, 12, 2)]
+# N, H, W, BatchNorm views: odd sizes, an image wider than one 128-pixel tile, two views; the last has 1040 tiles, more than
+# any grid cap of these persistent kernels (768, and 512 for stem_conv_fwd16): every workgroup runs a second tile
+STEM_GEOMS = [(2, 32, 32, 2), (1, 13, 7, 1), (3, 9, 70, 1), (1, 1, 1, 1), (4, 10, 12, 2), (1040, 2, 2, 2)]
 
 
 def stem_case(N, H, W, seed):
@@ -1182,36 +1183,6 @@ def stem_case(N, H, W, seed):
     need_exact(y.abs().sum(0), quantum(y), "stem partial sum")  # any partial row is a subset of these sums
     need_exact((y * y).sum(0), quantum(y) ** 2, "stem partial sum sq")
     return x, w, y
-
-
-def stem_wgrad_case(dt, N, H, W, views, seed):
-    """Stem weight gradient with bn1's backward apply on the operand path: dw = conv2d_weight(x, dxo) with
-    dxo = gamma * invstd * (dz - gs0 / count - xhat * gs1 / count), xhat = (xo - mean) * invstd, per view.  Dyadic inputs and a
-    power-of-two count keep dxo exact in fp32 and representable in dt (the kernel rounds it to dt before the MFMA)."""
-    g = torch.Generator().manual_seed(seed)
-    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    M = N * Ho * Wo
-    x = draw(g, (N, 3, H, W), 3, 0.6, -1)
-    dz = draw(g, (M, 64), 3, 0.6, 0)
-    xo = draw(g, (M, 64), 2, 0.9, 0)
-    mean = draw(g, (views, 64), 1, 0.8, -1)
-    invstd = torch.tensor([0.5, 1.0])[torch.randint(0, 2, (views, 64), generator=g)].double()
-    gamma = torch.tensor([0.5, 1.0])[torch.randint(0, 2, (64,), generator=g)].double()
-    count = 1024.0
-    gs = torch.cat([draw(g, (views, 64), 2, 0.8, -1), draw(g, (views, 64), 1, 0.8, -1)], 1) * count
-    ls = draw(g, (views, 128), 9, 0.9, 0)
-    v = torch.arange(M) // (M // views)
-    xh = (xo - mean[v]) * invstd[v]
-    dxo = gamma * invstd[v] * (dz - gs[v, :64] / count - xh * gs[v, 64:] / count)
-    need_repr(dxo, dt, "stem dxo")
-    dxo_n = dxo.reshape(N, Ho, Wo, 64).permute(0, 3, 1, 2)
-    dw = torch.nn.grad.conv2d_weight(x, (64, 3, 7, 7), dxo_n, stride=2, padding=3).permute(0, 2, 3, 1).reshape(64, 147)
-    dwa = torch.nn.grad.conv2d_weight(x.abs(), (64, 3, 7, 7), dxo_n.abs(), stride=2, padding=3)
-    need_exact(dwa, quantum(x) * quantum(dxo), "stem dw")
-    for t, nm in ((dz, "dz"), (xo, "xo")):
-        need_repr(t, dt, f"stem {nm}")
-    return dict(x=x, dz=dz, xo=xo, mean=mean, invstd=invstd, gamma=gamma, count=count, gs=gs, ls=ls, dw=dw,
-                dgamma=ls[:, 64:].sum(0), dbeta=ls[:, :64].sum(0))
 
 
 def test_stem_preconditions():
