@@ -11,21 +11,28 @@ namespace {
 // dyn (nullable): {loss scale, number of optimizer steps taken so far} on the device -- the fp16 mode's GradScaler state.
 // With it the gradient is also divided by the loss scale and the bias corrections use steps_taken + 1: a step skipped
 // for an overflow does not advance Adam's step count, as with torch.optim.AdamW under GradScaler.step().
+// The corrections are formed in double and rounded once, as sm3_adamw forms them on the host: in fp32 1 - beta2^step
+// cancels (step 2: 0.002 from 0.998, 3e-5 of itself lost).  The device's double pow need not round as the host's does,
+// so equal bits with sm3_adamw are not guaranteed at every step: two doubles a few ulp apart round to the same float
+// except next to a rounding boundary, and the first steps under a loss scale of 2^k are pinned equal to the same steps
+// without one (tests/test_trainer_schedule_gpu.py: steps 1 to 3).  DYN is a template parameter so that the
+// double-precision pow stays out of the code of the plain launch.
 struct AdamDyn {
     const float* loss_scale;
     const int32_t* steps_taken;
 };
+template <bool DYN>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
                                                     float b1, float b2, float eps, float wd, float inv_bc1,
                                                     float inv_sqrt_bc2, float gscale, const int32_t* found_inf,
                                                     AdamDyn dyn) {
     if (found_inf && *found_inf) return;
-    if (dyn.loss_scale) {
+    if (DYN) {
         gscale /= dyn.loss_scale[0];
-        const float step = (float)(dyn.steps_taken[0] + 1);
-        inv_bc1 = 1.f / (1.f - powf(b1, step));
-        inv_sqrt_bc2 = 1.f / sqrtf(1.f - powf(b2, step));
+        const double step = (double)(dyn.steps_taken[0] + 1);
+        inv_bc1 = (float)(1.0 / (1.0 - pow((double)b1, step)));
+        inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
     }
     const int64_t n4 = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -77,7 +84,7 @@ extern "C" int sm3_adamw(float* p, const float* g, float* m, float* v, int64_t n
     int64_t blocks = ((n >> 2) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
                        beta1, beta2, eps, weight_decay, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), grad_scale,
                        found_inf, AdamDyn{nullptr, nullptr});
     SM3_CHECK_LAUNCH();
@@ -92,7 +99,7 @@ extern "C" int sm3_adamw_dynamic(float* p, const float* g, float* m, float* v, i
     int64_t blocks = ((n >> 2) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
                        beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale, found_inf, AdamDyn{loss_scale, steps_taken});
     SM3_CHECK_LAUNCH();
     return 0;

@@ -390,6 +390,8 @@ class SM3Trainer:
             # GradScaler.step() + update() (backbone_train.py:126-127) without a host synchronisation: inf / nan check
             # of the (all-reduced, still scaled) gradients, unscale + AdamW skipped on overflow, scale update
             ops.check_finite(st.flat_g, sc["found_inf"])
+            if self.target_momentum is not None:
+                self._ema_skip = sc["found_inf"].clone()  # loss_scale_update clears the flag
             ops.adamw_dynamic(st.flat_p, st.flat_g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
                               self.wd, 1.0 / self.world, sc["scale"], sc["steps"], sc["found_inf"])
             ops.loss_scale_update(sc["scale"], sc["found_inf"], sc["tracker"], sc["steps"], self.scaler_cfg[1],
@@ -397,6 +399,8 @@ class SM3Trainer:
             self.step_count += 1  # calls made; the number of optimizer steps TAKEN lives on the device (steps_taken())
         if self.target_momentum is not None:
             skip = self.__dict__.pop("_p2p_skip", None)
+            if skip is None:
+                skip = self.__dict__.pop("_ema_skip", None)  # fp16: this step's overflow flag
             if skip is not None:
                 # a skipped step must not move the target either: the EMA factor becomes 0 on the device, no host read
                 w = (1.0 - self.target_momentum) * (skip == 0).to(torch.float32)
